@@ -19,6 +19,11 @@ and one all-gather of the per-rank rows that lands in device memory (the cell pa
 offset there: one host wait per step).  --full-halo / --host-offsets switch the two back.  --scaling weak: each rank owns one 1024^3 block of a 1024x1024x(1024 N) volume (the
 block repeats along z).  configs[4]: --workload noise --size 2048.
 
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, ms_per_step, the pass's roofline
+from the timed steps, host_side).  --full adds what the headline does not need: per-stage times, the mesh's copy to the
+host, the slab / series / first-call probes, the CPU baseline and the byte-for-byte parity check against the oracle.
+--dump-outputs DIR writes the mesh of the last timed step as .npy files (dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -242,6 +247,25 @@ def cpu_baseline(pkg, torch, args, device, gpu_mesh=None, gpu_iterations=None):
     }
 
 
+DUMP_ROWS = 1 << 20     # rows per array in --dump-outputs: at most 12 MiB of points + 32 MiB of quads
+
+
+def dump_outputs(path, mesh):
+    """--dump-outputs: the mesh a caller of the timed path receives from its last step, as path/<name>.npy --
+    mesh_counts (points, cells), points (float32 x, y, z) and cells (vertex ids as float64, exact below 2^53).  A mesh
+    of more than DUMP_ROWS rows is written as a fixed seeded sample of rows, ascending, drawn from the row count alone:
+    two builds that agree on the counts are compared on the same rows."""
+    os.makedirs(path, exist_ok=True)
+
+    def sample(a, seed):
+        if len(a) <= DUMP_ROWS:
+            return a
+        return a[np.sort(np.random.default_rng(seed).choice(len(a), DUMP_ROWS, replace=False))]
+    np.save(os.path.join(path, "mesh_counts.npy"), np.array([len(mesh.points), len(mesh.cells)], dtype=np.float64))
+    np.save(os.path.join(path, "points.npy"), sample(mesh.points, 740).astype(np.float32))
+    np.save(os.path.join(path, "cells.npy"), sample(mesh.cells, 741).astype(np.float64))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -344,8 +368,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--workload", default="marschner_lobb", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-stage times, the mesh's copy to the "
+                         "host, the slab / series / first-call probes, the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the mesh of the last one as DIR/*.npy (a fixed seeded sample of a large "
+                         "mesh, see dump_outputs); the inputs depend on the arguments alone")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="edge of the cube the CPU baseline is timed on (default: --size, i.e. the bench volume itself; 0 = skip)")
+                    help="--full: edge of the cube the CPU baseline is timed on (default: --size, i.e. the bench volume itself; 0 = skip)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N>1: strong = one size^3 volume cut into N slabs (default), weak = one size^3 block per rank")
     ap.add_argument("--check-against-single", action="store_true",
@@ -373,7 +403,7 @@ def main():
                     help="skip cuberille_warm_up (its toy extraction launches a few tiny kernels: profiles/collect.sh keeps them out "
                          "of the per-kernel averages this way; the untimed warm-up steps do the warming then)")
     ap.add_argument("--no-slab-probe", action="store_true",
-                    help="N=1: skip the extra measurement of one 1/8 slab (what a rank of an 8-GPU run does per step)")
+                    help="N=1, --full: skip the extra measurement of one 1/8 slab (what a rank of an 8-GPU run does per step)")
     ap.add_argument("--launch-timeout", type=int, default=600,
                     help="--gpus N > 1 from a bare shell: seconds one attempt of the self-started ranks may take")
     ap.add_argument("--no-launch-fallback", action="store_true",
@@ -383,6 +413,8 @@ def main():
                          "the rank gives up with exit code 3 (0 = wait forever)")
     ap.add_argument("--fallback-note", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a bare `python bench.py --gpus N`: the ranks are started HERE, as a child process, before this process has
@@ -532,14 +564,22 @@ def main():
             host_side[k] += int(sh.stats[k])
     barrier()
     dt = time.perf_counter() - t0
-    acc = {k: 0.0 for k in stage_keys}
-    ex.debug_option("stage_timing", 1)
-    for _ in range(STAGE_REPS):
-        r2 = sh.extract(buf, prm)
-        for k in stage_keys:
-            acc[k] += getattr(r2, k)
-    ex.debug_option("stage_timing", 0)
-    barrier()
+    if args.dump_outputs:
+        whole = sh.gather_mesh(dst=0)          # every rank takes part; rank 0 holds the whole mesh
+        if rank == 0:
+            dump_outputs(args.dump_outputs, whole)
+        del whole
+    stages = None
+    if args.full:
+        acc = {k: 0.0 for k in stage_keys}
+        ex.debug_option("stage_timing", 1)
+        for _ in range(STAGE_REPS):
+            r2 = sh.extract(buf, prm)
+            for k in stage_keys:
+                acc[k] += getattr(r2, k)
+        ex.debug_option("stage_timing", 0)
+        stages = {k: acc[k] / STAGE_REPS for k in stage_keys}
+        barrier()
     if world > 1:
         cdev = "cpu" if rehearsal else device
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -581,15 +621,13 @@ def main():
 
     if rank == 0:
         voxels = float(n) * n * gnz
-        stages = {k: acc[k] / STAGE_REPS for k in stage_keys}
         # B_A = Nx*Ny*Nz*sizeof(pixel), every voxel this rank's launch reads counted once
         launch_slices = (sh.thi - sh.tlo) if (world > 1 and sh.thin) else (sh.hi - sh.lo)
         alg_bytes = float(n) * n * launch_slices * np.dtype(dtype).itemsize
-        classify_gbs = alg_bytes / (stages["ms_classify"] * 1e-3) / 1e9
         pass_ms = live["ms_pass"] / args.steps          # HIP events around the pass, every step of the timed region
-        if pass_ms <= 0.0:                              # (volumes of a few M voxels get one event pair only: take the stage events)
+        if pass_ms <= 0.0 and stages is not None:       # (volumes of a few M voxels get one event pair only: take the stage events)
             pass_ms = stages["ms_classify"] + stages["ms_count"]
-        pass_gbs = alg_bytes / (pass_ms * 1e-3) / 1e9
+        pass_gbs = alg_bytes / (pass_ms * 1e-3) / 1e9 if pass_ms > 0.0 else None
         traffic, traffic_src = measured_traffic(args, world, alg_bytes)
         out = {
             "metric": "Mvoxels/s polygonized + achieved HBM GB/s, 1024^3 float32 @1/2/4/8 GPU",
@@ -617,16 +655,21 @@ def main():
             # library's own stream, averaged over the steps of the timed region
             "roofline": {"bound": "hbm",
                          "kernel": "classify+count+scan pass: k_classify_span/_flat + k_count + k_block_scan",
-                         "achieved": round(pass_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(pass_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src, "algorithmic_bytes": alg_bytes, "pass_ms": round(pass_ms, 4),
-                         "sweep_kernel_alone": {"ms": round(stages["ms_classify"], 4), "achieved": round(classify_gbs, 1),
-                                                "frac": round(classify_gbs / HBM_PEAK_GBS, 4)}},
-            "stages_ms": {k: round(v, 4) for k, v in stages.items()},
-            "stages_ms_source": "%d extractions after the timed region with the per-stage events on "
-                                "(cuberille_debug_set_option stage_timing); ms_total of the timed region: %.4f"
-                                % (STAGE_REPS, live["ms_total"] / args.steps),
+                         "achieved": None if pass_gbs is None else round(pass_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": None if pass_gbs is None else round(pass_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "traffic_source": traffic_src, "algorithmic_bytes": alg_bytes, "pass_ms": round(pass_ms, 4)},
         }
+        if stages is not None:
+            classify_gbs = alg_bytes / (stages["ms_classify"] * 1e-3) / 1e9
+            out["roofline"]["sweep_kernel_alone"] = {"ms": round(stages["ms_classify"], 4), "achieved": round(classify_gbs, 1),
+                                                     "frac": round(classify_gbs / HBM_PEAK_GBS, 4)}
+            out["roofline"]["note"] = ("largest kernel by time is the projection walk (%.0f %% of device time): f64 VALU-bound, "
+                                       "neither an HBM nor an MFMA roofline applies to it" % (
+                                           100.0 * stages["ms_project"] / stages["ms_total"]))
+            out["stages_ms"] = {k: round(v, 4) for k, v in stages.items()}
+            out["stages_ms_source"] = ("%d extractions after the timed region with the per-stage events on "
+                                       "(cuberille_debug_set_option stage_timing); ms_total of the timed region: %.4f"
+                                       % (STAGE_REPS, live["ms_total"] / args.steps))
         # what a step costs besides kernels (rank 0's view; per step, averaged over the timed region)
         out["host_side"] = {"halo_bytes_per_rank": host_side["halo_bytes"] // args.steps,
                             "halo_bit_plane_bytes_per_rank": host_side["halo_bit_bytes"] // args.steps,
@@ -636,9 +679,6 @@ def main():
                             "escaped_walks_per_step": round(host_side["escaped"] / args.steps, 2),
                             "steps_that_fetched_the_deep_halo": host_side["deep_halo_fetched"],
                             "wall_minus_device_ms": round(dt / args.steps * 1e3 - live["ms_total"] / args.steps, 4)}
-        out["roofline"]["note"] = ("largest kernel by time is the projection walk (%.0f %% of device time): f64 VALU-bound, "
-                                   "neither an HBM nor an MFMA roofline applies to it" % (
-                                       100.0 * stages["ms_project"] / stages["ms_total"]))
         if fallback is not None:
             out["fallback"] = fallback
         if single_check is not None:
@@ -646,7 +686,7 @@ def main():
         if gather_ms is not None:
             out["gather_mesh_ms"] = round(gather_ms, 1)
         mesh = None
-        if world == 1:
+        if args.full and world == 1:
             # outside the timed region, reported separately: copying the mesh to the host
             # (1) into host memory the context owns and keeps (cuberille_mesh_host: what the drop-in filter fills its
             # itk::Mesh from) -- the first mesh of the process, then, after one more extraction, the same buffers again;
@@ -665,23 +705,24 @@ def main():
             t0 = time.perf_counter()
             mesh = ex.download()
             out["d2h_mesh_into_fresh_caller_arrays_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
-        if world == 1 and not args.no_slab_probe and n >= 64:
+        probes = args.full and world == 1 and not args.no_slab_probe
+        if probes and n >= 64:
             try:                     # a probe beside the measurement: whatever it runs into, the line is printed
                 out["slab_eighth_probe"] = slab_probe(pkg, torch, ex, buf, n, dtype, prm)
             except Exception as e:   # noqa: BLE001
                 out["slab_eighth_probe"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_slab_probe and n >= 256:
+        if probes and n >= 256:
             try:
                 out["series_two_contexts"] = series_probe(pkg, torch, ex, buf, sh.desc, prm, local_rank, max(args.steps, 10))
             except Exception as e:   # noqa: BLE001
                 out["series_two_contexts"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_slab_probe and n >= 256:
+        if probes and n >= 256:
             try:
                 out["first_calls_on_a_fresh_context"] = first_calls_probe(pkg, torch, buf, sh.desc, prm, local_rank)
             except Exception as e:   # noqa: BLE001
                 out["first_calls_on_a_fresh_context"] = {"error": "%s: %s" % (type(e).__name__, e)}
         parity = None
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             parity, out["cpu_baseline"] = cpu_baseline(pkg, torch, args, device, mesh, int(res.proj_iterations))
             if parity is not None:
                 out["parity_at_bench_size"] = parity

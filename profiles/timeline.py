@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timeline of the cuberille kernels of ONE extraction in a rocprofv3 kernel trace (start / end relative to the
 extraction's first kernel, queue): shows which launches of the pass overlap.
-  rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-slab-probe
+  rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-slab-probe
   python3 profiles/timeline.py DIR [which extraction, default -4]"""
 import csv
 import glob

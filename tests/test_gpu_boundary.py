@@ -13,19 +13,22 @@ from conftest import point_bytes as _point_bytes
 from gpu_helpers import _bench_field, _closed_form_counts_torch, _host_threads, _read_vtk_polydata, run_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+# the reference's drivers, built against the drop-in header by __graft_entry__.build() (oracle/Makefile, target ref)
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
+REF_MISSING = "reference drivers not built: build() makes oracle/_ref/ only where the reference sources are"
 
 
 def test_reference_driver_unchanged(pkg, extractor, oracle, volumes, ctest_cases, tmp_path):
     """The reference's own CuberilleTest01.cxx, compiled UNCHANGED against the drop-in filter header
-    (midas-journal-740_amd/itk; built by __graft_entry__.build() where /root/reference exists), run
+    (midas-journal-740_amd/itk; built into oracle/_ref/ by __graft_entry__.build() where the reference sources are), run
     exactly as its CTest table runs it: `CuberilleTest01 Test01 <in> <out> <iso> <pts> <cells> ...`.
     The driver itself asserts the two counts; the .vtk it writes is compared with the oracle."""
     import os
     import subprocess
     from conftest import GOLDEN, ROOT
-    exe = os.path.join(ROOT, "midas-journal-740_amd", "itk", "build", "CuberilleTest01")
+    exe = os.path.join(REF_BIN, "CuberilleTest01")
     if not os.path.exists(exe):
-        pytest.skip("drop-in driver binary not built (needs /root/reference at build time)")
+        pytest.skip(REF_MISSING)
     for c in ctest_cases:
         out = str(tmp_path / (c["name"] + ".vtk"))
         args = [exe, "Test01", os.path.join(GOLDEN, "data", c["input"]), out, str(c["iso"]), str(c["points"]),
@@ -46,7 +49,7 @@ def test_reference_driver_unchanged(pkg, extractor, oracle, volumes, ctest_cases
         extractor.write_vtk(flat, threads=3)
         assert open(flat, "rb").read() == open(out, "rb").read(), c["name"]
     # the example main of Source/examples.cxx takes the same arguments without the test name
-    exe2 = os.path.join(ROOT, "midas-journal-740_amd", "itk", "build", "Examples")
+    exe2 = os.path.join(REF_BIN, "Examples")
     c = ctest_cases[-1]
     r = subprocess.run([exe2, os.path.join(GOLDEN, "data", c["input"]), str(tmp_path / "e.vtk"), str(c["iso"]),
                         str(c["points"]), str(c["cells"]), str(c["triangles"]), str(c["project"]), "0.2", "0.24", "0.95",
@@ -156,9 +159,9 @@ def test_caller_stream_orders_the_extraction(pkg, oracle, extractor, volumes):
 def test_reference_driver_built_with_a_projection_macro(oracle, volumes, ctest_cases, tmp_path, variant, suffix):
     """The reference's CuberilleTest01.cxx compiled unchanged with -DUSE_ADVANCED_PROJECTION=1 /
     -DUSE_LINESEARCH_PROJECTION=1 against the drop-in header: the macro reaches the device as projection_variant."""
-    exe = os.path.join(ROOT, "midas-journal-740_amd", "itk", "build", "CuberilleTest01_" + suffix)
+    exe = os.path.join(REF_BIN, "CuberilleTest01_" + suffix)
     if not os.path.exists(exe):
-        pytest.skip("drop-in driver binary not built (needs /root/reference at build time)")
+        pytest.skip(REF_MISSING)
     ran = 0
     for c in ctest_cases:
         if not c["project"] or ran >= 4:
