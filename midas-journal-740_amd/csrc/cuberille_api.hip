@@ -18,6 +18,7 @@
 #include <string>
 #include <sys/mman.h>
 #include <thread>
+#include <utility>
 #include <vector>
 
 using namespace cuberille;
@@ -111,7 +112,7 @@ struct cuberille_ctx {
   Totals *hostTotals = nullptr;          // pinned
   uint32_t *hostOcc = nullptr;           // pinned mirror of the per-slice occupancy of the last slab count
   size_t hostOccCap = 0;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[8] = {};                 // the timing marks (enum Mark), recorded by mark()
   Tuning tune;                           // development switches (cuberille_debug_set_option)
   // overlapped ingestion (cuberille_extract_host): pinned staging ring and a copy stream
   hipStream_t copyStream = nullptr;
@@ -123,7 +124,7 @@ struct cuberille_ctx {
   int aliasZ = -1;                       // local slice whose Q1 source is unresolved (the first occupied counted slice), -1
   bool slabMode = false;                 // the last count was given a slab
   bool thinHalo = false;                 // ... with CUBERILLE_SLAB_THIN_HALO: walks that leave the buffer are put aside
-  bool pointsStartedEarly = false;       // cuberille_emit_points ran ahead of cuberille_emit (two device intervals to add up)
+  bool pointsStartedEarly = false;       // split emit: the vertex phase ran ahead of the cells (two device intervals to add up)
   bool escapeChecked = false;            // THIN_HALO: the number of escaped walks of the current vertex phase has been read back
   // cuberille_step_begin / _end: what the previous extraction on this context produced sizes the blind launches
   bool warm = false;                     // cuberille_warm_up has run its toy extraction
@@ -160,6 +161,10 @@ struct cuberille_ctx {
 };
 
 namespace {
+
+// The timing marks of an extraction, one event each (cuberille_ctx::ev); which a mode records: mark(), by finish_result.
+enum Mark { PASS_BEGIN, CLASSIFY_END, PASS_END, CELLS_BEGIN, POINTS_BEGIN, POINTS_END, PROJECT_END, END };
+hipError_t mark(cuberille_ctx *c, Mark m);
 
 int fail(cuberille_ctx *c, int code, const std::string &msg) {
   if (c) c->err = msg; else g_create_error = msg;
@@ -424,6 +429,86 @@ void deriche_setup(double sigma, double spacing, int order, double out[20]) {
   for (int i = 0; i < 20; i++) out[i] = v[i];
 }
 
+// The layout of a whole image (count_prepare narrows it to a slab's owned range).
+Grid whole_grid(const cuberille_image_desc *img, const Tuning &t) {
+  Grid g{};
+  g.nx = (int)img->dims[0]; g.ny = (int)img->dims[1]; g.nzb = (int)img->dims[2];
+  g.W = (g.nx + 63) / 64;
+  g.lastpos = (g.nx - 1) & 63;
+  g.wShift = g.yShift = -1;
+  for (int b = 0; b < 31; b++) {
+    if (g.W == (1 << b)) g.wShift = b;
+    if (g.ny == (1 << b)) g.yShift = b;
+  }
+  g.gnz = g.nzb; g.zglob0 = 0; g.oz0 = 0; g.oz1 = g.nzb;
+  g.cmapLinear = t.cmap_linear;
+  return g;
+}
+
+// ---- workspace sizes: the bytes of every device buffer, reserved by count_prepare and emit_points_phase at their points of
+// an extraction and by cuberille_warm_up ahead of one.  A required buffer that cannot be had fails the call
+// (CUBERILLE_ERR_HIP); an optional one (0 bytes: not wanted) is done without.
+struct CountSizes {
+  size_t nwords, nseg;                                     // counted words, 64-word scan segments
+  size_t bits, occ, prefix, segPre, blockTot, blockBase;   // required
+  size_t flatBits, vqueue;                                 // optional
+};
+
+CountSizes count_sizes(const Grid &g, const Tuning &t) {
+  const size_t slice = (size_t)g.ny * g.W, nwords = (size_t)(g.oz1 - g.cz0) * slice, nblk = (nwords + COUNT_WB - 1) / COUNT_WB;
+  CountSizes s;
+  s.nwords = nwords; s.nseg = (nwords + 63) / 64;
+  s.bits = (slice * g.nzb + slice) * sizeof(u64);   // (+ one slice past the buffer: quirk Q1's source from the rank below)
+  s.occ = sizeof(Totals) + (size_t)g.nzb * sizeof(u32);   // the totals and the per-slice occupancy: one memset zeroes both
+  s.prefix = (nwords + 4) * sizeof(u32);            // (+ the tail of a 16-byte read at the last words: locate_word_wave)
+  s.segPre = s.nseg * sizeof(u64);
+  s.blockTot = (nblk + 2 * (nblk / 8192 + 1)) * sizeof(u64);   // (+ the sums of its chunks of 8192: k_block_partial)
+  s.blockBase = nblk * 2 * sizeof(u64);
+  s.flatBits = g.nx % 64 != 0 ? (slice * g.nzb + 32) * sizeof(u64) : 0;   // ragged rows: one flat stream, then rows
+  s.vqueue = nwords < 0xffffffffULL && !t.no_vqueue ? nwords * sizeof(u32) : 0;
+  return s;
+}
+
+// The dense corner -> vertex map: 4 B per lattice corner 0..nx, 0..ny, 0..nzb + 1 (the last plane also takes the handed-over
+// one), in bricks or row-major (Tuning::cmap_linear).  Optional.
+size_t cmap_bytes(const Grid &g, const Tuning &t) {
+  if (t.no_cmap) return 0;
+  return g.cmapLinear ? (size_t)(g.nx + 1) * (g.ny + 1) * (g.nzb + 2) * sizeof(u32)
+                      : (((size_t)g.nx + 4) >> 2) * (((size_t)g.ny + 4) >> 2) * (((size_t)g.nzb + 3) >> 1) * 32 * sizeof(u32);
+}
+
+// The emit's buffers for nV points (ghost + owned) with room behind them for the rank below's plane of planeCorners (quirk Q1
+// across slabs), nQ quads of totQ counted ones.  `cover`: what the next extraction on the context asks for when it launches
+// blindly from these counts (cuberille_step_begin: + 25 %), taken where a buffer has to grow anyway (dyn: they are that).
+struct Want { size_t bytes, cover; };
+struct EmitSizes {
+  Want points, cells;                 // required
+  Want headV, headQ;                  // optional (4 B per 64 outputs)
+  size_t cmap, escCap;                // optional; THIN_HALO: entries of the escape list (required there)
+};
+
+EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u64 nV, u64 totQ, u64 nQ, size_t planeCorners,
+                     size_t nwords) {
+  const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
+  const size_t quad = (triangles ? 6 : 4) * sizeof(u64);
+  const bool heads = nwords < 0xffffffffULL && !t.no_heads;
+  EmitSizes s;
+  s.points = {(size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float), (size_t)(nextV + planeCorners) * 3 * sizeof(float)};
+  s.cells = {(size_t)(nQ ? nQ : 1) * quad, (size_t)nextQ * quad};
+  s.headV = heads ? Want{(size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)} : Want{0, 0};
+  s.headQ = heads ? Want{(size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)} : Want{0, 0};
+  s.cmap = nV < 0xffffffffULL ? cmap_bytes(g, t) : 0;   // (more than 2^32 vertices: the cell kernel recomputes ids instead)
+  s.escCap = nV < ESCAPE_LIST_CAP ? (size_t)nV + 1 : (size_t)ESCAPE_LIST_CAP;
+  return s;
+}
+
+// An optional buffer: its pointer, or null when it is not wanted or cannot be had
+void *optional(DevBuf &b, size_t bytes, size_t cover = 0) {
+  if (bytes && b.reserve_covering(bytes, cover) == hipSuccess) return b.p;
+  (void)hipGetLastError();
+  return nullptr;
+}
+
 // First half of a count: layout, parameters, workspace, zeroed state.  The caller then thresholds the slices
 // (all at once, or z-range by z-range as they arrive) and calls count_finish.
 int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
@@ -440,22 +525,12 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
-  Grid g{};
-  g.nx = (int)img->dims[0]; g.ny = (int)img->dims[1]; g.nzb = (int)img->dims[2];
-  g.W = (g.nx + 63) / 64;
-  g.lastpos = (g.nx - 1) & 63;
-  g.wShift = g.yShift = -1;
-  for (int b = 0; b < 31; b++) {
-    if (g.W == (1 << b)) g.wShift = b;
-    if (g.ny == (1 << b)) g.yShift = b;
-  }
+  Grid g = whole_grid(img, c->tune);
   Geo geo{};
   Params p{};
   resolve(img, prm, geo, p);
   const bool whole = !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);   // (all-zero slab = whole volume)
-  if (whole) {
-    g.gnz = g.nzb; g.zglob0 = 0; g.oz0 = 0; g.oz1 = g.nzb;
-  } else {
+  if (!whole) {
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "slab ranges are inconsistent with the buffer");
@@ -486,40 +561,26 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     g.oz1 = (int)(slab->own_z1 - slab->z_begin);
   }
   g.cz0 = g.oz0 > 0 ? g.oz0 - 1 : 0;
-  g.cmapLinear = c->tune.cmap_linear;
-  const size_t nrowsAll = (size_t)g.ny * g.nzb;
-  const size_t nwordsAll = nrowsAll * g.W;
-  const size_t nwords = (size_t)(g.oz1 - g.cz0) * g.ny * g.W;
-  const size_t nseg = (nwords + 63) / 64;
-  const size_t nblk = (nwords + COUNT_WB - 1) / COUNT_WB;
-  if (nseg > 0x7fffffffULL) return fail(c, CUBERILLE_ERR_LIMIT, "volume too large for one device scan");
+  const CountSizes sz = count_sizes(g, c->tune);
+  if (sz.nseg > 0x7fffffffULL) return fail(c, CUBERILLE_ERR_LIMIT, "volume too large for one device scan");
 
   // ---- workspace ----------------------------------------------------------------------------------
-  // (+ one slice past the buffer: a slab may be handed the source slice of quirk Q1 from the rank below)
-  HIP_TRY(c, c->bits.reserve((nwordsAll + (size_t)g.ny * g.W) * sizeof(u64)));
+  HIP_TRY(c, c->bits.reserve(sz.bits));
   c->slabMode = !whole;
   c->thinHalo = !whole && (slab->flags & CUBERILLE_SLAB_THIN_HALO) != 0 && p.project;
   c->pointsStartedEarly = false;
   c->escapeChecked = false;
   c->extIds = nullptr;
   c->extPts = nullptr;
-  // the totals and the per-slice occupancy share one allocation: one memset zeroes both
   static_assert(sizeof(Totals) % 16 == 0, "the occupancy words follow the totals");
-  HIP_TRY(c, c->occ.reserve(sizeof(Totals) + (size_t)g.nzb * sizeof(u32)));
-  HIP_TRY(c, c->prefix.reserve((nwords + 4) * sizeof(u32)));   // (+ the tail of a 16-byte read at the last words: locate_word_wave)
-  HIP_TRY(c, c->segPre.reserve(nseg * sizeof(u64)));
-  HIP_TRY(c, c->blockTot.reserve((nblk + 2 * (nblk / 8192 + 1)) * sizeof(u64)));     // (+ the sums of its chunks of 8192: k_block_partial)
-  HIP_TRY(c, c->blockBase.reserve(nblk * 2 * sizeof(u64)));
+  HIP_TRY(c, c->occ.reserve(sz.occ));
+  HIP_TRY(c, c->prefix.reserve(sz.prefix));
+  HIP_TRY(c, c->segPre.reserve(sz.segPre));
+  HIP_TRY(c, c->blockTot.reserve(sz.blockTot));
+  HIP_TRY(c, c->blockBase.reserve(sz.blockBase));
   Workspace w{};
-  w.flatBits = nullptr;
-  if (g.nx % 64 != 0) {   // ragged rows: thresholded as one flat stream first, then cut into rows
-    if (c->flatBits.reserve((nwordsAll + 32) * sizeof(u64)) == hipSuccess) w.flatBits = (u64 *)c->flatBits.p;
-    else (void)hipGetLastError();
-  }
-  w.vqueue = nullptr;
-  if (nwords < 0xffffffffULL && !c->tune.no_vqueue && c->vqueue.reserve(nwords * sizeof(u32)) == hipSuccess)
-    w.vqueue = (u32 *)c->vqueue.p;
-  else (void)hipGetLastError();
+  w.flatBits = (u64 *)optional(c->flatBits, sz.flatBits);
+  w.vqueue = (u32 *)optional(c->vqueue, sz.vqueue);
   w.vox = dev_voxels;
   w.bits = (u64 *)c->bits.p; w.sliceOcc = (u32 *)((char *)c->occ.p + sizeof(Totals));
   w.prefix = (u32 *)c->prefix.p;
@@ -527,19 +588,19 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   w.totals = (Totals *)c->occ.p;
 
   hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemsetAsync(w.totals, 0, sizeof(Totals) + (size_t)g.nzb * sizeof(u32), s));
+  HIP_TRY(c, hipMemsetAsync(w.totals, 0, sz.occ, s));
   c->stagesTimed = c->tune.stage_timing != 0;
   c->lightTiming = !c->stagesTimed && (u64)g.nx * (u64)g.ny * (u64)g.nzb <= (4ull << 20);
-  HIP_TRY(c, hipEventRecord(c->ev[0], s));
+  HIP_TRY(c, mark(c, PASS_BEGIN));
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
-  c->nwords = nwords; c->nseg = nseg;
+  c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
 
 // Second half: count + scan of the thresholded volume (launches only).
 int count_launch(cuberille_ctx *c, const Gate &gate) {
   hipStream_t s = c->stream;
-  if (c->stagesTimed) HIP_TRY(c, hipEventRecord(c->ev[1], s));
+  HIP_TRY(c, mark(c, CLASSIFY_END));
   HIP_TRY(c, launch_occupancy(c->pixel_type, c->w, c->g, c->tune, s));
   // (the LDS-tiled form pays where most words carry surface -- 2048^3 noise -- and costs where few do: it stages every
   //  row, a sparse block's untiled form skips whole words; the previous extraction's density decides)
@@ -565,7 +626,7 @@ int count_launch(cuberille_ctx *c, const Gate &gate) {
     if (sampled && mixed * 4 >= sampled) tiled = 3;
   }
   HIP_TRY(c, launch_count(c->w, c->g, c->nwords, c->prm.q1, gate, tiled, c->tune.count_no_fold, s));
-  if (!c->lightTiming) HIP_TRY(c, hipEventRecord(c->ev[2], s));
+  HIP_TRY(c, mark(c, PASS_END));
   return CUBERILLE_OK;
 }
 
@@ -712,7 +773,7 @@ int cuberille_recount(cuberille_ctx *c, const void *dev_source_bits, uint64_t *n
   c->pointsStartedEarly = false;
   c->escapeChecked = false;
   HIP_TRY(c, hipMemsetAsync(c->w.totals, 0, sizeof(Totals), s));
-  HIP_TRY(c, hipEventRecord(c->ev[0], s));   // ms_pass of a recounted slab: this count alone, not the host time since the first
+  HIP_TRY(c, mark(c, PASS_BEGIN));           // ms_pass of a recounted slab: this count alone, not the host time since the first
   return count_finish(c, n_points, n_cells);
 }
 
@@ -754,7 +815,7 @@ namespace {
 // (cuberille_emit_points may have started it already, while the caller was gathering the counts of the other ranks).
 // dyn (cuberille_step_begin): buffers and launches are sized for the cover values, the kernels read the real counts
 // from the device and run only when they fit (Totals::go).
-int emit_points_phase(cuberille_ctx *c, bool dyn = false, u64 coverV = 0, u64 coverQ = 0, u32 coverVW = 0) {
+int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV = 0, u64 coverQ = 0, u32 coverVW = 0) {
   if (c->pointsEmitted) return CUBERILLE_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const u64 nV = dyn ? coverV : c->tot.totV;                 // ghost + owned
@@ -764,51 +825,32 @@ int emit_points_phase(cuberille_ctx *c, bool dyn = false, u64 coverV = 0, u64 co
   const u32 nVW = dyn ? coverVW : c->tot.nVertexWords;
   // room behind this rank's points for the positions of a plane of the rank below's vertices (quirk Q1 across slabs)
   const size_t planeCorners = (c->slabMode || c->g.extAlias) ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) : 0;
-  // (a first extraction also makes room for the blind launches of the one behind it: gate.coverV / coverQ of cuberille_step_begin)
-  const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
-  HIP_TRY(c, c->points.reserve_covering((size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float),
-                                        (size_t)(nextV + planeCorners) * 3 * sizeof(float)));
-  HIP_TRY(c, c->cells.reserve_covering((size_t)(nQ ? nQ : 1) * (c->prm.triangles ? 6 : 4) * sizeof(u64),
-                                       (size_t)nextQ * (c->prm.triangles ? 6 : 4) * sizeof(u64)));
+  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords);
+  HIP_TRY(c, c->points.reserve_covering(sz.points.bytes, sz.points.cover));
+  HIP_TRY(c, c->cells.reserve_covering(sz.cells.bytes, sz.cells.cover));
   Workspace &w = c->w;
   w.points = (float *)c->points.p;
   w.cells = (u64 *)c->cells.p;
-  // dense corner -> vertex map (4 B per lattice corner of the buffer); when it cannot be had
-  // (more than 2^32 vertices, or no memory) the cell kernel recomputes ids instead
-  w.cmap = nullptr;
-  if (nV < 0xffffffffULL && !c->tune.no_cmap) {
-    // (bricks over the lattice corners 0..nx, 0..ny, 0..nzb + 1: the last plane also takes the handed-over one)
-    const size_t mapBytes = c->g.cmapLinear ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) * (c->g.nzb + 2) * sizeof(u32)
-                          : (((size_t)c->g.nx + 4) >> 2) * (((size_t)c->g.ny + 4) >> 2) * (((size_t)c->g.nzb + 3) >> 1) * 32 * sizeof(u32);
-    if (c->cmap.reserve(mapBytes) == hipSuccess) w.cmap = (u32 *)c->cmap.p;
-    else (void)hipGetLastError();
-  }
-  // head tables for the per-wave inverse mapping (4 B per 64 outputs)
-  w.headV = w.headQ = nullptr;
-  if (c->nwords < 0xffffffffULL && !c->tune.no_heads) {
-    if (c->headQ.reserve_covering((size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)) == hipSuccess)
-      w.headQ = (u32 *)c->headQ.p;
-    if (!w.vqueue && c->headV.reserve_covering((size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)) == hipSuccess)
-      w.headV = (u32 *)c->headV.p;
-    (void)hipGetLastError();
-  }
+  // without the corner map the cell kernel recomputes ids, without the head tables the waves search their outputs' words
+  w.cmap = (u32 *)optional(c->cmap, sz.cmap);
+  w.headQ = (u32 *)optional(c->headQ, sz.headQ.bytes, sz.headQ.cover);
+  w.headV = w.vqueue ? nullptr : (u32 *)optional(c->headV, sz.headV.bytes, sz.headV.cover);
   // THIN_HALO: room for the vertices whose walk leaves the buffer (more than these: the step is redone with the deep halo)
   w.escList = nullptr;
   w.escCap = 0;
   if (c->thinHalo) {
-    const size_t cap = nV < ESCAPE_LIST_CAP ? (size_t)nV + 1 : (size_t)ESCAPE_LIST_CAP;
-    HIP_TRY(c, c->escList.reserve(cap * sizeof(u32)));
+    HIP_TRY(c, c->escList.reserve(sz.escCap * sizeof(u32)));
     w.escList = (u32 *)c->escList.p;
-    w.escCap = (u32)cap;
+    w.escCap = (u32)sz.escCap;
   }
   // (the blind form needs every scratch table: the fallbacks without them size their launches from the counts)
   if (dyn && (!w.cmap || !w.headQ || !w.vqueue || c->tune.points_variant != 3))
     return fail(c, CUBERILLE_ERR_STATE, "internal: blind launch without the scratch tables");
   hipStream_t s = c->stream;
-  if (!c->lightTiming && (!c->oneCall || c->stagesTimed)) HIP_TRY(c, hipEventRecord(c->ev[4], s));
+  HIP_TRY(c, mark(c, POINTS_BEGIN));
   HIP_TRY(c, launch_heads(w, c->g, nV, totQ, dyn ? 1 : 0, s));
   HIP_TRY(c, launch_emit_points(w, c->g, c->geo, c->prm.q1, nV, nVW, c->tune, dyn ? 1 : 0, s));
-  if (c->stagesTimed) HIP_TRY(c, hipEventRecord(c->ev[5], s));
+  HIP_TRY(c, mark(c, POINTS_END));
   w.gradImg = nullptr;
   if (c->prm.project && c->prm.gradVariant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN && nV) {
     // the whole-image gradient pre-pass of txx:478-498 in its recursive-Gaussian form (the shipped central differences
@@ -856,9 +898,31 @@ int emit_points_phase(cuberille_ctx *c, bool dyn = false, u64 coverV = 0, u64 co
       c->held.n[0] = c->g.nx; c->held.n[1] = c->g.ny; c->held.n[2] = c->g.nzb;
     }
   }
-  if (c->stagesTimed) HIP_TRY(c, hipEventRecord(c->ev[6], s));
+  if (ahead) c->pointsStartedEarly = true;   // the caller turns to the other ranks now: the cells come as an interval of their own
+  HIP_TRY(c, mark(c, PROJECT_END));
   c->pointsEmitted = true;
   return CUBERILLE_OK;
+}
+
+// ---- timing marks: each mode records what finish_result reads, no more (an event between two kernels idles the stream for
+// 8-10 us, as long as the kernels of a small volume take).  With stage timing off: light = at most 4 Mi voxels (lightTiming),
+// one call = cuberille_extract_device (oneCall), default = the rest; stages = Tuning::stage_timing as it was when the count
+// ran (stagesTimed).  split: the vertex phase ran ahead of the cells (pointsStartedEarly: cuberille_emit_points ahead of
+// cuberille_emit, also after cuberille_recount; a step).
+//   mark          recorded                                     light  one call  default  stages
+//   PASS_BEGIN    count_prepare, cuberille_recount               x       x         x        x
+//   CLASSIFY_END  count_launch, ahead of the count               .       .         .        x
+//   PASS_END      count_launch, behind the count                 .       x         x        x
+//   POINTS_BEGIN  emit_points_phase, ahead of the heads          .       .         x        x
+//   POINTS_END    emit_points_phase, behind the vertex scatter   .       .         .        x
+//   PROJECT_END   emit_points_phase, at its end                  .       .       split      x
+//   CELLS_BEGIN   cuberille_emit, _step_end: ahead of the cells  .       .       split    split
+//   END           cuberille_emit, _step_end: behind the cells    x       x         x        x
+hipError_t mark(cuberille_ctx *c, Mark m) {
+  const bool stages = c->stagesTimed, coarse = !c->lightTiming && !c->oneCall, split = c->pointsStartedEarly;
+  const bool on[8] = {true, stages, !c->lightTiming, split && (stages || coarse), stages || coarse, stages,
+                      stages || (split && coarse), true};   // (in the order of enum Mark)
+  return on[m] ? hipEventRecord(c->ev[m], c->stream) : hipSuccess;
 }
 
 // After the last kernel of an extraction has completed and the totals are back in pinned memory: statistics, device times.
@@ -869,31 +933,33 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->tot.nEscaped = c->hostTotals->nEscaped;
   c->tot.err = c->hostTotals->err;
   cuberille_result &r = c->res;
+  auto ms = [c](float *out, Mark from, Mark to) { return hipEventElapsedTime(out, c->ev[from], c->ev[to]); };
+  const bool split = c->pointsStartedEarly;
   r.ms_scan = 0.0f;                          // the prefix sums are part of the count stage (k_count + k_block_scan)
-  if (c->stagesTimed) {                      // (the switch as it was when the count ran)
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_classify, c->ev[0], c->ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_count, c->ev[1], c->ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_emit_points, c->ev[4], c->ev[5]));
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_project, c->ev[5], c->ev[6]));
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_emit_cells, c->pointsStartedEarly ? c->ev[3] : c->ev[6], c->ev[7]));
+  if (c->stagesTimed) {
+    HIP_TRY(c, ms(&r.ms_classify, PASS_BEGIN, CLASSIFY_END));
+    HIP_TRY(c, ms(&r.ms_count, CLASSIFY_END, PASS_END));
+    HIP_TRY(c, ms(&r.ms_emit_points, POINTS_BEGIN, POINTS_END));
+    HIP_TRY(c, ms(&r.ms_project, POINTS_END, PROJECT_END));
+    HIP_TRY(c, ms(&r.ms_emit_cells, split ? CELLS_BEGIN : PROJECT_END, END));
   }
   float b = 0.f, b2 = 0.f;
   if (c->lightTiming) {
     // one event pair: the whole extraction as the stream saw it (a host turn between count and emit included, where
     // the caller took one); no pass figure
-    HIP_TRY(c, hipEventElapsedTime(&b, c->ev[0], c->ev[7]));
+    HIP_TRY(c, ms(&b, PASS_BEGIN, END));
     r.ms_pass = 0.f;
   } else if (c->oneCall && !c->stagesTimed) {
     // one call, no host turn in the middle: the pass, and everything behind it
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_pass, c->ev[0], c->ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(&b, c->ev[2], c->ev[7]));
+    HIP_TRY(c, ms(&r.ms_pass, PASS_BEGIN, PASS_END));
+    HIP_TRY(c, ms(&b, PASS_END, END));
   } else {
-    HIP_TRY(c, hipEventElapsedTime(&r.ms_pass, c->ev[0], c->ev[2]));
-    if (c->pointsStartedEarly) {
-      HIP_TRY(c, hipEventElapsedTime(&b, c->ev[4], c->ev[6]));
-      HIP_TRY(c, hipEventElapsedTime(&b2, c->ev[3], c->ev[7]));
+    HIP_TRY(c, ms(&r.ms_pass, PASS_BEGIN, PASS_END));
+    if (split) {
+      HIP_TRY(c, ms(&b, POINTS_BEGIN, PROJECT_END));
+      HIP_TRY(c, ms(&b2, CELLS_BEGIN, END));
     } else {
-      HIP_TRY(c, hipEventElapsedTime(&b, c->ev[4], c->ev[7]));
+      HIP_TRY(c, ms(&b, POINTS_BEGIN, END));
     }
   }
   r.ms_total = r.ms_pass + b + b2;           // device time: the host's turn between count and emit is in none of the intervals
@@ -934,13 +1000,7 @@ int cuberille_emit_points(cuberille_ctx *c) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   int rc = emit_preconditions(c, "cuberille_emit_points");
   if (rc) return rc;
-  if (c->pointsEmitted) return CUBERILLE_OK;
-  rc = emit_points_phase(c);
-  if (rc) return rc;
-  // the caller turns to the other ranks now: this phase gets its own end mark, cuberille_emit starts a second interval
-  if (!c->stagesTimed && !c->lightTiming && !c->oneCall) HIP_TRY(c, hipEventRecord(c->ev[6], c->stream));
-  c->pointsStartedEarly = true;
-  return CUBERILLE_OK;
+  return emit_points_phase(c, true);
 }
 
 int cuberille_escaped_count(cuberille_ctx *c, uint64_t *n_escaped) {
@@ -1000,7 +1060,7 @@ int cuberille_emit(cuberille_ctx *c, uint64_t point_id_offset, cuberille_result 
     return fail(c, CUBERILLE_ERR_STATE, "cuberille_emit after cuberille_recount needs cuberille_set_alias_plane");
   c->slabMesh = point_id_offset != 0 || c->tot.V0 != 0 || part_of_a_volume(c->g);
   c->pointOffset = point_id_offset;
-  rc = emit_points_phase(c);
+  rc = emit_points_phase(c, false);
   if (rc) return rc;
   if (c->thinHalo) {
     // no cell is written while a vertex waits for slices this buffer lacks (the count and the vertex phase stand: the
@@ -1018,12 +1078,12 @@ int cuberille_emit(cuberille_ctx *c, uint64_t point_id_offset, cuberille_result 
   hipStream_t s = c->stream;
   // the vertex phase was started ahead of this call (cuberille_emit_points): the device may have idled since, waiting
   // for the host's all-gather -- the cell phase is timed as an interval of its own
-  if (c->pointsStartedEarly && !c->lightTiming && (!c->oneCall || c->stagesTimed)) HIP_TRY(c, hipEventRecord(c->ev[3], s));
+  HIP_TRY(c, mark(c, CELLS_BEGIN));
   if (planeCorners)
     HIP_TRY(c, hipMemcpyAsync(w.points + 3 * nV, c->extPts, planeCorners * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, launch_emit_cells(w, c->g, c->prm.triangles, c->prm.q1, point_id_offset, nQ, needPlane ? c->extIds : nullptr,
                                nullptr, 0, 0, 0, s));
-  HIP_TRY(c, hipEventRecord(c->ev[7], s));
+  HIP_TRY(c, mark(c, END));
   HIP_TRY(c, hipMemcpyAsync(c->hostTotals, w.totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return finish_result(c, res);
@@ -1051,7 +1111,7 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
     gate.coverVW = (u32)(vw < c->nwords ? vw : c->nwords);
     rc = count_launch(c, gate);
     if (rc) return rc;
-    rc = emit_points_phase(c, true, gate.coverV, gate.coverQ, gate.coverVW);
+    rc = emit_points_phase(c, true, true, gate.coverV, gate.coverQ, gate.coverVW);
     if (rc == CUBERILLE_OK) {
       c->stepMode = 1;
     } else {
@@ -1075,14 +1135,11 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
     //  confirm: the vertex phase runs on it, the cell pass decides from the rows -- row_flags)
     c->stepMode = 2;
     if (!c->aliasMustResolve) {
-      rc = emit_points_phase(c);
+      rc = emit_points_phase(c, true);
       if (rc) return rc;
     }
   }
-  if (c->pointsEmitted) {
-    if (!c->stagesTimed && !c->lightTiming && !c->oneCall) HIP_TRY(c, hipEventRecord(c->ev[6], c->stream));
-    c->pointsStartedEarly = true;
-  }
+  c->pointsStartedEarly = true;   // (the cells follow the host's gather of the rows, also where the vertex phase waits)
   *dev_row = c->w.totals;
   *row_bytes = sizeof(Totals);
   return CUBERILLE_OK;
@@ -1154,7 +1211,7 @@ int step_end_impl(cuberille_ctx *c, const void *dev_rows, int n_ranks, int rank,
     HIP_TRY(c, hipHostMalloc((void **)&c->hostRows, (size_t)n_ranks * sizeof(Totals), hipHostMallocDefault));
     c->hostRowsCap = (size_t)n_ranks;
   }
-  if (!c->lightTiming && (!c->oneCall || c->stagesTimed)) HIP_TRY(c, hipEventRecord(c->ev[3], s));
+  HIP_TRY(c, mark(c, CELLS_BEGIN));
   // the cells, unless a flag stands somewhere (the kernel looks at the rows itself: every rank decides alike).  Sized
   // by the cover values (blind) or by this rank's counts; a rank whose vertex phase did not run launches nothing.
   if (blind || c->pointsEmitted) {
@@ -1162,7 +1219,7 @@ int step_end_impl(cuberille_ctx *c, const void *dev_rows, int n_ranks, int rank,
     HIP_TRY(c, launch_emit_cells(c->w, c->g, c->prm.triangles, c->prm.q1, base, nQ, nullptr, (const Totals *)dev_rows, n_ranks, rank,
                                  blind ? 1 : 0, s));
   }
-  HIP_TRY(c, hipEventRecord(c->ev[7], s));
+  HIP_TRY(c, mark(c, END));
   {
     const int rc = totals_to_host(c);
     if (rc) return rc;
@@ -1264,14 +1321,82 @@ int ensure_staging(cuberille_ctx *c, size_t bytes) {
   return CUBERILLE_OK;
 }
 
-// Host threads that copy pageable caller memory into the pinned staging ring, one fixed share of every chunk
-// each (a single memcpy stream cannot feed a PCIe Gen5 link; a handful can).
+// Let what is in flight finish before the staging slots are written again (a chunked copy that failed half way).
+void drain(cuberille_ctx *c) {
+  (void)hipStreamSynchronize(c->copyStream);
+  (void)hipStreamSynchronize(c->stream);
+}
+
+// Host threads that move the chunks of `total` bytes between pageable memory and the pinned staging slots, each one a fixed
+// share of every chunk (a single memcpy stream cannot feed a PCIe Gen5 link; a handful can).  move(i, a, b) moves bytes
+// [a, b) of chunk i; the threads take chunk i once release(i) has been called, and wait(i) returns when all of them are
+// done with it.  Destruction lets them finish what has been released and joins them.
 struct StagePool {
-  std::vector<std::thread> workers;
-  std::atomic<long long> freeUpTo{-1};      // chunks whose staging slot may be overwritten: all i <= freeUpTo
-  std::vector<std::atomic<int>> done;       // per chunk: workers that have copied their share
-  explicit StagePool(size_t nchunks) : done(nchunks) { for (auto &d : done) d.store(0); }
+  template <class Move>
+  StagePool(size_t total, size_t chunk, Move move) : done_((total + chunk - 1) / chunk) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    n_ = (int)(hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1));
+    for (auto &d : done_) d.store(0);
+    for (int t = 0; t < n_; t++)
+      threads_.emplace_back([this, t, total, chunk, move] {
+        for (size_t i = 0; i < done_.size(); i++) {
+          while (released_.load(std::memory_order_acquire) < (long long)i) {
+            if (abort_.load(std::memory_order_relaxed)) return;
+            std::this_thread::yield();
+          }
+          const size_t cb = total - i * chunk < chunk ? total - i * chunk : chunk;
+          const size_t a = cb * t / n_ & ~(size_t)63, b = (t == n_ - 1) ? cb : (cb * (t + 1) / n_ & ~(size_t)63);
+          move(i, a, b);
+          done_[i].fetch_add(1, std::memory_order_release);
+        }
+      });
+  }
+  ~StagePool() {
+    abort_.store(true);
+    for (auto &t : threads_) t.join();
+  }
+  void release(size_t i) { released_.store((long long)i, std::memory_order_release); }
+  void wait(size_t i) { while (done_[i].load(std::memory_order_acquire) < n_) std::this_thread::yield(); }
+  int n_ = 1;
+  std::atomic<long long> released_{-1};     // the threads may take every chunk i <= released_
+  std::atomic<bool> abort_{false};
+  std::vector<std::atomic<int>> done_;      // per chunk: threads that have moved their share
+  std::vector<std::thread> threads_;
 };
+
+// The extraction of a volume uploaded in chunks through the staging slots (of stageBytes): chunk i (slices [z0, z1)) goes
+// through slot i & 1 -- wait until the slot is free (chunk i - 2 has crossed the link), fill it (fill(i, slot, z0, z1): 0,
+// or the status with which the caller's source gave up), copy it on the copy stream, threshold it on the context's stream
+// once it has landed.
+template <class Fill>
+int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm, size_t stageBytes,
+                    size_t slicesPerChunk, const char *what, Fill fill, cuberille_result *res) {
+  int rc = ensure_staging(c, stageBytes);
+  if (rc) return rc;
+  rc = count_prepare(c, img, c->voxOwn.p, prm, nullptr);
+  if (rc) return rc;
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type), nz = (size_t)img->dims[2];
+  hipError_t e = hipSuccess;
+  int gaveUp = 0;
+  for (size_t i = 0; i * slicesPerChunk < nz; i++) {
+    const size_t z0 = i * slicesPerChunk, z1 = z0 + slicesPerChunk < nz ? z0 + slicesPerChunk : nz;
+    void *slot = c->stage[i & 1];
+    if (i >= 2 && (e = hipEventSynchronize(c->chunkIn[i & 1])) != hipSuccess) break;
+    if ((gaveUp = fill(i, slot, z0, z1)) != 0) break;
+    e = hipMemcpyAsync((char *)c->voxOwn.p + z0 * sliceBytes, slot, (z1 - z0) * sliceBytes, hipMemcpyHostToDevice, c->copyStream);
+    if (e == hipSuccess) e = hipEventRecord(c->chunkIn[i & 1], c->copyStream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->chunkIn[i & 1], 0);
+    if (e == hipSuccess) e = launch_classify(c->pixel_type, c->w, c->g, c->prm, (int)z0, (int)z1, c->tune, c->stream);
+    if (e != hipSuccess) break;
+  }
+  if (e != hipSuccess || gaveUp) {
+    drain(c);
+    if (gaveUp) return fail(c, CUBERILLE_ERR_SOURCE, "the chunk source gave up with status " + std::to_string(gaveUp));
+    return fail(c, CUBERILLE_ERR_HIP, std::string(what) + hipGetErrorString(e));
+  }
+  rc = count_finish(c, nullptr, nullptr);
+  return rc ? rc : cuberille_emit(c, 0, res);
+}
 
 }  // namespace
 
@@ -1282,10 +1407,8 @@ int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, co
   int rc = validate(c, img, host_voxels, prm);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t psz = pixel_size(img->pixel_type);
-  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * psz;
-  const size_t nz = (size_t)img->dims[2];
-  const size_t bytes = sliceBytes * nz;
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+  const size_t bytes = sliceBytes * (size_t)img->dims[2];
   HIP_TRY(c, c->voxOwn.reserve(bytes));
   // below a GiB: one plain copy (the runtime stages pageable memory itself, at link rate once the copy is large; the
   // chunk pipeline below needs some tens of chunks to amortise its start -- measured 34 ms against 11 ms at 512^3 f32);
@@ -1295,61 +1418,17 @@ int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, co
     HIP_TRY(c, hipMemcpyAsync(c->voxOwn.p, host_voxels, bytes, hipMemcpyHostToDevice, c->stream));
     return cuberille_extract_device(c, img, c->voxOwn.p, prm, nullptr, res);
   }
-  // large volumes: z-chunks through a pinned double buffer on a copy stream; chunk i is thresholded on the
-  // context's stream while chunk i+1 crosses the link and the host threads stage chunk i+2
-  rc = ensure_staging(c, kChunk);
-  if (rc) return rc;
-  rc = count_prepare(c, img, c->voxOwn.p, prm, nullptr);
-  if (rc) return rc;
-  const size_t slicesPerChunk = kChunk / sliceBytes;
-  const size_t nchunks = (nz + slicesPerChunk - 1) / slicesPerChunk;
-  unsigned hw = std::thread::hardware_concurrency();
-  const int nT = (int)(hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1));
-  StagePool pool(nchunks);
-  const char *src = (const char *)host_voxels;
-  auto chunkRange = [&](size_t i, size_t &z0, size_t &z1) { z0 = i * slicesPerChunk; z1 = z0 + slicesPerChunk < nz ? z0 + slicesPerChunk : nz; };
-  std::atomic<bool> abort{false};
-  for (int t = 0; t < nT; t++) {
-    pool.workers.emplace_back([&, t] {
-      for (size_t i = 0; i < nchunks && !abort.load(std::memory_order_relaxed); i++) {
-        while (pool.freeUpTo.load(std::memory_order_acquire) < (long long)i) {
-          if (abort.load(std::memory_order_relaxed)) return;
-          std::this_thread::yield();
-        }
-        size_t z0, z1;
-        chunkRange(i, z0, z1);
-        const size_t cb = (z1 - z0) * sliceBytes;
-        const size_t a = cb * t / nT & ~(size_t)63, b = (t == nT - 1) ? cb : (cb * (t + 1) / nT & ~(size_t)63);
-        std::memcpy((char *)c->stage[i & 1] + a, src + z0 * sliceBytes + a, b - a);
-        pool.done[i].fetch_add(1, std::memory_order_release);
-      }
-    });
-  }
-  auto joinAll = [&] { for (auto &w : pool.workers) if (w.joinable()) w.join(); };
-  hipError_t e = hipSuccess;
-  pool.freeUpTo.store(1, std::memory_order_release);          // both slots start free
-  for (size_t i = 0; i < nchunks && e == hipSuccess; i++) {
-    while (pool.done[i].load(std::memory_order_acquire) < nT) std::this_thread::yield();
-    size_t z0, z1;
-    chunkRange(i, z0, z1);
-    e = hipMemcpyAsync((char *)c->voxOwn.p + z0 * sliceBytes, c->stage[i & 1], (z1 - z0) * sliceBytes, hipMemcpyHostToDevice,
-                       c->copyStream);
-    if (e == hipSuccess) e = hipEventRecord(c->chunkIn[i & 1], c->copyStream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->chunkIn[i & 1], 0);
-    if (e == hipSuccess) e = launch_classify(img->pixel_type, c->w, c->g, c->prm, (int)z0, (int)z1, c->tune, c->stream);
-    // slot (i & 1) is free for chunk i + 2 once this chunk has crossed the link
-    if (e == hipSuccess && i + 2 < nchunks) {
-      e = hipEventSynchronize(c->chunkIn[i & 1]);
-      pool.freeUpTo.store((long long)i + 2, std::memory_order_release);
-    }
-  }
-  if (e != hipSuccess) abort.store(true);
-  joinAll();
-  if (e != hipSuccess) return fail(c, CUBERILLE_ERR_HIP, std::string("overlapped upload: ") + hipGetErrorString(e));
-  uint64_t np = 0, nc = 0;
-  rc = count_finish(c, &np, &nc);
-  if (rc) return rc;
-  return cuberille_emit(c, 0, res);
+  // large volumes: z-chunks of whole slices; chunk i is thresholded on the context's stream while chunk i+1 crosses the
+  // link and the host threads stage chunk i+2
+  const size_t chunk = kChunk / sliceBytes * sliceBytes;
+  StagePool pool(bytes, chunk, [&](size_t i, size_t a, size_t b) {
+    std::memcpy((char *)c->stage[i & 1] + a, (const char *)host_voxels + i * chunk + a, b - a);
+  });
+  return extract_chunked(c, img, prm, kChunk, kChunk / sliceBytes, "overlapped upload: ", [&](size_t i, void *, size_t, size_t) {
+    pool.release(i);
+    pool.wait(i);
+    return 0;
+  }, res);
 }
 
 int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, cuberille_chunk_source source, void *user,
@@ -1358,44 +1437,12 @@ int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, 
   int rc = validate(c, img, (const void *)source, prm);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t psz = pixel_size(img->pixel_type);
-  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * psz;
-  const size_t nz = (size_t)img->dims[2];
-  HIP_TRY(c, c->voxOwn.reserve(sliceBytes * nz));
-  // chunks of about 32 MiB, whole slices, at least one
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+  HIP_TRY(c, c->voxOwn.reserve(sliceBytes * (size_t)img->dims[2]));
+  // chunks of about 32 MiB, whole slices, at least one; the caller's source fills each slot on this thread, in order
   const size_t slicesPerChunk = sliceBytes >= (32u << 20) ? 1 : (32u << 20) / sliceBytes;
-  const size_t chunkBytes = slicesPerChunk * sliceBytes;
-  const size_t nchunks = (nz + slicesPerChunk - 1) / slicesPerChunk;
-  rc = ensure_staging(c, chunkBytes);
-  if (rc) return rc;
-  rc = count_prepare(c, img, c->voxOwn.p, prm, nullptr);
-  if (rc) return rc;
-  hipError_t e = hipSuccess;
-  int gaveUp = 0;
-  for (size_t i = 0; i < nchunks && e == hipSuccess; i++) {
-    const size_t z0 = i * slicesPerChunk, z1 = z0 + slicesPerChunk < nz ? z0 + slicesPerChunk : nz;
-    // the slot is free once chunk i - 2 has crossed the link
-    if (i >= 2) e = hipEventSynchronize(c->chunkIn[i & 1]);
-    if (e != hipSuccess) break;
-    gaveUp = source(user, c->stage[i & 1], (int64_t)z0, (int64_t)z1);
-    if (gaveUp) break;
-    e = hipMemcpyAsync((char *)c->voxOwn.p + z0 * sliceBytes, c->stage[i & 1], (z1 - z0) * sliceBytes, hipMemcpyHostToDevice,
-                       c->copyStream);
-    if (e == hipSuccess) e = hipEventRecord(c->chunkIn[i & 1], c->copyStream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->chunkIn[i & 1], 0);
-    if (e == hipSuccess) e = launch_classify(img->pixel_type, c->w, c->g, c->prm, (int)z0, (int)z1, c->tune, c->stream);
-  }
-  if (gaveUp || e != hipSuccess) {
-    // let what is in flight finish before the staging slots are used again
-    (void)hipStreamSynchronize(c->copyStream);
-    (void)hipStreamSynchronize(c->stream);
-    if (gaveUp) return fail(c, CUBERILLE_ERR_SOURCE, "the chunk source gave up with status " + std::to_string(gaveUp));
-    return fail(c, CUBERILLE_ERR_HIP, std::string("streamed upload: ") + hipGetErrorString(e));
-  }
-  uint64_t np = 0, nc = 0;
-  rc = count_finish(c, &np, &nc);
-  if (rc) return rc;
-  return cuberille_emit(c, 0, res);
+  return extract_chunked(c, img, prm, slicesPerChunk * sliceBytes, slicesPerChunk, "streamed upload: ",
+                         [&](size_t, void *slot, size_t z0, size_t z1) { return source(user, slot, (int64_t)z0, (int64_t)z1); }, res);
 }
 
 int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm) {
@@ -1454,23 +1501,15 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
   if (live) return CUBERILLE_OK;
   // the buffers whose size follows from the description (count_prepare, emit_points_phase, cuberille_extract_host); a
   // reservation that fails here is asked for again, and reported, by the extraction
-  const size_t nx = (size_t)img->dims[0], ny = (size_t)img->dims[1], nz = (size_t)img->dims[2];
-  const size_t W = (nx + 63) / 64, nwords = nz * ny * W, nseg = (nwords + 63) / 64, nblk = (nwords + COUNT_WB - 1) / COUNT_WB;
-  const size_t bytes = nx * ny * nz * pixel_size(img->pixel_type);
-  bool ok = c->voxOwn.reserve(bytes) == hipSuccess;
-  ok = ok && c->bits.reserve((nwords + ny * W) * sizeof(u64)) == hipSuccess;
-  ok = ok && c->occ.reserve(sizeof(Totals) + nz * sizeof(u32)) == hipSuccess;
-  ok = ok && c->prefix.reserve((nwords + 4) * sizeof(u32)) == hipSuccess;
-  ok = ok && c->segPre.reserve(nseg * sizeof(u64)) == hipSuccess;
-  ok = ok && c->blockTot.reserve((nblk + 2 * (nblk / 8192 + 1)) * sizeof(u64)) == hipSuccess;
-  ok = ok && c->blockBase.reserve(nblk * 2 * sizeof(u64)) == hipSuccess;
-  if (ok && nx % 64 != 0) ok = c->flatBits.reserve((nwords + 32) * sizeof(u64)) == hipSuccess;
-  if (ok && nwords < 0xffffffffULL && !c->tune.no_vqueue) ok = c->vqueue.reserve(nwords * sizeof(u32)) == hipSuccess;
-  if (ok && !c->tune.no_cmap) {
-    const size_t mapBytes = c->tune.cmap_linear ? (nx + 1) * (ny + 1) * (nz + 2) * sizeof(u32)
-                          : ((nx + 4) >> 2) * ((ny + 4) >> 2) * ((nz + 3) >> 1) * 32 * sizeof(u32);
-    ok = c->cmap.reserve(mapBytes) == hipSuccess;
-  }
+  const Grid g = whole_grid(img, c->tune);
+  const CountSizes sz = count_sizes(g, c->tune);
+  const size_t bytes = (size_t)g.nx * g.ny * g.nzb * pixel_size(img->pixel_type);
+  const std::pair<DevBuf *, size_t> want[] = {{&c->voxOwn, bytes}, {&c->bits, sz.bits}, {&c->occ, sz.occ}, {&c->prefix, sz.prefix},
+                                              {&c->segPre, sz.segPre}, {&c->blockTot, sz.blockTot}, {&c->blockBase, sz.blockBase},
+                                              {&c->flatBits, sz.flatBits}, {&c->vqueue, sz.vqueue}, {&c->cmap, cmap_bytes(g, c->tune)}};
+  bool ok = true;
+  for (const auto &b : want)   // (0 bytes: not wanted, nothing to reserve)
+    if (b.first->reserve(b.second) != hipSuccess) { ok = false; break; }
   if (!ok) (void)hipGetLastError();
   // the pinned staging ring: a chunked upload (volumes of a GiB and more) and the download of a mesh of more than 128 MiB
   // go through it; a volume of 64 MiB can carry such a mesh
@@ -1585,37 +1624,17 @@ int download_pipelined(cuberille_ctx *c, void *dst, const void *src, size_t byte
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return CUBERILLE_OK;
   }
-  {
-    const int rc = ensure_staging(c, kChunk);
-    if (rc) return rc;
-  }
+  if (const int rc = ensure_staging(c, kChunk)) return rc;
   // the mesh was written on the context's stream
   HIP_TRY(c, hipEventRecord(c->stageFree[0], c->stream));
   HIP_TRY(c, hipStreamWaitEvent(c->copyStream, c->stageFree[0], 0));
   const size_t nchunks = (bytes + kChunk - 1) / kChunk;
-  unsigned hw = std::thread::hardware_concurrency();
-  const int nT = (int)(hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1));
-  std::vector<std::atomic<int>> landed(nchunks), moved(nchunks);
-  for (size_t i = 0; i < nchunks; i++) { landed[i].store(0); moved[i].store(0); }
-  std::atomic<bool> abort{false};
-  std::vector<std::thread> workers;
-  for (int t = 0; t < nT; t++) {
-    workers.emplace_back([&, t] {
-      for (size_t i = 0; i < nchunks; i++) {
-        while (!landed[i].load(std::memory_order_acquire)) {
-          if (abort.load(std::memory_order_relaxed)) return;
-          std::this_thread::yield();
-        }
-        const size_t off = i * kChunk, cb = bytes - off < kChunk ? bytes - off : kChunk;
-        const size_t a = cb * t / nT & ~(size_t)63, b = (t == nT - 1) ? cb : (cb * (t + 1) / nT & ~(size_t)63);
-        std::memcpy((char *)dst + off + a, (const char *)c->stage[i & 1] + a, b - a);
-        moved[i].fetch_add(1, std::memory_order_release);
-      }
-    });
-  }
+  auto chunkBytes = [&](size_t i) { return bytes - i * kChunk < kChunk ? bytes - i * kChunk : kChunk; };
+  StagePool pool(bytes, kChunk, [&](size_t i, size_t a, size_t b) {
+    std::memcpy((char *)dst + i * kChunk + a, (const char *)c->stage[i & 1] + a, b - a);
+  });
   auto issue = [&](size_t i) -> hipError_t {
-    const size_t off = i * kChunk, cb = bytes - off < kChunk ? bytes - off : kChunk;
-    hipError_t e = hipMemcpyAsync(c->stage[i & 1], (const char *)src + off, cb, hipMemcpyDeviceToHost, c->copyStream);
+    hipError_t e = hipMemcpyAsync(c->stage[i & 1], (const char *)src + i * kChunk, chunkBytes(i), hipMemcpyDeviceToHost, c->copyStream);
     if (e == hipSuccess) e = hipEventRecord(c->chunkIn[i & 1], c->copyStream);
     return e;
   };
@@ -1623,20 +1642,16 @@ int download_pipelined(cuberille_ctx *c, void *dst, const void *src, size_t byte
   for (size_t i = 0; i < nchunks && e == hipSuccess; i++) {
     if (i + 1 < nchunks) {
       // slot (i + 1) & 1 held chunk i - 1: the host threads must be done with it
-      if (i >= 1) while (moved[i - 1].load(std::memory_order_acquire) < nT) std::this_thread::yield();
+      if (i >= 1) pool.wait(i - 1);
       e = issue(i + 1);
       if (e != hipSuccess) break;
     }
     e = hipEventSynchronize(c->chunkIn[i & 1]);
-    if (e == hipSuccess) landed[i].store(1, std::memory_order_release);
+    if (e == hipSuccess) pool.release(i);
   }
-  if (e != hipSuccess) abort.store(true);
-  for (auto &w : workers) w.join();
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(c->copyStream);
-    return fail(c, CUBERILLE_ERR_HIP, std::string("mesh download: ") + hipGetErrorString(e));
-  }
-  return CUBERILLE_OK;
+  if (e == hipSuccess) return CUBERILLE_OK;
+  drain(c);
+  return fail(c, CUBERILLE_ERR_HIP, std::string("mesh download: ") + hipGetErrorString(e));
 }
 
 }  // namespace

@@ -514,6 +514,35 @@ def test_warm_up_leaves_a_live_count_and_mesh_alone(pkg, oracle, volumes):
         ex.close()
 
 
+@pytest.mark.parametrize("dims", [(128, 24, 20), (70, 33, 29)])
+def test_warm_up_reserves_what_the_count_asks_for(pkg, oracle, dims):
+    """cuberille_warm_up(img) reserves the count's workspace at the sizes the count asks for (one source for both): with the
+    allocation drill armed at the very next allocation, a count of that image makes none and goes through; the emit behind it
+    allocates and reports the drill; the next extraction equals the oracle -- for whole-word rows and for ragged ones."""
+    import torch
+    nx, ny, nz = dims
+    vox = (np.random.default_rng(nx).random((nz, ny, nx)) < 0.3).astype(np.uint8) * 200
+    kw = dict(triangles=True, project=True, threshold=0.2, step=0.24, relax=0.95, max_steps=30)
+    want = oracle.run(vox, 100, **kw)
+    prm = pkg.make_params(100, **kw)
+    desc = pkg.make_desc(np.uint8, dims)
+    dev = torch.from_numpy(vox).cuda()
+    torch.cuda.synchronize()
+    ex = pkg.Extractor(0)
+    try:
+        ex.warm_up(desc)
+        ex.debug_option("fail_alloc_at", 0)
+        assert ex.count(dev.data_ptr(), desc, prm) == (len(want.points), len(want.cells))
+        with pytest.raises(pkg._abi.CuberilleError) as e:
+            ex.emit(0)
+        assert e.value.code == pkg._abi.ERR_HIP and "reserve" in str(e.value), str(e.value)
+        ex.extract_device(dev.data_ptr(), desc, prm)
+        assert_same_mesh(ex.download(), want)
+    finally:
+        ex.debug_option("defaults", 0)
+        ex.close()
+
+
 def _geom(vol):
     return (vol.voxels, vol.spacing, vol.origin, vol.direction)
 
