@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("CUBERILLE_LIB") or os.path.join(CSRC, "libcuberille_h
 
 OK, ERR_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_HALO, ERR_LIMIT, ERR_SOURCE, RETRY = range(9)
 SLAB_THIN_HALO = 1
+INTERP_LINEAR, INTERP_BSPLINE = 0, 1   # cuberille_set_interpolator
 ESCAPED_OVERFLOW = 1 << 62          # Extractor.escaped_count(): more walks escaped than the library's list holds
 
 # every symbol include/cuberille_hip.h declares (tests check the built library exports them all)
@@ -29,6 +30,7 @@ EXPORTS = [
     "cuberille_minimum_halo", "cuberille_escaped_count", "cuberille_reproject_escaped", "cuberille_step_begin", "cuberille_step_end",
     "cuberille_slice_counts", "cuberille_failed_row", "cuberille_warm_up", "cuberille_mesh_host", "cuberille_step_classify", "cuberille_step_count",
     "cuberille_release_host_mesh", "cuberille_hold_gradient", "cuberille_gradient_held",
+    "cuberille_set_interpolator", "cuberille_bspline_coefficients", "cuberille_bspline_coefficients_info",
 ]
 ABI_VERSION = 13
 
@@ -128,6 +130,9 @@ def lib():
     L.cuberille_release_host_mesh.argtypes = [vp]
     L.cuberille_hold_gradient.argtypes = [vp, C.c_int]
     L.cuberille_gradient_held.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.cuberille_set_interpolator.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
+    L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_slice_occupancy.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_write_vtk_buffers.argtypes = [C.c_char_p, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int]

@@ -107,6 +107,11 @@ struct cuberille_ctx {
   DevBuf heldGrad;                       // cuberille_hold_gradient: the float gradient image of the first projecting extraction
   HeldGradient held{};                   // ... with its geometry (img == null: none yet); what every later walk follows
   bool holdGradient = false;             // ... asked for
+  int interp = CUBERILLE_INTERP_LINEAR;  // cuberille_set_interpolator: the value interpolator of later walks ...
+  int bsBits = 0;                        // ... and, for the B-spline, its coordinate / coefficient width (32 or 64)
+  DevBuf bsCoef, bsScratch;              // the B-spline coefficient image, and the double scratch of its passes (32-bit only)
+  int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
+  int64_t bsDims[3] = {0, 0, 0};         // ... and its size
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
   Totals *hostTotals = nullptr;          // pinned
@@ -144,6 +149,7 @@ struct cuberille_ctx {
   const float *extPts = nullptr;
   // state of the last count
   bool counted = false, haveMesh = false, slabMesh = false;
+  int countBsBits = 0;                   // the B-spline walk of the running count/emit pair: its width (0: not this interpolator)
   bool pointsEmitted = false;            // the offset-free part of the emit has been launched for the current count
   bool stagesTimed = false;              // the per-stage events of the running count/emit pair are being recorded
   bool lightTiming = false;              // a few million voxels at most: ONE event pair around the extraction (every event
@@ -233,6 +239,14 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
     for (int i = 0; i < 3; i++)
       if (img->dims[i] < 4)   // (ITK's recursive filter throws for shorter lines)
         return fail(c, CUBERILLE_ERR_ARGUMENT, "the recursive-Gaussian gradient needs at least 4 voxels along every axis");
+  if (c->interp == CUBERILLE_INTERP_BSPLINE && prm->project_vertices) {
+    if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator walks the default projection branch only (txx:439-474)");
+    if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is offered with the central-difference gradient only");
+    if (c->holdGradient)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is not offered on a context holding a gradient (cuberille_hold_gradient)");
+  }
   // the iso value is an InputPixelType in the reference (h:180-181): for the integer pixel types it must convert
   // without leaving the type's range (a fraction is cut off like a C cast does)
   double lo = 0.0, hi = 0.0;
@@ -301,7 +315,7 @@ void cuberille_destroy(cuberille_ctx *c) {
   if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);
   DevBuf *bufs[] = {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
                     &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
-                    &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad};
+                    &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch};
   for (DevBuf *b : bufs) b->release();
   c->hostPoints.release();
   c->hostCells.release();
@@ -429,6 +443,24 @@ void deriche_setup(double sigma, double spacing, int order, double out[20]) {
   for (int i = 0; i < 20; i++) out[i] = v[i];
 }
 
+// BSplineDecompositionImageFilter of ITK 3.x, order 3 (one pole), for a line of n pixels: SetPoles, the gain of
+// DataToCoefficients1D, the horizon of SetInitialCausalCoefficient (m_Tolerance 1e-10) and the powers its full mirror sum
+// and SetInitialAntiCausalCoefficient use -- in double on the host, with the host's pow / log, like the restatement in
+// itk/itk_lite/itkBSplineLite.h.  Layout = cuberille::BsAxis; the kernels (k_bs_rows, k_bs_lines) run the recurrences.
+BsAxis bspline_axis(long long n) {
+  BsAxis a{};
+  a.z = std::sqrt(3.0) - 2.0;
+  double c0 = 1.0;
+  c0 = c0 * (1.0 - a.z) * (1.0 - 1.0 / a.z);
+  a.gain = c0;
+  a.iz = 1.0 / a.z;
+  a.zN1 = std::pow(a.z, (double)(n - 1LL));
+  a.anti = a.z / (a.z * a.z - 1.0);
+  a.horizon = (int)(long)std::ceil(std::log(1e-10) / std::log(std::fabs(a.z)));
+  a.n = n;
+  return a;
+}
+
 // The layout of a whole image (count_prepare narrows it to a slab's owned range).
 Grid whole_grid(const cuberille_image_desc *img, const Tuning &t) {
   Grid g{};
@@ -542,6 +574,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
       return fail(c, CUBERILLE_ERR_ARGUMENT, "the recursive-Gaussian gradient filters whole lines of the volume: not offered on slabs");
     if (p.project && c->holdGradient)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "a held gradient image (cuberille_hold_gradient) belongs to a whole volume: not offered on slabs");
+    if (p.project && c->interp == CUBERILLE_INTERP_BSPLINE)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline prefilter filters whole lines of the volume: not offered on slabs");
     const bool thin = (slab->flags & CUBERILLE_SLAB_THIN_HALO) != 0;
     if (thin && p.project && p.variant != CUBERILLE_PROJECT_DEFAULT)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "a THIN_HALO slab is only offered with the default projection branch");
@@ -593,6 +627,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->lightTiming = !c->stagesTimed && (u64)g.nx * (u64)g.ny * (u64)g.nzb <= (4ull << 20);
   HIP_TRY(c, mark(c, PASS_BEGIN));
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
+  c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -886,7 +921,25 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
       c->voxelHaloEvent = nullptr;
     }
     w.held = c->holdGradient && c->held.img ? &c->held : nullptr;
-    HIP_TRY(c, launch_project(c->pixel_type, w, c->g, c->geo, c->prm, nV, nGhost, tn, c->thinHalo ? 1 : 0, dyn ? 1 : 0, s));
+    if (c->countBsBits && nV) {
+      // cuberille_set_interpolator(CUBERILLE_INTERP_BSPLINE): the coefficient image of the whole volume, then the walk reading it
+      // (a whole volume, the default branch, the central gradient: count_prepare and validate saw to that)
+      const size_t nvox = (size_t)c->g.nx * c->g.ny * c->g.nzb;
+      c->bsValidBits = 0;
+      HIP_TRY(c, c->bsCoef.reserve(nvox * (size_t)(c->countBsBits / 8)));
+      double *scratch = nullptr;
+      if (c->countBsBits == 32) {
+        HIP_TRY(c, c->bsScratch.reserve(nvox * sizeof(double)));
+        scratch = (double *)c->bsScratch.p;
+      }
+      const BsAxis ax[3] = {bspline_axis(c->g.nx), bspline_axis(c->g.ny), bspline_axis(c->g.nzb)};
+      HIP_TRY(c, launch_bspline_prefilter(c->pixel_type, w.vox, c->g, ax, c->bsCoef.p, c->countBsBits, scratch, s));
+      HIP_TRY(c, launch_project_bspline(c->pixel_type, w, c->g, c->geo, c->prm, nV, c->bsCoef.p, c->countBsBits, s));
+      c->bsValidBits = c->countBsBits;
+      c->bsDims[0] = c->g.nx; c->bsDims[1] = c->g.ny; c->bsDims[2] = c->g.nzb;
+    } else {
+      HIP_TRY(c, launch_project(c->pixel_type, w, c->g, c->geo, c->prm, nV, nGhost, tn, c->thinHalo ? 1 : 0, dyn ? 1 : 0, s));
+    }
     if (c->holdGradient && !c->held.img) {
       // quirk Q3 on request: this is the context's first projecting extraction -- ComputeGradientImage() of txx:478-498
       // runs (the walk above evaluated the same taps on the fly) and its image stays for every extraction to come
@@ -967,8 +1020,11 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   r.proj_stop_steps = r.proj_stop_threshold = 0;
   if (c->prm.project) {
     r.proj_stop_steps = c->tot.stopSteps;
-    // the default branch ends every walk one way or the other (txx:456-472): only the rare way is counted on the device
-    r.proj_stop_threshold = c->prm.variant == CUBERILLE_PROJECT_DEFAULT ? r.n_points - c->tot.stopSteps : c->tot.stopThr;
+    // the default branch ends every walk one way or the other (txx:456-472): k_project counts only the rare way; the B-spline
+    // walk counts both, and the two counts must then add up to the points
+    r.proj_stop_threshold = c->prm.variant == CUBERILLE_PROJECT_DEFAULT && !c->countBsBits ? r.n_points - c->tot.stopSteps : c->tot.stopThr;
+    if (c->countBsBits && r.proj_stop_threshold + r.proj_stop_steps != r.n_points)
+      return fail(c, CUBERILLE_ERR_STATE, "internal: the B-spline walk's termination counts do not add up to the points");
   }
   r.n_escaped = c->tot.nEscaped;
   // what this extraction produced sizes the blind launches of the next cuberille_step_begin on this context
@@ -1100,7 +1156,8 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
   // blind launches need: the sizes of a previous extraction on this context, the default projection branch and every
   // scratch table (the vertex-word queue is set up by count_prepare; the others are checked below)
   const bool blind = c->haveHistory && c->w.vqueue && !c->tune.no_cmap && !c->tune.no_heads && c->tune.points_variant == 3 &&
-                     (!c->prm.project || (c->prm.variant == CUBERILLE_PROJECT_DEFAULT && c->prm.gradVariant == 0 && !c->holdGradient)) &&
+                     (!c->prm.project || (c->prm.variant == CUBERILLE_PROJECT_DEFAULT && c->prm.gradVariant == 0 && !c->holdGradient &&
+                                          c->countBsBits == 0)) &&
                      c->histV + c->histV / 4 < 0xfffff000ULL;
   if (blind) {
     Gate gate{};
@@ -1709,6 +1766,41 @@ int cuberille_gradient_held(cuberille_ctx *c, int64_t dims[3]) {
   if (!c) return 0;
   if (dims) for (int i = 0; i < 3; i++) dims[i] = c->held.img ? c->held.n[i] : 0;
   return c->held.img ? 1 : 0;
+}
+
+int cuberille_set_interpolator(cuberille_ctx *c, int kind, int spline_order, int coordinate_bits, int coefficient_bits) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  if (kind == CUBERILLE_INTERP_LINEAR) {
+    c->interp = CUBERILLE_INTERP_LINEAR;
+    return CUBERILLE_OK;
+  }
+  if (kind != CUBERILLE_INTERP_BSPLINE) return fail(c, CUBERILLE_ERR_ARGUMENT, "unknown interpolator kind");
+  if (spline_order != 3)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "the device B-spline walk implements spline order 3 (the reference driver's SetSplineOrder(3))");
+  if (!((coordinate_bits == 32 && coefficient_bits == 32) || (coordinate_bits == 64 && coefficient_bits == 64)))
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "the device B-spline walk implements <float, float> (32, 32) and <double, double> (64, 64)");
+  c->interp = CUBERILLE_INTERP_BSPLINE;
+  c->bsBits = coordinate_bits;
+  return CUBERILLE_OK;
+}
+
+int cuberille_bspline_coefficients_info(cuberille_ctx *c, int64_t dims[3], int *coefficient_bits) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (dims) for (int i = 0; i < 3; i++) dims[i] = c->bsValidBits ? c->bsDims[i] : 0;
+  if (coefficient_bits) *coefficient_bits = c->bsValidBits;
+  return c->bsValidBits ? 1 : 0;
+}
+
+int cuberille_bspline_coefficients(cuberille_ctx *c, void *host_out, size_t capacity_bytes) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (!c->bsValidBits) return fail(c, CUBERILLE_ERR_STATE, "no B-spline extraction on this context has projected a vertex");
+  const size_t bytes = (size_t)c->bsDims[0] * (size_t)c->bsDims[1] * (size_t)c->bsDims[2] * (size_t)(c->bsValidBits / 8);
+  if (!host_out || capacity_bytes < bytes) return fail(c, CUBERILLE_ERR_ARGUMENT, "the output buffer is smaller than the coefficient image");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(host_out, c->bsCoef.p, bytes, hipMemcpyDeviceToHost));
+  return CUBERILLE_OK;
 }
 
 int cuberille_release_host_mesh(cuberille_ctx *c) {

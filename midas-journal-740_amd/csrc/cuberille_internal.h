@@ -178,6 +178,18 @@ struct Params {
   int gradVariant;            // CUBERILLE_GRADIENT_*
 };
 
+// One axis of the order-3 B-spline prefilter (ITK's BSplineDecompositionImageFilter), evaluated on the host in double
+// (cuberille_api.hip, bspline_axis): the kernels only run the recurrences, so device pow / log never enter.
+struct BsAxis {
+  double z;            // the pole, sqrt(3) - 2
+  double gain;         // (1 - z)(1 - 1/z)
+  double iz;           // 1 / z
+  double zN1;          // pow(z, n - 1): the full mirror sum of the causal init (lines no longer than the horizon)
+  double anti;         // z / (z*z - 1): the anti-causal init
+  long long n;         // line length
+  int horizon;         // ceil(log(1e-10) / log|z|): lines longer than this take the truncated power sum
+};
+
 // cuberille_step_begin: what the launches behind the count were sized for (k_block_scan sets Totals::go accordingly)
 struct Gate {
   int on;
@@ -203,6 +215,12 @@ hipError_t launch_alias_plane(const Workspace &w, const Grid &g, int zLocal, u64
                               hipStream_t s);
 hipError_t launch_recursive_gaussian(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, const double coef[3][2][20],
                                      hipStream_t s);
+// cuberille_set_interpolator(CUBERILLE_INTERP_BSPLINE): the coefficient image of the whole volume (coefBits 32: float, with a
+// double scratch volume; 64: double, in place), and the default walk reading it
+hipError_t launch_bspline_prefilter(int pixel_type, const void *vox, const Grid &g, const BsAxis ax[3], void *coef, int coefBits,
+                                    double *scratch, hipStream_t s);
+hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, const Params &p, u64 nPoints,
+                                  const void *coef, int coefBits, hipStream_t s);
 hipError_t launch_gradient_image(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *out, hipStream_t s);
 hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo,
                           const Params &p, u64 nPoints, u64 nGhost, const Tuning &t, int mode, int dyn, hipStream_t s);

@@ -3131,6 +3131,249 @@ __global__ __launch_bounds__(256) void k_rg_direction(double *__restrict__ grad,
 }
 
 // ---------------------------------------------------------------------------------------------
+// K4d: the reference driver's other interpolator (USE_BSPLINE_INTERPOLATOR, Testing/CuberilleTest01.cxx:73-74,148-151):
+// itk::BSplineInterpolateImageFunction of spline order 3, <float, float> or <double, double>, restated bit for bit from
+// itk/itk_lite/itkBSplineLite.h (parity with ITK's own bytes unpinned).  Two parts:
+//   the prefilter (BSplineDecompositionImageFilter): the input rounded to the coefficient type C, then the x, y and z
+//   passes in turn; every line runs gain, causal init + recursion and anti-causal init + recursion in double, and is
+//   written back as C.  The causal values stay double until the anti-causal pass has read them: in the coefficient image
+//   itself when C is double, else in a double scratch volume.  Lines along y and z: one lane per line, the lanes of a wave
+//   on neighbouring x, so every step is a coalesced row access.  Lines along x: a wave takes 64 rows and moves them
+//   through LDS in tiles of 64 x BS_TW (coalesced loads and stores of the tile; each lane runs its row's recursion out of
+//   LDS).  Constants per axis come from the host (BsAxis).
+//   the value (EvaluateAtContinuousIndex): 4 x 4 x 4 taps, weights in ITK's written order, mirror boundaries, a double
+//   sum with x fastest -- in the default branch of the walk (txx:439-474) with the shipped central-difference gradient.
+// ---------------------------------------------------------------------------------------------
+constexpr int BS_TW = 32;          // columns of an x-pass tile (>= the horizon, 18, so the causal init lies in the first tile)
+
+// ITK 3.x SetInitialCausalCoefficient on the gained line s(0 .. n-1)
+template <class F>
+__device__ __forceinline__ double bs_causal_init(const BsAxis &a, F s) {
+  double zn = a.z;
+  if ((long long)a.horizon < a.n) {
+    double sum = s(0);
+    for (int n = 1; n < a.horizon; n++) {
+      sum += zn * s(n);
+      zn *= a.z;
+    }
+    return sum;
+  }
+  double z2n = a.zN1;
+  double sum = s(0) + z2n * s(a.n - 1);
+  z2n *= z2n * a.iz;
+  for (long long n = 1; n <= a.n - 2; n++) {
+    sum += (zn + z2n) * s(n);
+    zn *= a.z;
+    z2n *= a.iz;
+  }
+  return sum / (1.0 - zn * zn);
+}
+
+// lines along y (outer = nx*ny, stride = nx) or z (outer = nx, stride = nx*ny): line L starts at (L % nx) + (L / nx) * outer.
+// In place on the coefficient image; `causal` is that image when C is double, so neither pointer is __restrict__: the load
+// of coef[n] must stay ahead of the store to causal[n] (the lane reads position n, then writes it).
+template <class C>
+__global__ __launch_bounds__(256) void k_bs_lines(C *coef, double *causal, BsAxis a, long long nx, long long nLines,
+                                                  long long outer, long long stride) {
+  const long long L = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (L >= nLines || a.n == 1) return;             // a line of one pixel is left alone
+  const long long base = (L % nx) + (L / nx) * outer;
+  const long long N = a.n;
+  auto S = [&](long long i) -> double { return (double)coef[base + i * stride] * a.gain; };
+  double prev = bs_causal_init(a, S);
+  causal[base] = prev;
+  double before = prev;
+#pragma unroll 8
+  for (long long n = 1; n < N; n++) {
+    const double c = S(n) + a.z * prev;            // m_Scratch[n] += z * m_Scratch[n - 1]
+    causal[base + n * stride] = c;
+    before = prev;
+    prev = c;
+  }
+  double next = a.anti * (a.z * before + prev);    // c[N-1] = z/(z*z-1) * (z*c[N-2] + c[N-1])
+  coef[base + (N - 1) * stride] = (C)next;
+#pragma unroll 8
+  for (long long n = N - 2; n >= 0; n--) {
+    next = a.z * (next - causal[base + n * stride]);
+    coef[base + n * stride] = (C)next;
+  }
+}
+
+// lines along x, 64 rows per wave through LDS; reads the voxels (rounded to C first), writes the coefficient image
+template <class TIn, class C>
+__global__ __launch_bounds__(64) void k_bs_rows(const TIn *__restrict__ in, C *coef, double *causal, BsAxis a, long long nRows) {
+  __shared__ double tile[64][BS_TW + 1];
+  const int lane = threadIdx.x;
+  const long long row0 = (long long)blockIdx.x * 64;
+  const long long N = a.n;
+  const int rows = nRows - row0 < 64 ? (int)(nRows - row0) : 64;
+  const bool active = lane < rows;
+  if (N == 1) {                                    // a line of one pixel is left alone: the copy alone
+    if (active) coef[row0 + lane] = (C)in[row0 + lane];
+    return;
+  }
+  double prev = 0.0, before = 0.0;
+  for (long long t0 = 0; t0 < N; t0 += BS_TW) {
+    const int w = N - t0 < BS_TW ? (int)(N - t0) : BS_TW;
+    for (int e = lane; e < 64 * BS_TW; e += 64) {
+      const int r = e / BS_TW, col = e % BS_TW;
+      if (r < rows && col < w) tile[r][col] = (double)(C)in[(row0 + r) * N + t0 + col] * a.gain;
+    }
+    __syncthreads();
+    if (active) {
+      int col = 0;
+      if (t0 == 0) {
+        prev = bs_causal_init(a, [&](long long i) -> double { return tile[lane][i]; });
+        tile[lane][0] = prev;
+        before = prev;
+        col = 1;
+      }
+      for (; col < w; col++) {
+        const double c = tile[lane][col] + a.z * prev;
+        tile[lane][col] = c;
+        before = prev;
+        prev = c;
+      }
+    }
+    __syncthreads();
+    for (int e = lane; e < 64 * BS_TW; e += 64) {
+      const int r = e / BS_TW, col = e % BS_TW;
+      if (r < rows && col < w) causal[(row0 + r) * N + t0 + col] = tile[r][col];
+    }
+    __syncthreads();
+  }
+  const long long last = ((N - 1) / BS_TW) * BS_TW;
+  double next = 0.0;
+  for (long long t0 = last; t0 >= 0; t0 -= BS_TW) {
+    const int w = N - t0 < BS_TW ? (int)(N - t0) : BS_TW;
+    for (int e = lane; e < 64 * BS_TW; e += 64) {
+      const int r = e / BS_TW, col = e % BS_TW;
+      if (r < rows && col < w) tile[r][col] = causal[(row0 + r) * N + t0 + col];
+    }
+    __syncthreads();
+    if (active) {
+      int col = w - 1;
+      if (t0 == last) {
+        next = a.anti * (a.z * before + prev);
+        tile[lane][col] = next;
+        col--;
+      }
+      for (; col >= 0; col--) {
+        next = a.z * (next - tile[lane][col]);
+        tile[lane][col] = next;
+      }
+    }
+    __syncthreads();
+    for (int e = lane; e < 64 * BS_TW; e += 64) {
+      const int r = e / BS_TW, col = e % BS_TW;
+      if (r < rows && col < w) coef[(row0 + r) * N + t0 + col] = (C)tile[r][col];
+    }
+    __syncthreads();
+  }
+}
+
+// ITK 3.x mirror boundary on a buffer position (index - region start): period 2N-2, reflected into [0, N)
+__device__ __forceinline__ long long bs_mirror(long long e, long long N) {
+  if (e >= 0 && e < N) return e;                   // (what the general form gives inside, without the divisions)
+  if (N == 1) return 0;
+  const long long L2 = 2 * N - 2;
+  e = (e < 0) ? (-e - L2 * ((-e) / L2)) : (e - L2 * (e / L2));
+  if (N <= e) e = L2 - e;
+  return e;
+}
+
+// EvaluateAtContinuousIndex of order 3 at the point q (ITK's Evaluate: the continuous index of TransformPhysicalPointTo-
+// ContinuousIndex, computed in double and cast to the coordinate type, which is C here)
+template <class C>
+__device__ double bspline_value(const C *__restrict__ coef, const Geo &geo, const int n[3], const float q[3]) {
+  double wt[3][4];
+  int at[3][4];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    double ci = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) ci += geo.p2i[r * 3 + k] * ((double)q[k] - geo.origin[k]);
+    const C x = (C)ci;
+    double f = (double)floorf((float)x);           // DetermineRegionOfSupport: floor((float)x[n]) - 3/2
+    if (!(fabs(f) <= 1099511627776.0)) f = 0.0;    // (not finite, or beyond 2^40: the taps of index 0, as itkBSplineLite.h)
+    const long long i1 = (long long)f;
+    const double w = (double)x - (double)i1;       // SetInterpolationWeights, case 3
+    wt[r][3] = (1.0 / 6.0) * w * w * w;
+    wt[r][0] = (1.0 / 6.0) + 0.5 * w * (w - 1.0) - wt[r][3];
+    wt[r][2] = w + wt[r][0] - 2.0 * wt[r][3];
+    wt[r][1] = 1.0 - wt[r][0] - wt[r][2] - wt[r][3];
+#pragma unroll
+    for (int k = 0; k < 4; k++) at[r][k] = (int)bs_mirror(i1 - 1 + k - geo.istart[r], n[r]);
+  }
+  double wxy[16];
+#pragma unroll
+  for (int py = 0; py < 4; py++)
+#pragma unroll
+    for (int px = 0; px < 4; px++) wxy[py * 4 + px] = wt[0][px] * wt[1][py];   // (w = 1.0; w *= wx; w *= wy: the same product)
+  double interpolated = 0.0;
+#pragma unroll
+  for (int pz = 0; pz < 4; pz++) {
+    const C *plane = coef + (size_t)at[2][pz] * n[1] * n[0];
+#pragma unroll
+    for (int py = 0; py < 4; py++) {
+      const C *row = plane + (size_t)at[1][py] * n[0];
+#pragma unroll
+      for (int px = 0; px < 4; px++) interpolated += (wxy[py * 4 + px] * wt[2][pz]) * (double)row[at[0][px]];
+    }
+  }
+  return interpolated;
+}
+
+// the default branch of the walk (txx:439-474) with the B-spline value: one lane per vertex, as k_project_variant
+template <class T, class C>
+__global__ __launch_bounds__(256) void k_project_bspline(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentity,
+                                                         float *__restrict__ points, u64 nPoints, Totals *__restrict__ tot,
+                                                         const C *__restrict__ coef) {
+  const int lane = threadIdx.x & 63;
+  const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned passes = 0;
+  bool byThr = false, bySteps = false;
+  if (idx < nPoints) {
+    VariantCtx<T> x;
+    x.s = Sampler<T>{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+    x.geo = geo;
+    x.dirIdentity = dirIdentity != 0;
+    x.unitP2I = true;
+    for (int i = 0; i < 9; i++) x.unitP2I = x.unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
+    x.n[0] = g.nx; x.n[1] = g.ny; x.n[2] = (int)g.gnz;
+    x.iso = (double)iso_as<T>(prm.iso, prm.isoInt);
+    x.gimg = nullptr;
+    x.held = HeldGradient{};
+    x.heldUnitP2I = false;
+    const int n[3] = {g.nx, g.ny, g.nzb};
+    float vertex[3] = {points[3 * idx], points[3 * idx + 1], points[3 * idx + 2]};
+    double normal[3];
+    double step = prm.step;
+    unsigned numberOfSteps = 0;
+    for (;;) {
+      passes++;
+      variant_normal(x, vertex, normal);                                          // txx:451-452
+      const double value = bspline_value<C>(coef, geo, n, vertex);                // txx:455
+      if (fabs(value - x.iso) < prm.thr) { byThr = true; break; }                 // txx:456-460
+      const double sign = (value < x.iso) ? +1.0 : -1.0;                          // txx:463
+#pragma unroll
+      for (int k = 0; k < 3; k++) vertex[k] = (float)((double)vertex[k] + (normal[k] * sign * step));   // txx:464-467
+      step *= prm.relax;                                                          // txx:468
+      if (numberOfSteps++ > prm.max_steps) { bySteps = true; break; }             // txx:469-473
+    }
+    points[3 * idx] = vertex[0]; points[3 * idx + 1] = vertex[1]; points[3 * idx + 2] = vertex[2];
+  }
+  unsigned sum = passes;
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) sum += __shfl_down(sum, sft, 64);
+  if (lane == 0 && sum) atomicAdd(&tot->iters, (u64)sum);
+  // both ways a walk ends are counted here (k_project counts the rare one only): the host checks they add up to n_points
+  const u64 nThr = __ballot(byThr), nSteps = __ballot(bySteps);
+  if (lane == 0 && nThr) atomicAdd(&tot->stopThr, (u64)__popcll(nThr));
+  if (lane == 0 && nSteps) atomicAdd(&tot->stopSteps, (u64)__popcll(nSteps));
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <class F>
@@ -3675,6 +3918,48 @@ hipError_t launch_recursive_gaussian(int pixel_type, const Workspace &w, const G
   }
   hipLaunchKernelGGL(k_rg_direction, dim3(grid_for(nvox, 256, 0)), dim3(256), 0, s, w.gradImg, geo, nvox);
   return hipGetLastError();
+}
+
+// The order-3 B-spline coefficient image of the whole volume (K4d): x, y, z passes, each complete before the next.
+hipError_t launch_bspline_prefilter(int pixel_type, const void *vox, const Grid &g, const BsAxis ax[3], void *coef, int coefBits,
+                                    double *scratch, hipStream_t s) {
+  const long long nx = g.nx, ny = g.ny, nz = g.nzb;
+  auto run = [&](auto *ctag) -> hipError_t {
+    typedef typename std::remove_pointer<decltype(ctag)>::type C;
+    C *c = (C *)coef;
+    double *causal = sizeof(C) == 8 ? (double *)coef : scratch;   // (C is double: the causal values go where they end up)
+    const long long nRows = ny * nz;
+    hipError_t e = by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+      typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+      hipLaunchKernelGGL((k_bs_rows<T, C>), dim3((unsigned)((nRows + 63) / 64)), dim3(64), 0, s, (const T *)vox, c, causal, ax[0], nRows);
+      return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    const long long yLines = nx * nz, zLines = nx * ny;
+    hipLaunchKernelGGL((k_bs_lines<C>), dim3((unsigned)((yLines + 255) / 256)), dim3(256), 0, s, c, causal, ax[1], nx, yLines,
+                       nx * ny, nx);
+    hipLaunchKernelGGL((k_bs_lines<C>), dim3((unsigned)((zLines + 255) / 256)), dim3(256), 0, s, c, causal, ax[2], nx, zLines,
+                       nx, nx * ny);
+    return hipGetLastError();
+  };
+  return coefBits == 64 ? run((double *)nullptr) : run((float *)nullptr);
+}
+
+hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, const Params &p, u64 nPoints,
+                                  const void *coef, int coefBits, hipStream_t s) {
+  if (nPoints == 0) return hipSuccess;
+  int dirIdentity = 1;
+  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+    typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+    if (coefBits == 64)
+      hipLaunchKernelGGL((k_project_bspline<T, double>), dim3(grid_for(nPoints, 256, 0)), dim3(256), 0, s, (const T *)w.vox, g, geo, p,
+                         dirIdentity, w.points, nPoints, w.totals, (const double *)coef);
+    else
+      hipLaunchKernelGGL((k_project_bspline<T, float>), dim3(grid_for(nPoints, 256, 0)), dim3(256), 0, s, (const T *)w.vox, g, geo, p,
+                         dirIdentity, w.points, nPoints, w.totals, (const float *)coef);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace cuberille

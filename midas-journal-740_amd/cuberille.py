@@ -351,6 +351,29 @@ class Extractor:
         along it.  hold=False drops the image and returns to the default: each volume's own gradient."""
         _abi.check(self._ctx, self._lib.cuberille_hold_gradient(self._ctx, 1 if hold else 0))
 
+    def set_interpolator(self, kind, spline_order=3, coordinate_bits=32, coefficient_bits=32):
+        """The value interpolator of the walk for the later extractions (cuberille_set_interpolator): _abi.INTERP_LINEAR
+        (the default) or _abi.INTERP_BSPLINE -- itk::BSplineInterpolateImageFunction of spline_order 3, <float, float>
+        (bits 32, 32) or <double, double> (64, 64), its coefficient image computed on the device."""
+        _abi.check(self._ctx, self._lib.cuberille_set_interpolator(self._ctx, int(kind), int(spline_order), int(coordinate_bits),
+                                                                   int(coefficient_bits)))
+
+    def bspline_coefficients(self, dims_xyz=None, bits=None):
+        """The coefficient image of the last B-spline extraction as an array (nz, ny, nx) of float32 / float64, sized from
+        the context's own record of it (cuberille_bspline_coefficients_info).  dims_xyz / bits, when given, must match it."""
+        dims = (C.c_int64 * 3)()
+        have = C.c_int()
+        if not self._lib.cuberille_bspline_coefficients_info(self._ctx, dims, C.byref(have)):
+            raise _abi.CuberilleError(_abi.ERR_STATE, "no B-spline extraction on this context has projected a vertex")
+        nx, ny, nz = (int(v) for v in dims)
+        if dims_xyz is not None and tuple(int(v) for v in dims_xyz) != (nx, ny, nz):
+            raise ValueError("the coefficient image held is %dx%dx%d, not %s" % (nx, ny, nz, tuple(dims_xyz)))
+        if bits is not None and int(bits) != have.value:
+            raise ValueError("the coefficient image held is %d bits wide, not %d" % (have.value, bits))
+        out = np.empty((nz, ny, nx), dtype=np.float64 if have.value == 64 else np.float32)
+        _abi.check(self._ctx, self._lib.cuberille_bspline_coefficients(self._ctx, C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
     @property
     def gradient_held(self):
         """None, or the (nz, ny, nx) of the volume whose gradient image the extractor holds."""
@@ -464,6 +487,7 @@ class CuberilleImageToMeshFilter:
         self._variant = PROJECT_DEFAULT           # h:22-23: both alternative branches are compiled out
         self._gradient = GRADIENT_CENTRAL         # h:21: and so is the recursive-Gaussian gradient
         self._stale_gradient = False
+        self._bspline = None                      # (coordinate bits, coefficient bits) of SetBSplineInterpolator, or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -580,6 +604,23 @@ class CuberilleImageToMeshFilter:
     def GetReproduceStaleGradient(self):
         return self._stale_gradient
 
+    def SetBSplineInterpolator(self, order=3, coordinate=np.float32, coefficient=np.float32):
+        """Stands for SetInterpolator(itk::BSplineInterpolateImageFunction<TImage, coordinate, coefficient>) with
+        SetSplineOrder(order) -- the reference driver's USE_BSPLINE_INTERPOLATOR configuration -- walked on the device
+        (cuberille_set_interpolator).  coordinate / coefficient: float32 or float64 (or 32 / 64), the same for both; order 3.
+        Update() then raises on anything the library refuses (a projection variant, the recursive-Gaussian gradient, a
+        reproduced stale gradient)."""
+        def bits(t):
+            return int(t) if isinstance(t, int) else np.dtype(t).itemsize * 8
+        cb, kb = bits(coordinate), bits(coefficient)
+        if int(order) != 3 or cb != kb or cb not in (32, 64):
+            raise ValueError("the device B-spline walk implements order 3 with float32/float32 or float64/float64")
+        self._bspline = (cb, kb)
+
+    def SetLinearInterpolator(self):
+        """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
+        self._bspline = None
+
     def Update(self):
         if self._input is None:
             # the ITK pipeline throws for a missing required input (txx:33)
@@ -591,6 +632,10 @@ class CuberilleImageToMeshFilter:
         prm = make_params(self._iso, self._triangles, self._project, self._threshold, self._step, self._relax,
                           self._max_steps, self._q1, self._variant, self._gradient)
         self._extractor.hold_gradient(self._stale_gradient)
+        if self._bspline:
+            self._extractor.set_interpolator(_abi.INTERP_BSPLINE, 3, *self._bspline)
+        else:
+            self._extractor.set_interpolator(_abi.INTERP_LINEAR)
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
 

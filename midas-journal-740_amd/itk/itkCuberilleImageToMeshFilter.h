@@ -117,7 +117,9 @@ public:
   /** The image to polygonize (reference h:184, txx:53-56). */
   virtual void SetInput(const InputImageType *inputImage);
 
-  /** Interpolator (reference h:187-188).  The kernels implement LinearInterpolateImageFunction<TInputImage,double>;
+  /** Interpolator (reference h:187-188).  The kernels implement LinearInterpolateImageFunction<TInputImage,double> and,
+   *  through SetBSplineOnDevice below, BSplineInterpolateImageFunction<TInputImage,float,float> / <...,double,double> of
+   *  spline order 3 (the reference driver's USE_BSPLINE_INTERPOLATOR configuration, Testing/CuberilleTest01.cxx:148-151);
    *  with any other type the GPU still does the topology and the lattice points, and the walk of txx:439-474 runs on
    *  the host through the user's Evaluate() -- on the calling thread, as the reference does (txx:455), unless
    *  SetHostWalkThreads asks for more (the interpolator must then be safe to call from several threads at once). */
@@ -193,6 +195,19 @@ public:
   itkSetMacro(ReproduceStaleGradient, bool);
   itkBooleanMacro(ReproduceStaleGradient);
 
+  /** Not in the reference.  With TInterpolator = BSplineInterpolateImageFunction<TInputImage, float, float> or
+   *  <TInputImage, double, double> whose spline order is 3 at Update(), projection on, the default projection branch, the
+   *  central-difference gradient and ReproduceStaleGradient off, the walk runs on the GPU (cuberille_set_interpolator):
+   *  the library computes the coefficient image itself and evaluates the 64 taps there, and the quads are split on the
+   *  device.  The user's interpolator object then only supplies its spline order; it is not given the image (that would
+   *  cost the host prefilter the device route exists to avoid).  The device route restates itk_lite/itkBSplineLite.h bit
+   *  for bit; against real ITK's class it may differ in the last bits.  false: every update
+   *  walks on the host through the user's own object -- with real ITK, the way to get ITK's own coefficients.  Default
+   *  true.  Every other configuration takes the host walk whatever this says. */
+  itkGetMacro(BSplineOnDevice, bool);
+  itkSetMacro(BSplineOnDevice, bool);
+  itkBooleanMacro(BSplineOnDevice);
+
 protected:
   CuberilleImageToMeshFilter();
   ~CuberilleImageToMeshFilter();
@@ -218,6 +233,7 @@ private:
   unsigned int m_HostWalkThreads;
   bool m_ReleaseHostMeshAfterFill;
   bool m_ReproduceStaleGradient;
+  bool m_BSplineOnDevice;
   double m_LastDeviceSeconds;
   double m_LastMeshFillSeconds;
   double m_LastExtractSeconds;

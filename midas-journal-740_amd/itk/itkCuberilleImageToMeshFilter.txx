@@ -7,6 +7,7 @@
 
 #include "itkCuberilleImageToMeshFilter.h"
 #include "itkMetaDataObject.h"
+#include "itkBSplineInterpolateImageFunction.h"
 #include "cuberille_hip.h"
 
 #include <cmath>
@@ -450,6 +451,15 @@ inline void SplitQuads(const float *points, const uint64_t *quads, uint64_t nQua
 // the one interpolator the kernels implement (I5: linear, double coordinates)
 template <class TInterpolator, class TImage> struct IsGpuInterpolator { enum { Value = 0 }; };
 template <class TImage> struct IsGpuInterpolator<LinearInterpolateImageFunction<TImage, double>, TImage> { enum { Value = 1 }; };
+
+// ... and the B-spline one the kernels implement on request (SetBSplineOnDevice): coordinate and coefficient type both float
+// or both double; Bits = their width, 0 for every other interpolator
+template <class TInterpolator, class TImage> struct DeviceBSpline { enum { Bits = 0 }; };
+template <class TImage> struct DeviceBSpline<BSplineInterpolateImageFunction<TImage, float, float>, TImage> { enum { Bits = 32 }; };
+template <class TImage> struct DeviceBSpline<BSplineInterpolateImageFunction<TImage, double, double>, TImage> { enum { Bits = 64 }; };
+// the spline order of the user's object, read only where the type has one
+template <class TInterpolator> unsigned int SplineOrderOf(const TInterpolator *i, FillTag<true>) { return i->GetSplineOrder(); }
+template <class TInterpolator> unsigned int SplineOrderOf(const TInterpolator *, FillTag<false>) { return 0; }
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
@@ -468,6 +478,7 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_HostWalkThreads = 1;
   m_ReleaseHostMeshAfterFill = false;
   m_ReproduceStaleGradient = false;
+  m_BSplineOnDevice = true;
   m_LastDeviceSeconds = 0.0;
   m_LastMeshFillSeconds = 0.0;
   m_LastExtractSeconds = 0.0;
@@ -529,9 +540,16 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   const unsigned int Dim = InputImageType::ImageDimension;
   if (Dim != 3) itkExceptionMacro(<< "the cuberille path is three-dimensional");
   if (cuberille_detail::PixelCode<InputPixelType>::Value < 0) itkExceptionMacro(<< "unsupported pixel type");
-  // any other TInterpolator than the linear one the kernels implement: topology and lattice points on the GPU,
-  // the walk on the host through the user's interpolator (see HostWalk above)
-  const bool hostWalk = m_ProjectVerticesToIsoSurface && !cuberille_detail::IsGpuInterpolator<TInterpolator, TInputImage>::Value;
+  // the B-spline interpolator of order 3 walks on the device where the library offers it (SetBSplineOnDevice); any other
+  // TInterpolator than the linear one the kernels implement: topology and lattice points on the GPU, the walk on the host
+  // through the user's interpolator (see HostWalk above)
+  const int bsplineBits = cuberille_detail::DeviceBSpline<TInterpolator, TInputImage>::Bits;
+  if (m_Interpolator.IsNull()) m_Interpolator = InterpolatorType::New();
+  const bool deviceBSpline = bsplineBits != 0 && m_BSplineOnDevice && m_ProjectVerticesToIsoSurface && !USE_ADVANCED_PROJECTION &&
+                             !USE_LINESEARCH_PROJECTION && !USE_GRADIENT_RECURSIVE_GAUSSIAN && !m_ReproduceStaleGradient &&
+                             cuberille_detail::SplineOrderOf(m_Interpolator.GetPointer(), cuberille_detail::FillTag<bsplineBits != 0>()) == 3;
+  const bool hostWalk = m_ProjectVerticesToIsoSurface && !cuberille_detail::IsGpuInterpolator<TInterpolator, TInputImage>::Value &&
+                        !deviceBSpline;
 
   // parameter resolution exactly where the reference does it: largest spacing, then the default
   // step length, which sticks to the filter object once resolved
@@ -539,8 +557,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   for (unsigned int i = 1; i < Dim; i++)
     if (image->GetSpacing()[i] > m_MaxSpacing) m_MaxSpacing = image->GetSpacing()[i];
   if (m_ProjectVertexStepLength < 0.0) m_ProjectVertexStepLength = m_MaxSpacing * 0.25;
-  if (m_Interpolator.IsNull()) m_Interpolator = InterpolatorType::New();
-  m_Interpolator->SetInputImage(image);
+  if (!deviceBSpline) m_Interpolator->SetInputImage(image);   // (the device route computes its own coefficients)
 
   cuberille_image_desc desc;
   (void)cuberille_detail::DescribeImage(image.GetPointer(), desc);      // (an empty region is the library's to refuse)
@@ -567,6 +584,9 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   this->AcquireContext(true);
   if (cuberille_hold_gradient(m_Context, (m_ReproduceStaleGradient && !hostWalk) ? 1 : 0) != CUBERILLE_OK)
     itkExceptionMacro(<< "cuberille_hold_gradient: " << cuberille_last_error(m_Context));
+  if (cuberille_set_interpolator(m_Context, deviceBSpline ? CUBERILLE_INTERP_BSPLINE : CUBERILLE_INTERP_LINEAR, 3,
+                                 deviceBSpline ? bsplineBits : 0, deviceBSpline ? bsplineBits : 0) != CUBERILLE_OK)
+    itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
   cuberille_result res;
   const double extractStart = cuberille_detail::WallSeconds();
   if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)

@@ -655,7 +655,7 @@ template <class TPixel, unsigned int VDimension = 3, class TTraits = void> class
 template <class TIn, class TOut> class BinaryThresholdImageFilter;
 template <class TIn, class TOut> class BinaryMask3DMeshSource;
 template <class TImage> class ImageFileWriter;
-template <class TImage, class TCoordRep = double, class TCoefficientType = double> class BSplineInterpolateImageFunction;
+template <class TImage, class TCoordRep = double, class TCoefficientType = double> class BSplineInterpolateImageFunction;   // (defined in itkBSplineLite.h)
 template <class TIn, class TOut, class TCriterion> class QuadEdgeMeshQuadricDecimation;
 template <class TMesh> class NumberOfFacesCriterion;
 template <class TImage> class ConstShapedNeighborhoodIterator;
