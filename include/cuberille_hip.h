@@ -380,6 +380,54 @@ int cuberille_bspline_coefficients(cuberille_ctx *ctx, void *host_out, size_t ca
  * (x, y, z) and coefficient_bits its width (32 or 64) -- else 0 (zeros written).  Either pointer may be null. */
 int cuberille_bspline_coefficients_info(cuberille_ctx *ctx, int64_t dims[3], int *coefficient_bits);
 
+/* NEW SYMBOLS (added within ABI 13: no existing struct or symbol changes).
+ * A context group: N contexts driven together by one call, for a caller that holds the whole volume in host memory (the
+ * reference's driver: SetInput(image); Update()) on a node with several GPUs.  Member i owns slab i of the volume, slabs of
+ * equal thickness along z; its buffer is the owned range widened by cuberille_required_halo (the full halo, never
+ * CUBERILLE_SLAB_THIN_HALO) and clipped to the volume, uploaded straight from the caller's image on the member's own stream
+ * and link -- no member needs another's voxels, so there is no halo exchange, no collective and no peer-to-peer copy.  The
+ * counts are summed on the host, quirk Q1 across a cut (the four calls above) is handed over through host memory, and the
+ * slabs' meshes land in disjoint ranges of one host mesh the group owns: the same ids, cell order and bits as
+ * cuberille_extract_host of the whole volume on one context.  Device ids may repeat (N contexts on one GPU share its link:
+ * that measures the group's overhead, not scaling).  Not thread-safe; distinct groups are independent.
+ * cuberille_group_create: 1 <= n <= 64, else CUBERILLE_ERR_ARGUMENT (the text of a failed create: cuberille_group_last_error(NULL)).
+ * cuberille_group_context: member i, e.g. for cuberille_debug_set_option; null outside [0, n).  Do not extract on it directly
+ *   between a group extraction and the reads of its mesh.
+ * cuberille_group_plan (needs no GPU): the cuts the group would use for this image and these parameters.  *n_used = min(n, Nz)
+ *   members take part; bounds[4 i .. 4 i + 3] = own_z0, own_z1, buf_z0, buf_z1 of slab i (room for 4 n entries).  Slab i's
+ *   description is the image's with dims[2] = buf_z1 - buf_z0, its cuberille_slab {Nz, buf_z0, own_z0, own_z1, 0, 0}.
+ *   CUBERILLE_ERR_ARGUMENT for n outside 1 .. 64 and for CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN with projection (it needs
+ *   whole lines, as on any slab).
+ * cuberille_group_warm_up: cuberille_warm_up of every member with its slab's description (img may be null).
+ * cuberille_group_extract_host: one host thread per slab uploads and counts its slab (below a GiB per slab one plain copy,
+ *   from a GiB the chunked pipeline of cuberille_extract_host; the host staging threads of ONE context are split between the
+ *   slabs, at least one each) and starts its vertex phase when no other slab can change its counts; the host then plans and
+ *   stages quirk Q1's hand-overs, the slabs emit (those of a hand-over in rank order, the others at once).  *res: n_points,
+ *   n_cells and the walk counters summed over the slabs, verts_per_cell as usual, every ms_* field the LARGEST of the slabs'
+ *   (they run side by side).  Refused with CUBERILLE_ERR_ARGUMENT and a message: the recursive-Gaussian gradient with
+ *   projection, a member with the B-spline interpolator set (cuberille_set_interpolator), a member holding a gradient
+ *   (cuberille_hold_gradient).  A failure on any slab drains every member's streams and returns its status; the text names
+ *   the slab and the call.  The group stays usable.
+ * cuberille_group_slab_result: slab i's own result of the last extraction (i < n_used).
+ * cuberille_group_mesh_host / _release_host_mesh / _mesh_write_vtk: as cuberille_mesh_host / cuberille_release_host_mesh /
+ *   cuberille_mesh_write_vtk, for the assembled mesh (cells hold global ids).
+ * cuberille_group_debug_fail_alloc: failure drill -- the n-th device allocation that slab `slab`'s thread makes during the
+ *   upload and count of the NEXT extraction reports out-of-memory (slab -1: every slab's; n < 0: off). */
+typedef struct cuberille_group cuberille_group;
+int cuberille_group_create(cuberille_group **out, const int *device_ids, int n);
+void cuberille_group_destroy(cuberille_group *g);
+const char *cuberille_group_last_error(const cuberille_group *g);
+cuberille_ctx *cuberille_group_context(cuberille_group *g, int i);
+int cuberille_group_plan(const cuberille_image_desc *img, const cuberille_params *prm, int n, int64_t *bounds, int *n_used);
+int cuberille_group_warm_up(cuberille_group *g, const cuberille_image_desc *img, const cuberille_params *prm);
+int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc *img, const void *host_voxels,
+                                 const cuberille_params *prm, cuberille_result *res);
+int cuberille_group_slab_result(const cuberille_group *g, int i, cuberille_result *res);
+int cuberille_group_mesh_host(cuberille_group *g, float **points, uint64_t **cells);
+int cuberille_group_release_host_mesh(cuberille_group *g);
+int cuberille_group_mesh_write_vtk(cuberille_group *g, const char *path, int n_threads);
+int cuberille_group_debug_fail_alloc(cuberille_group *g, int slab, int64_t n);
+
 /* Flat-mesh file output (replaces the itk::Mesh fill + itk::VTKPolyDataWriter pass of
  * Testing/CuberilleTest01.cxx:161-187 for callers that keep the flat buffers): legacy-ASCII VTK POLYDATA in
  * the layout of that writer (header lines, "POINTS n float", "POLYGONS m k"), coordinates with 9 significant

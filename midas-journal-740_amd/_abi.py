@@ -31,7 +31,12 @@ EXPORTS = [
     "cuberille_slice_counts", "cuberille_failed_row", "cuberille_warm_up", "cuberille_mesh_host", "cuberille_step_classify", "cuberille_step_count",
     "cuberille_release_host_mesh", "cuberille_hold_gradient", "cuberille_gradient_held",
     "cuberille_set_interpolator", "cuberille_bspline_coefficients", "cuberille_bspline_coefficients_info",
+    "cuberille_group_create", "cuberille_group_destroy", "cuberille_group_last_error", "cuberille_group_context",
+    "cuberille_group_plan", "cuberille_group_warm_up", "cuberille_group_extract_host", "cuberille_group_slab_result",
+    "cuberille_group_mesh_host", "cuberille_group_release_host_mesh", "cuberille_group_mesh_write_vtk",
+    "cuberille_group_debug_fail_alloc",
 ]
+GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
 
 
@@ -157,6 +162,21 @@ def lib():
     L.cuberille_recount.argtypes = [vp, vp, u64p, u64p]
     L.cuberille_alias_plane_device.argtypes = [vp, C.c_int64, vp, vp]
     L.cuberille_set_alias_plane.argtypes = [vp, vp, vp]
+    L.cuberille_group_create.argtypes = [C.POINTER(vp), C.POINTER(C.c_int), C.c_int]
+    L.cuberille_group_destroy.argtypes = [vp]
+    L.cuberille_group_destroy.restype = None
+    L.cuberille_group_last_error.argtypes = [vp]
+    L.cuberille_group_last_error.restype = C.c_char_p
+    L.cuberille_group_context.argtypes = [vp, C.c_int]
+    L.cuberille_group_context.restype = vp
+    L.cuberille_group_plan.argtypes = [C.POINTER(ImageDesc), C.POINTER(Params), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.cuberille_group_warm_up.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(Params)]
+    L.cuberille_group_extract_host.argtypes = [vp, C.POINTER(ImageDesc), vp, C.POINTER(Params), C.POINTER(Result)]
+    L.cuberille_group_slab_result.argtypes = [vp, C.c_int, C.POINTER(Result)]
+    L.cuberille_group_mesh_host.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.cuberille_group_release_host_mesh.argtypes = [vp]
+    L.cuberille_group_mesh_write_vtk.argtypes = [vp, C.c_char_p, C.c_int]
+    L.cuberille_group_debug_fail_alloc.argtypes = [vp, C.c_int, C.c_int64]
     _lib = L
     return L
 
@@ -171,6 +191,12 @@ def failed_row():
     if rc != OK:
         raise CuberilleError(rc, "cuberille_failed_row")
     return row
+
+
+def check_group(group, rc):
+    if rc != OK:
+        text = lib().cuberille_group_last_error(group)
+        raise CuberilleError(rc, text.decode("utf-8", "replace") if text else "")
 
 
 def check(ctx, rc):

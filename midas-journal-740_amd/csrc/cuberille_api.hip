@@ -9,6 +9,7 @@
 #include "../../include/cuberille_hip.h"
 #include "cuberille_internal.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -124,6 +125,8 @@ struct cuberille_ctx {
   void *stage[2] = {nullptr, nullptr};
   size_t stageBytes = 0;
   hipEvent_t stageFree[2] = {}, chunkIn[2] = {};
+  int poolThreads = 0;                   // host threads of a chunked copy (StagePool); 0: the single-context rule.  A
+                                         // cuberille_group splits that budget across its members
   bool aliasBelowBuffer = false;         // soft condition of the last slab count (cuberille_slab_info)
   bool aliasMustResolve = false;         // ... and it is certain: the source slice lies in this slab's own halo
   int aliasZ = -1;                       // local slice whose Q1 source is unresolved (the first occupied counted slice), -1
@@ -1388,11 +1391,16 @@ void drain(cuberille_ctx *c) {
 // share of every chunk (a single memcpy stream cannot feed a PCIe Gen5 link; a handful can).  move(i, a, b) moves bytes
 // [a, b) of chunk i; the threads take chunk i once release(i) has been called, and wait(i) returns when all of them are
 // done with it.  Destruction lets them finish what has been released and joins them.
+// threads: 0 = the rule of one context (8 where the host has 16 cores or more).
+int pool_threads_default() {
+  const unsigned hw = std::thread::hardware_concurrency();
+  return (int)(hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1));
+}
+
 struct StagePool {
   template <class Move>
-  StagePool(size_t total, size_t chunk, Move move) : done_((total + chunk - 1) / chunk) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    n_ = (int)(hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1));
+  StagePool(size_t total, size_t chunk, Move move, int threads = 0) : done_((total + chunk - 1) / chunk) {
+    n_ = threads > 0 ? threads : pool_threads_default();
     for (auto &d : done_) d.store(0);
     for (int t = 0; t < n_; t++)
       threads_.emplace_back([this, t, total, chunk, move] {
@@ -1421,16 +1429,17 @@ struct StagePool {
   std::vector<std::thread> threads_;
 };
 
-// The extraction of a volume uploaded in chunks through the staging slots (of stageBytes): chunk i (slices [z0, z1)) goes
+// The count of a volume uploaded in chunks through the staging slots (of stageBytes): chunk i (slices [z0, z1)) goes
 // through slot i & 1 -- wait until the slot is free (chunk i - 2 has crossed the link), fill it (fill(i, slot, z0, z1): 0,
 // or the status with which the caller's source gave up), copy it on the copy stream, threshold it on the context's stream
-// once it has landed.
+// once it has landed.  img describes the buffer (slab: its place in the volume, or null for a whole one); every slice of
+// the buffer is thresholded, as classify_slab does.  The caller emits.
 template <class Fill>
-int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm, size_t stageBytes,
-                    size_t slicesPerChunk, const char *what, Fill fill, cuberille_result *res) {
+int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm, const cuberille_slab *slab,
+                    size_t stageBytes, size_t slicesPerChunk, const char *what, Fill fill) {
   int rc = ensure_staging(c, stageBytes);
   if (rc) return rc;
-  rc = count_prepare(c, img, c->voxOwn.p, prm, nullptr);
+  rc = count_prepare(c, img, c->voxOwn.p, prm, slab);
   if (rc) return rc;
   const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type), nz = (size_t)img->dims[2];
   hipError_t e = hipSuccess;
@@ -1451,9 +1460,33 @@ int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cub
     if (gaveUp) return fail(c, CUBERILLE_ERR_SOURCE, "the chunk source gave up with status " + std::to_string(gaveUp));
     return fail(c, CUBERILLE_ERR_HIP, std::string(what) + hipGetErrorString(e));
   }
-  rc = count_finish(c, nullptr, nullptr);
-  return rc ? rc : cuberille_emit(c, 0, res);
+  return count_finish(c, nullptr, nullptr);
 }
+
+// Large volumes from pageable host memory: z-chunks of whole slices; chunk i is thresholded on the context's stream while
+// chunk i+1 crosses the link and the host threads (c->poolThreads) stage chunk i+2.  The buffer (img) starts `base` bytes
+// into host_voxels.
+constexpr size_t kUploadChunk = 32u << 20;
+int count_host_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels, size_t base,
+                       const cuberille_params *prm, const cuberille_slab *slab) {
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+  const size_t bytes = sliceBytes * (size_t)img->dims[2];
+  const size_t chunk = kUploadChunk / sliceBytes * sliceBytes;
+  const char *src = (const char *)host_voxels + base;
+  StagePool pool(bytes, chunk, [&](size_t i, size_t a, size_t b) {
+    std::memcpy((char *)c->stage[i & 1] + a, src + i * chunk + a, b - a);
+  }, c->poolThreads);
+  return extract_chunked(c, img, prm, slab, kUploadChunk, kUploadChunk / sliceBytes, "overlapped upload: ",
+                         [&](size_t i, void *, size_t, size_t) {
+                           pool.release(i);
+                           pool.wait(i);
+                           return 0;
+                         });
+}
+
+// Where the size rule of cuberille_extract_host sends a buffer of these dimensions: the chunk pipeline (a GiB and more, slices
+// that fit a chunk) or one plain copy.
+bool upload_in_chunks(size_t sliceBytes, size_t bytes) { return bytes >= (1ull << 30) && sliceBytes <= kUploadChunk; }
 
 }  // namespace
 
@@ -1470,22 +1503,12 @@ int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, co
   // below a GiB: one plain copy (the runtime stages pageable memory itself, at link rate once the copy is large; the
   // chunk pipeline below needs some tens of chunks to amortise its start -- measured 34 ms against 11 ms at 512^3 f32);
   // the extraction follows on the stream
-  const size_t kChunk = 32u << 20;
-  if (bytes < (1ull << 30) || sliceBytes > kChunk) {
+  if (!upload_in_chunks(sliceBytes, bytes)) {
     HIP_TRY(c, hipMemcpyAsync(c->voxOwn.p, host_voxels, bytes, hipMemcpyHostToDevice, c->stream));
     return cuberille_extract_device(c, img, c->voxOwn.p, prm, nullptr, res);
   }
-  // large volumes: z-chunks of whole slices; chunk i is thresholded on the context's stream while chunk i+1 crosses the
-  // link and the host threads stage chunk i+2
-  const size_t chunk = kChunk / sliceBytes * sliceBytes;
-  StagePool pool(bytes, chunk, [&](size_t i, size_t a, size_t b) {
-    std::memcpy((char *)c->stage[i & 1] + a, (const char *)host_voxels + i * chunk + a, b - a);
-  });
-  return extract_chunked(c, img, prm, kChunk, kChunk / sliceBytes, "overlapped upload: ", [&](size_t i, void *, size_t, size_t) {
-    pool.release(i);
-    pool.wait(i);
-    return 0;
-  }, res);
+  rc = count_host_chunked(c, img, host_voxels, 0, prm, nullptr);
+  return rc ? rc : cuberille_emit(c, 0, res);
 }
 
 int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, cuberille_chunk_source source, void *user,
@@ -1498,8 +1521,9 @@ int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, 
   HIP_TRY(c, c->voxOwn.reserve(sliceBytes * (size_t)img->dims[2]));
   // chunks of about 32 MiB, whole slices, at least one; the caller's source fills each slot on this thread, in order
   const size_t slicesPerChunk = sliceBytes >= (32u << 20) ? 1 : (32u << 20) / sliceBytes;
-  return extract_chunked(c, img, prm, slicesPerChunk * sliceBytes, slicesPerChunk, "streamed upload: ",
-                         [&](size_t, void *slot, size_t z0, size_t z1) { return source(user, slot, (int64_t)z0, (int64_t)z1); }, res);
+  rc = extract_chunked(c, img, prm, nullptr, slicesPerChunk * sliceBytes, slicesPerChunk, "streamed upload: ",
+                       [&](size_t, void *slot, size_t z0, size_t z1) { return source(user, slot, (int64_t)z0, (int64_t)z1); });
+  return rc ? rc : cuberille_emit(c, 0, res);
 }
 
 int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm) {
@@ -1689,7 +1713,7 @@ int download_pipelined(cuberille_ctx *c, void *dst, const void *src, size_t byte
   auto chunkBytes = [&](size_t i) { return bytes - i * kChunk < kChunk ? bytes - i * kChunk : kChunk; };
   StagePool pool(bytes, kChunk, [&](size_t i, size_t a, size_t b) {
     std::memcpy((char *)dst + i * kChunk + a, (const char *)c->stage[i & 1] + a, b - a);
-  });
+  }, c->poolThreads);
   auto issue = [&](size_t i) -> hipError_t {
     hipError_t e = hipMemcpyAsync(c->stage[i & 1], (const char *)src + i * kChunk, chunkBytes(i), hipMemcpyDeviceToHost, c->copyStream);
     if (e == hipSuccess) e = hipEventRecord(c->chunkIn[i & 1], c->copyStream);
@@ -1843,6 +1867,443 @@ int cuberille_slice_occupancy(cuberille_ctx *c, uint32_t *occupied, size_t n_sli
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(occupied, c->w.sliceOcc, n_slices * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CUBERILLE_OK;
+}
+
+}  // extern "C"
+
+// ---- cuberille_group: N contexts, one host-resident volume, one mesh ------------------------------------------------------
+// Every member uploads its slab plus the full halo straight from the caller's image on its own stream and link, so no
+// member needs another's voxels.  The host sums the counts, plans quirk Q1's hand-overs (distributed.alias_plan, restated)
+// and stages them through host memory, so the same code runs whether the members share a device or not.
+
+struct cuberille_group {
+  std::vector<cuberille_ctx *> ctx;
+  std::string err;
+  int used = 0;                          // members the last extraction cut the volume for (min(n, Nz))
+  std::vector<cuberille_result> slabRes; // ... and each one's result
+  std::vector<u64> pointOff, cellOff;    // ... its first point and first cell in the assembled mesh
+  cuberille_result res{};
+  bool haveMesh = false;
+  HostBuf hostPoints, hostCells;         // cuberille_group_mesh_host: the assembled mesh
+  bool hostMeshValid = false;
+  int drillSlab = -1;                    // cuberille_group_debug_fail_alloc: armed for the next extraction's upload and count
+  long long drillAt = -1;
+};
+
+namespace {
+
+constexpr int kGroupMax = 64;
+
+int gfail(cuberille_group *g, int code, const std::string &msg) {
+  g->err = msg;
+  return code;
+}
+
+// The cuts of a group of n: slabs of equal thickness (distributed.slab_range), each buffer the owned range widened by the
+// full required halo and clipped to the volume.  bounds[4 i ..]: own_z0, own_z1, buf_z0, buf_z1.
+int group_plan_impl(const cuberille_image_desc *img, const cuberille_params *prm, int n, int64_t *bounds, int *n_used,
+                    std::string *why) {
+  auto no = [why](const char *m) { if (why) *why = m; return CUBERILLE_ERR_ARGUMENT; };
+  if (!img || !prm) return no("null image or parameter pointer");
+  if (n < 1 || n > kGroupMax) return no("a group has 1 to 64 members");
+  for (int i = 0; i < 3; i++) {
+    if (img->dims[i] < 1) return no("image dimensions must be >= 1");
+    if (!(img->spacing[i] > 0.0)) return no("spacing must be > 0");
+  }
+  if (prm->project_vertices && prm->gradient_variant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN)
+    return no("the recursive-Gaussian gradient filters whole lines of the volume: not offered on slabs, so not in a group");
+  int64_t below = 0, above = 0;
+  if (cuberille_required_halo(img, prm, &below, &above) != CUBERILLE_OK) return no("bad image description or parameters");
+  const int64_t nz = img->dims[2];
+  const int used = (int64_t)n < nz ? n : (int)nz;
+  const int64_t base = nz / used, rem = nz % used;
+  for (int r = 0; r < used; r++) {
+    const int64_t z0 = r * base + (r < rem ? r : rem), z1 = z0 + base + (r < rem ? 1 : 0);
+    if (bounds) {
+      bounds[4 * r] = z0;
+      bounds[4 * r + 1] = z1;
+      bounds[4 * r + 2] = z0 - below > 0 ? z0 - below : 0;
+      bounds[4 * r + 3] = z1 + above < nz ? z1 + above : nz;
+    }
+  }
+  if (n_used) *n_used = used;
+  return CUBERILLE_OK;
+}
+
+// Let every member's streams finish (a failure on one slab: the others may still be copying from the caller's image).
+void group_drain(cuberille_group *g) {
+  for (cuberille_ctx *c : g->ctx) {
+    if (hipSetDevice(c->device) != hipSuccess) continue;
+    (void)hipStreamSynchronize(c->stream);
+    if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);
+    (void)hipGetLastError();
+  }
+}
+
+// One slab's outcome of a phase: the call that failed and the member's text
+struct SlabStatus {
+  int rc = CUBERILLE_OK;
+  std::string what;
+  void set(int code, const char *call, cuberille_ctx *c) {
+    rc = code;
+    what = std::string(call) + ": " + (c ? c->err : std::string());
+  }
+};
+
+// Run f(i) for i in [0, n) on threads of their own (one per slab), f(0) on the calling thread.
+template <class F> void for_each_slab(int n, F f) {
+  std::vector<std::thread> th;
+  for (int i = 1; i < n; i++) th.emplace_back([&f, i] { f(i); });
+  if (n > 0) f(0);
+  for (auto &t : th) t.join();
+}
+
+// The first failed slab as the group's error (after draining every member), or OK
+int group_failure(cuberille_group *g, const std::vector<SlabStatus> &st) {
+  for (size_t i = 0; i < st.size(); i++)
+    if (st[i].rc != CUBERILLE_OK) {
+      group_drain(g);
+      return gfail(g, st[i].rc, "slab " + std::to_string(i) + ": " + st[i].what);
+    }
+  return CUBERILLE_OK;
+}
+
+// One entry of quirk Q1's hand-over plan: consumer slab, source slab, source slice, whether the consumer needs the plane
+struct AliasEntry { int consumer, source; int64_t zp; bool plane; };
+
+}  // namespace
+
+extern "C" {
+
+int cuberille_group_create(cuberille_group **out, const int *device_ids, int n) {
+  if (!out) return fail(nullptr, CUBERILLE_ERR_ARGUMENT, "null output pointer");
+  *out = nullptr;
+  if (!device_ids || n < 1 || n > kGroupMax) return fail(nullptr, CUBERILLE_ERR_ARGUMENT, "a group has 1 to 64 members");
+  cuberille_group *g = new (std::nothrow) cuberille_group;
+  if (!g) return fail(nullptr, CUBERILLE_ERR_ARGUMENT, "out of host memory");
+  for (int i = 0; i < n; i++) {
+    cuberille_ctx *c = nullptr;
+    const int rc = cuberille_create(&c, device_ids[i]);
+    if (rc != CUBERILLE_OK) {
+      const std::string why = g_create_error;
+      cuberille_group_destroy(g);
+      return fail(nullptr, rc, "member " + std::to_string(i) + " (device " + std::to_string(device_ids[i]) + "): " + why);
+    }
+    g->ctx.push_back(c);
+  }
+  *out = g;
+  return CUBERILLE_OK;
+}
+
+void cuberille_group_destroy(cuberille_group *g) {
+  if (!g) return;
+  for (cuberille_ctx *c : g->ctx) cuberille_destroy(c);
+  g->hostPoints.release();
+  g->hostCells.release();
+  delete g;
+}
+
+const char *cuberille_group_last_error(const cuberille_group *g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+
+cuberille_ctx *cuberille_group_context(cuberille_group *g, int i) {
+  if (!g || i < 0 || i >= (int)g->ctx.size()) return nullptr;
+  return g->ctx[(size_t)i];
+}
+
+int cuberille_group_plan(const cuberille_image_desc *img, const cuberille_params *prm, int n, int64_t *bounds, int *n_used) {
+  return group_plan_impl(img, prm, n, bounds, n_used, nullptr);
+}
+
+int cuberille_group_warm_up(cuberille_group *g, const cuberille_image_desc *img, const cuberille_params *prm) {
+  if (!g) return CUBERILLE_ERR_ARGUMENT;
+  const int n = (int)g->ctx.size();
+  std::vector<int64_t> b(4 * (size_t)n);
+  int used = 0;
+  cuberille_params dflt{};
+  dflt.generate_triangles = 1; dflt.project_vertices = 1; dflt.distance_threshold = 0.5; dflt.step_length = -1.0;
+  dflt.relaxation = 0.95; dflt.max_steps = 50; dflt.emulate_empty_slice_aliasing = 1;
+  if (img) {
+    std::string why;
+    if (group_plan_impl(img, prm ? prm : &dflt, n, b.data(), &used, &why) != CUBERILLE_OK)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "cuberille_group_warm_up: " + why);
+  }
+  const int share = std::max(1, pool_threads_default() / std::max(1, used ? used : n));
+  std::vector<SlabStatus> st((size_t)n);
+  for_each_slab(n, [&](int i) {
+    cuberille_ctx *c = g->ctx[(size_t)i];
+    c->poolThreads = share;
+    int rc;
+    if (i < used) {
+      cuberille_image_desc d = *img;
+      d.dims[2] = b[4 * (size_t)i + 3] - b[4 * (size_t)i + 2];
+      rc = cuberille_warm_up(c, &d, prm);
+    } else {
+      rc = cuberille_warm_up(c, nullptr, nullptr);
+    }
+    if (rc) st[(size_t)i].set(rc, "cuberille_warm_up", c);
+  });
+  return group_failure(g, st);
+}
+
+int cuberille_group_debug_fail_alloc(cuberille_group *g, int slab, int64_t n) {
+  if (!g || slab < -1 || slab >= (int)g->ctx.size()) return CUBERILLE_ERR_ARGUMENT;
+  g->drillSlab = n < 0 ? -1 : slab;
+  g->drillAt = n < 0 ? -1 : (long long)n;
+  return CUBERILLE_OK;
+}
+
+int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc *img, const void *host_voxels,
+                                 const cuberille_params *prm, cuberille_result *res) {
+  if (!g) return CUBERILLE_ERR_ARGUMENT;
+  g->haveMesh = false;
+  g->hostMeshValid = false;
+  const int drillSlab = g->drillSlab;
+  const long long drillAt = g->drillAt;
+  g->drillSlab = -1;                         // (one extraction)
+  g->drillAt = -1;
+  if (!img || !host_voxels || !prm) return gfail(g, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
+  const int n = (int)g->ctx.size();
+  std::vector<int64_t> b(4 * (size_t)n);
+  int used = 0;
+  std::string why;
+  if (group_plan_impl(img, prm, n, b.data(), &used, &why) != CUBERILLE_OK) return gfail(g, CUBERILLE_ERR_ARGUMENT, why);
+  for (int i = 0; i < n; i++) {
+    const cuberille_ctx *c = g->ctx[(size_t)i];
+    if (c->interp == CUBERILLE_INTERP_BSPLINE)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has the B-spline interpolator set: its "
+                                              "prefilter needs whole lines of the volume, not offered in a group");
+    if (c->holdGradient)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " holds a gradient (cuberille_hold_gradient): "
+                                              "it belongs to a whole volume, not offered in a group");
+  }
+  {
+    const int rc = validate(g->ctx[0], img, host_voxels, prm);
+    if (rc) return gfail(g, rc, g->ctx[0]->err);
+  }
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+  const int share = std::max(1, pool_threads_default() / used);   // the staging threads of ONE context, split
+  const bool q1 = prm->emulate_empty_slice_aliasing != 0;
+
+  // 1. upload and count, every slab at once; a slab that no other can change starts its vertex phase right away
+  std::vector<SlabStatus> st((size_t)used);
+  std::vector<uint64_t> np((size_t)used, 0), nc((size_t)used, 0);
+  std::vector<cuberille_slab_status> info((size_t)used);
+  for_each_slab(used, [&](int i) {
+    cuberille_ctx *c = g->ctx[(size_t)i];
+    SlabStatus &s = st[(size_t)i];
+    const int64_t *bi = &b[4 * (size_t)i];
+    c->poolThreads = share;
+    cuberille_image_desc d = *img;
+    d.dims[2] = bi[3] - bi[2];
+    const cuberille_slab slab = {img->dims[2], bi[2], bi[0], bi[1], 0, 0, nullptr, nullptr};
+    const size_t bytes = sliceBytes * (size_t)d.dims[2], base = sliceBytes * (size_t)bi[2];
+    if (drillSlab == i || (drillSlab == -1 && drillAt >= 0)) g_fail_alloc_countdown = drillAt;
+    int rc = CUBERILLE_OK;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = c->voxOwn.reserve(bytes);
+    if (e != hipSuccess) {
+      rc = fail(c, CUBERILLE_ERR_HIP, std::string("device copy of the slab: ") + hipGetErrorString(e));
+      s.set(rc, "upload", c);
+    } else if (upload_in_chunks(sliceBytes, bytes)) {
+      rc = validate(c, &d, host_voxels, prm);
+      if (!rc) rc = count_host_chunked(c, &d, host_voxels, base, prm, &slab);
+      if (!rc) { np[(size_t)i] = c->res.n_points; nc[(size_t)i] = c->res.n_cells; }
+      if (rc) s.set(rc, "chunked upload and count", c);
+    } else {
+      e = hipMemcpyAsync(c->voxOwn.p, (const char *)host_voxels + base, bytes, hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) {
+        rc = fail(c, CUBERILLE_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+        s.set(rc, "upload", c);
+      } else if ((rc = cuberille_count(c, &d, c->voxOwn.p, prm, &slab, &np[(size_t)i], &nc[(size_t)i])) != CUBERILLE_OK) {
+        s.set(rc, "cuberille_count", c);
+      }
+    }
+    g_fail_alloc_countdown = -1;
+    if (rc) return;
+    info[(size_t)i].alias_z = -1;
+    if (q1 && (rc = cuberille_slab_info(c, &info[(size_t)i])) != CUBERILLE_OK) { s.set(rc, "cuberille_slab_info", c); return; }
+    if (info[(size_t)i].alias_z < 0 && (rc = cuberille_emit_points(c)) != CUBERILLE_OK) s.set(rc, "cuberille_emit_points", c);
+  });
+  if (const int rc = group_failure(g, st)) return rc;
+
+  // 2. quirk Q1 across the cuts (distributed.alias_plan): the consumer counts again with the source slice's bits at hand
+  std::vector<AliasEntry> plan;
+  if (q1)
+    for (int r = 1; r < used; r++) {
+      const int64_t az = info[(size_t)r].alias_z;
+      if (az < 0) continue;
+      int src = -1;
+      int64_t zp = -1;
+      for (int s = 0; s < r; s++) {
+        const int64_t h = info[(size_t)s].highest_occupied_z < az ? info[(size_t)s].highest_occupied_z
+                                                                   : info[(size_t)s].second_highest_occupied_z;
+        if (h >= 0 && h < az && h > zp) { src = s; zp = h; }
+      }
+      if (src >= 0) plan.push_back({r, src, zp, az >= b[4 * (size_t)r]});   // (az below own_z0: the ghost slice, bits only)
+    }
+  for (const AliasEntry &a : plan) {
+    cuberille_ctx *sc = g->ctx[(size_t)a.source], *cc = g->ctx[(size_t)a.consumer];
+    std::vector<SlabStatus> st2((size_t)used);
+    const uint64_t *dw = nullptr;
+    size_t nw = 0;
+    int rc = cuberille_slice_bits_device(sc, a.zp, &dw, &nw);
+    if (rc) { st2[(size_t)a.source].set(rc, "cuberille_slice_bits_device", sc); return group_failure(g, st2); }
+    std::vector<uint64_t> words(nw);
+    hipError_t e = hipSetDevice(sc->device);
+    if (e == hipSuccess) e = hipMemcpyAsync(words.data(), dw, nw * sizeof(uint64_t), hipMemcpyDeviceToHost, sc->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(sc->stream);
+    if (e != hipSuccess) {
+      st2[(size_t)a.source].set(fail(sc, CUBERILLE_ERR_HIP, hipGetErrorString(e)), "quirk-Q1 source bits to the host", sc);
+      return group_failure(g, st2);
+    }
+    DevBuf dev;
+    e = hipSetDevice(cc->device);
+    if (e == hipSuccess) e = dev.reserve(nw * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemcpyAsync(dev.p, words.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice, cc->stream);
+    if (e != hipSuccess) st2[(size_t)a.consumer].set(fail(cc, CUBERILLE_ERR_HIP, hipGetErrorString(e)), "quirk-Q1 source bits to the consumer", cc);
+    else if ((rc = cuberille_recount(cc, dev.p, &np[(size_t)a.consumer], &nc[(size_t)a.consumer])) != CUBERILLE_OK)
+      st2[(size_t)a.consumer].set(rc, "cuberille_recount", cc);
+    dev.release();                           // (the recount has waited for its stream)
+    if (const int rc2 = group_failure(g, st2)) return rc2;
+  }
+  std::vector<u64> poff((size_t)used + 1, 0);
+  for (int i = 0; i < used; i++) poff[(size_t)i + 1] = poff[(size_t)i] + np[(size_t)i];
+
+  // 3. emit: the slabs of a hand-over in rank order (the source's plane after its emit, before the consumer's), the rest at once
+  std::vector<char> inChain((size_t)used, 0);
+  for (const AliasEntry &a : plan)
+    if (a.plane) inChain[(size_t)a.consumer] = inChain[(size_t)a.source] = 1;
+  const size_t corners = (size_t)(img->dims[0] + 1) * (size_t)(img->dims[1] + 1);
+  std::vector<std::vector<uint64_t>> planeIds(plan.size());
+  std::vector<std::vector<float>> planePts(plan.size());
+  std::vector<SlabStatus> est((size_t)used);
+  std::vector<cuberille_result> sres((size_t)used);
+  auto emitOne = [&](int i) {
+    cuberille_ctx *c = g->ctx[(size_t)i];
+    SlabStatus &s = est[(size_t)i];
+    DevBuf ids, pts;
+    if (hipSetDevice(c->device) != hipSuccess) { s.set(fail(c, CUBERILLE_ERR_HIP, "hipSetDevice"), "cuberille_emit", c); return false; }
+    for (size_t k = 0; k < plan.size(); k++) {
+      if (!plan[k].plane || plan[k].consumer != i) continue;
+      hipError_t e = hipSetDevice(c->device);
+      if (e == hipSuccess) e = ids.reserve(corners * sizeof(uint64_t));
+      if (e == hipSuccess) e = pts.reserve(corners * 3 * sizeof(float));
+      if (e == hipSuccess) e = hipMemcpyAsync(ids.p, planeIds[k].data(), corners * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(pts.p, planePts[k].data(), corners * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) { s.set(fail(c, CUBERILLE_ERR_HIP, hipGetErrorString(e)), "quirk-Q1 plane to the consumer", c); return false; }
+      const int rc = cuberille_set_alias_plane(c, (const uint64_t *)ids.p, (const float *)pts.p);
+      if (rc) { s.set(rc, "cuberille_set_alias_plane", c); return false; }
+    }
+    int rc = cuberille_emit(c, poff[(size_t)i], &sres[(size_t)i]);
+    ids.release();
+    pts.release();
+    if (rc) { s.set(rc, "cuberille_emit", c); return false; }
+    for (size_t k = 0; k < plan.size(); k++) {
+      if (!plan[k].plane || plan[k].source != i) continue;
+      planeIds[k].resize(corners);
+      planePts[k].resize(corners * 3);
+      hipError_t e = hipSetDevice(c->device);
+      if (e == hipSuccess) e = ids.reserve(corners * sizeof(uint64_t));
+      if (e == hipSuccess) e = pts.reserve(corners * 3 * sizeof(float));
+      if (e != hipSuccess) { s.set(fail(c, CUBERILLE_ERR_HIP, hipGetErrorString(e)), "quirk-Q1 plane of the source", c); return false; }
+      if ((rc = cuberille_alias_plane_device(c, plan[k].zp, (uint64_t *)ids.p, (float *)pts.p)) != CUBERILLE_OK) {
+        s.set(rc, "cuberille_alias_plane_device", c);
+        return false;
+      }
+      e = hipMemcpyAsync(planeIds[k].data(), ids.p, corners * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(planePts[k].data(), pts.p, corners * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) { s.set(fail(c, CUBERILLE_ERR_HIP, hipGetErrorString(e)), "quirk-Q1 plane to the host", c); return false; }
+    }
+    return true;
+  };
+  std::vector<int> lanes;                    // -1: the hand-over chain, in rank order, on one thread
+  if (std::find(inChain.begin(), inChain.end(), 1) != inChain.end()) lanes.push_back(-1);
+  for (int i = 0; i < used; i++) if (!inChain[(size_t)i]) lanes.push_back(i);
+  for_each_slab((int)lanes.size(), [&](int l) {
+    if (lanes[(size_t)l] >= 0) { (void)emitOne(lanes[(size_t)l]); return; }
+    for (int i = 0; i < used; i++)
+      if (inChain[(size_t)i] && !emitOne(i)) return;   // (a failed link ends the chain: the later ones need its plane)
+  });
+  if (const int rc = group_failure(g, est)) return rc;
+
+  // 4. one result: counts and walk statistics summed, device times the largest of the slabs
+  cuberille_result r{};
+  r.verts_per_cell = prm->generate_triangles ? 3 : 4;
+  g->pointOff.assign((size_t)used, 0);
+  g->cellOff.assign((size_t)used, 0);
+  for (int i = 0; i < used; i++) {
+    const cuberille_result &s = sres[(size_t)i];
+    g->pointOff[(size_t)i] = r.n_points;
+    g->cellOff[(size_t)i] = r.n_cells;
+    r.n_points += s.n_points; r.n_cells += s.n_cells;
+    r.proj_iterations += s.proj_iterations; r.proj_stop_threshold += s.proj_stop_threshold;
+    r.proj_stop_steps += s.proj_stop_steps; r.n_escaped += s.n_escaped;
+    float *dst[] = {&r.ms_classify, &r.ms_count, &r.ms_scan, &r.ms_emit_points, &r.ms_project, &r.ms_emit_cells, &r.ms_total, &r.ms_pass};
+    const float src[] = {s.ms_classify, s.ms_count, s.ms_scan, s.ms_emit_points, s.ms_project, s.ms_emit_cells, s.ms_total, s.ms_pass};
+    for (int k = 0; k < 8; k++) *dst[k] = std::max(*dst[k], src[k]);
+  }
+  g->slabRes = sres;
+  g->used = used;
+  g->res = r;
+  g->haveMesh = true;
+  g->err.clear();
+  if (res) *res = r;
+  return CUBERILLE_OK;
+}
+
+int cuberille_group_slab_result(const cuberille_group *g, int i, cuberille_result *res) {
+  if (!g || !res) return CUBERILLE_ERR_ARGUMENT;
+  if (!g->haveMesh) return CUBERILLE_ERR_STATE;
+  if (i < 0 || i >= g->used) return CUBERILLE_ERR_ARGUMENT;
+  *res = g->slabRes[(size_t)i];
+  return CUBERILLE_OK;
+}
+
+int cuberille_group_mesh_host(cuberille_group *g, float **points, uint64_t **cells) {
+  if (!g) return CUBERILLE_ERR_ARGUMENT;
+  if (!g->haveMesh) return gfail(g, CUBERILLE_ERR_STATE, "no mesh: call cuberille_group_extract_host first");
+  if (!g->hostMeshValid) {
+    const cuberille_result &r = g->res;
+    const size_t pb = (size_t)r.n_points * 3 * sizeof(float), cb = (size_t)r.n_cells * r.verts_per_cell * sizeof(uint64_t);
+    if (!g->hostPoints.reserve(pb ? pb : 1) || !g->hostCells.reserve(cb ? cb : 1))
+      return gfail(g, CUBERILLE_ERR_HIP, "cuberille_group_mesh_host: out of host memory");
+    // every slab's part into its own range, at once; the staging threads of one context split between them
+    std::vector<SlabStatus> st((size_t)g->used);
+    const int share = std::max(1, pool_threads_default() / g->used);
+    for_each_slab(g->used, [&](int i) {
+      cuberille_ctx *c = g->ctx[(size_t)i];
+      c->poolThreads = share;
+      const int rc = cuberille_mesh_download(c, (float *)g->hostPoints.p + 3 * g->pointOff[(size_t)i],
+                                             (uint64_t *)g->hostCells.p + (size_t)r.verts_per_cell * g->cellOff[(size_t)i]);
+      if (rc) st[(size_t)i].set(rc, "cuberille_mesh_download", c);
+    });
+    if (const int rc = group_failure(g, st)) return rc;
+    g->hostMeshValid = true;
+  }
+  if (points) *points = (float *)g->hostPoints.p;
+  if (cells) *cells = (uint64_t *)g->hostCells.p;
+  return CUBERILLE_OK;
+}
+
+int cuberille_group_release_host_mesh(cuberille_group *g) {
+  if (!g) return CUBERILLE_ERR_ARGUMENT;
+  g->hostPoints.release();
+  g->hostCells.release();
+  g->hostMeshValid = false;
+  return CUBERILLE_OK;
+}
+
+int cuberille_group_mesh_write_vtk(cuberille_group *g, const char *path, int n_threads) {
+  if (!g || !path) return CUBERILLE_ERR_ARGUMENT;
+  float *pts = nullptr;
+  uint64_t *cells = nullptr;
+  const int rc = cuberille_group_mesh_host(g, &pts, &cells);
+  if (rc) return rc;
+  const cuberille_result &r = g->res;
+  const int wr = cuberille_write_vtk_buffers(path, pts, r.n_points, cells, r.n_cells, r.verts_per_cell, n_threads);
+  if (wr != CUBERILLE_OK) return gfail(g, wr, std::string("cannot write ") + path);
   return CUBERILLE_OK;
 }
 

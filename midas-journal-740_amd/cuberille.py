@@ -453,6 +453,111 @@ def minimum_halo(desc, params):
     return int(lo.value), int(hi.value)
 
 
+def group_plan(desc, params, n):
+    """The cuts a group of n contexts makes of this image for these parameters (cuberille_group_plan, needs no GPU):
+    [(own_z0, own_z1, buf_z0, buf_z1)] for the min(n, Nz) slabs that take part."""
+    n = int(n)
+    bounds = (C.c_int64 * (4 * max(n, 1)))()
+    used = C.c_int()
+    rc = _abi.lib().cuberille_group_plan(C.byref(desc), C.byref(params), n, bounds, C.byref(used))
+    if rc != _abi.OK:
+        raise _abi.CuberilleError(rc, "cuberille_group_plan: %d members, or these parameters, are not offered" % n)
+    return [tuple(int(v) for v in bounds[4 * i:4 * i + 4]) for i in range(used.value)]
+
+
+class ExtractorGroup:
+    """Several contexts driven together (include/cuberille_hip.h: cuberille_group): a host-resident volume is cut into
+    z-slabs of equal thickness, each uploaded with its full halo straight from host memory to its member's device, and
+    one mesh comes back -- the same ids, cell order and bits as Extractor.extract_host of the whole volume.  devices: one
+    device id per member; ids may repeat (several contexts on one GPU)."""
+
+    def __init__(self, devices):
+        self._lib = _abi.lib()
+        self._g = C.c_void_p()
+        ids = [int(d) for d in devices]
+        arr = (C.c_int * max(len(ids), 1))(*ids)
+        rc = self._lib.cuberille_group_create(C.byref(self._g), arr, len(ids))
+        if rc != _abi.OK:
+            text = self._lib.cuberille_group_last_error(None)
+            self._g = C.c_void_p()
+            raise _abi.CuberilleError(rc, text.decode() if text else "")
+        self.devices = ids
+        self.result = None
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            self._lib.cuberille_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def plan(self, desc, params):
+        """[(own_z0, own_z1, buf_z0, buf_z1)] per slab this group would cut for desc (needs no GPU)."""
+        return group_plan(desc, params, len(self.devices))
+
+    def warm_up(self, desc=None, params=None):
+        """cuberille_group_warm_up: every member loads its code objects and, with an image description, reserves the
+        workspace of its slab."""
+        _abi.check_group(self._g, self._lib.cuberille_group_warm_up(self._g, C.byref(desc) if desc is not None else None,
+                                                                    C.byref(params) if params is not None else None))
+
+    def context(self, i):
+        """The raw cuberille_ctx pointer of member i (for cuberille_debug_set_option and the like)."""
+        p = self._lib.cuberille_group_context(self._g, int(i))
+        if not p:
+            raise IndexError("member %d of a group of %d" % (i, len(self.devices)))
+        return C.c_void_p(p)
+
+    def debug_option(self, i, name, value):
+        """Development switch of member i (cuberille_debug_set_option)."""
+        ctx = self.context(i)
+        _abi.check(ctx, self._lib.cuberille_debug_set_option(ctx, name.encode(), int(value)))
+
+    def debug_fail_alloc(self, slab, n):
+        """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
+        (slab -1: every slab's; n < 0: off)."""
+        _abi.check_group(self._g, self._lib.cuberille_group_debug_fail_alloc(self._g, int(slab), int(n)))
+
+    def extract_host(self, vol, params):
+        """vol: mha.Volume in host memory.  Upload + extract on every member; the summed result (device times: the
+        largest of the slabs')."""
+        vox = np.ascontiguousarray(vol.voxels)
+        desc = make_desc(vox.dtype, vol.dims, vol.spacing, vol.origin, vol.direction, getattr(vol, "index_start", (0, 0, 0)))
+        check_iso(int(desc.pixel_type), params)
+        res = _abi.Result()
+        _abi.check_group(self._g, self._lib.cuberille_group_extract_host(
+            self._g, C.byref(desc), C.c_void_p(vox.ctypes.data), C.byref(params), C.byref(res)))
+        self.result = res
+        return res
+
+    def slab_result(self, i):
+        """Slab i's own result of the last extraction."""
+        res = _abi.Result()
+        _abi.check_group(self._g, self._lib.cuberille_group_slab_result(self._g, int(i), C.byref(res)))
+        return res
+
+    def download(self):
+        """The assembled mesh of the last extraction, copied out of the group's host memory."""
+        res = self.result
+        npnt, ncell, vpc = int(res.n_points), int(res.n_cells), int(res.verts_per_cell)
+        pp, cp = C.c_void_p(), C.c_void_p()
+        _abi.check_group(self._g, self._lib.cuberille_group_mesh_host(self._g, C.byref(pp), C.byref(cp)))
+        pts = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_float)), shape=(max(npnt * 3, 1),))[:npnt * 3]
+        cells = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_uint64)), shape=(max(ncell * vpc, 1),))[:ncell * vpc]
+        return Mesh(pts.reshape(npnt, 3).copy(), cells.reshape(ncell, vpc).copy())
+
+    def release_host_mesh(self):
+        _abi.check_group(self._g, self._lib.cuberille_group_release_host_mesh(self._g))
+
+    def write_vtk(self, path, threads=0):
+        """The assembled mesh as legacy-ASCII VTK polydata (cuberille_group_mesh_write_vtk)."""
+        _abi.check_group(self._g, self._lib.cuberille_group_mesh_write_vtk(self._g, os.fsencode(path), int(threads)))
+
+
 def _clamp(v, lo, hi):
     return lo if v < lo else (hi if v > hi else v)
 
@@ -469,8 +574,11 @@ class CuberilleImageToMeshFilter:
     over).  Output: Mesh with the reference's vertex ids, cell order and coordinates.
     """
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, devices=None):
         self._device = device
+        self._devices = [int(d) for d in devices] if devices else []
+        self._group = None
+        self.last_number_of_slabs = 0
         self._extractor = None
         self._input = None
         self._output = None
@@ -514,6 +622,23 @@ class CuberilleImageToMeshFilter:
         self._threshold = _clamp(self._threshold_asked, 0.0, _pixel_max(self._dtype))
         if self._acquire(False) and self._dtype in PIXEL_CODES:
             self._extractor.warm_up(make_desc(self._dtype, image.dims, image.spacing, image.origin, image.direction, image.index_start))
+
+    def SetDevices(self, devices):
+        """Not in the reference (like the C++ drop-in's SetDevices): more than one device id -- ids may repeat -- makes
+        Update() cut the volume into z-slabs, one per member of an ExtractorGroup, where the parameters are ones a slab
+        takes; otherwise (an empty list, the default, or the B-spline interpolator, a reproduced stale gradient or the
+        recursive-Gaussian gradient) it runs on `device` alone."""
+        self._devices = [int(d) for d in devices] if devices else []
+        if self._group is not None and self._group.devices != self._devices:
+            self._group.close()
+            self._group = None
+
+    def GetDevices(self):
+        return list(self._devices)
+
+    def GetLastNumberOfSlabs(self):
+        """Slabs the last Update() was cut into: 1 on the single context."""
+        return self.last_number_of_slabs
 
     # h:180-181
     def SetIsoSurfaceValue(self, v):
@@ -631,6 +756,14 @@ class CuberilleImageToMeshFilter:
             self._step = max(vol.spacing) * 0.25
         prm = make_params(self._iso, self._triangles, self._project, self._threshold, self._step, self._relax,
                           self._max_steps, self._q1, self._variant, self._gradient)
+        if len(self._devices) > 1 and not self._bspline and not self._stale_gradient and \
+                not (self._project and self._gradient == GRADIENT_RECURSIVE_GAUSSIAN):
+            if self._group is None:
+                self._group = ExtractorGroup(self._devices)
+            self.last_result = self._group.extract_host(vol, prm)
+            self._output = self._group.download()
+            self.last_number_of_slabs = len(self._group.plan(self._group_desc(vol), prm))
+            return
         self._extractor.hold_gradient(self._stale_gradient)
         if self._bspline:
             self._extractor.set_interpolator(_abi.INTERP_BSPLINE, 3, *self._bspline)
@@ -638,6 +771,11 @@ class CuberilleImageToMeshFilter:
             self._extractor.set_interpolator(_abi.INTERP_LINEAR)
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
+        self.last_number_of_slabs = 1
+
+    @staticmethod
+    def _group_desc(vol):
+        return make_desc(vol.voxels.dtype, vol.dims, vol.spacing, vol.origin, vol.direction, getattr(vol, "index_start", (0, 0, 0)))
 
     def GetOutput(self):
         return self._output

@@ -39,7 +39,11 @@
 #include "itkVectorLinearInterpolateImageFunction.h"
 #include "itkNumericTraits.h"
 
-struct cuberille_ctx;   // include/cuberille_hip.h
+#include <string>
+#include <vector>
+
+struct cuberille_ctx;     // include/cuberille_hip.h
+struct cuberille_group;
 
 namespace itk
 {
@@ -208,6 +212,18 @@ public:
   itkSetMacro(BSplineOnDevice, bool);
   itkBooleanMacro(BSplineOnDevice);
 
+  /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
+   *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
+   *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
+   *  order and bits as the single context's.  Empty (the default): the single context on GetDevice(), as before.  Update()
+   *  takes the single context all the same for what a slab cannot do: the B-spline walk on the device,
+   *  ReproduceStaleGradient, the recursive-Gaussian gradient.  The environment variable CUBERILLE_DEVICES (say "0,1,2,3"
+   *  or "0,0"), read by the constructor, gives the default, so that an unchanged driver runs split; a malformed value
+   *  makes Update() throw.  GetLastNumberOfSlabs(): the slabs the last Update() was cut into (1: the single context). */
+  void SetDevices(const std::vector<int> &devices);
+  const std::vector<int> &GetDevices() const { return m_Devices; }
+  unsigned int GetLastNumberOfSlabs() const { return m_LastNumberOfSlabs; }
+
 protected:
   CuberilleImageToMeshFilter();
   ~CuberilleImageToMeshFilter();
@@ -241,6 +257,13 @@ private:
   ::cuberille_ctx    *m_Context;
   int m_ContextDevice;                        // the device m_Context lives on (SetDevice may come after the constructor)
   bool AcquireContext(bool mustSucceed);      // create + cuberille_warm_up when there is none (or it sits on another device)
+  std::vector<int> m_Devices;                 // SetDevices / CUBERILLE_DEVICES: more than one = the group route
+  std::string m_DevicesError;                 // a malformed CUBERILLE_DEVICES, thrown by Update()
+  ::cuberille_group *m_Group;
+  std::vector<int> m_GroupDevices;            // the devices m_Group was made for
+  bool m_LastUpdateGrouped;                   // the last Update() ran on m_Group: its buffers are the ones to read
+  unsigned int m_LastNumberOfSlabs;
+  bool AcquireGroup(bool mustSucceed);        // create + cuberille_group_warm_up for m_Devices
 };
 
 } // end namespace itk

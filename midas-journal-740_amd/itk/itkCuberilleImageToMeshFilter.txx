@@ -448,6 +448,24 @@ inline void SplitQuads(const float *points, const uint64_t *quads, uint64_t nQua
     }
 }
 
+// CUBERILLE_DEVICES: device ids separated by commas ("0,1,2,3", "0,0"); false when the text is anything else
+inline bool ParseDeviceList(const char *text, std::vector<int> &out)
+{
+  out.clear();
+  const char *p = text;
+  while (true)
+    {
+    while (*p == ' ') p++;
+    if (*p < '0' || *p > '9') return false;
+    long v = 0;
+    while (*p >= '0' && *p <= '9') { v = v * 10 + (*p++ - '0'); if (v > 4096) return false; }
+    out.push_back(static_cast<int>(v));
+    while (*p == ' ') p++;
+    if (*p == 0) return true;
+    if (*p++ != ',') return false;
+    }
+}
+
 // the one interpolator the kernels implement (I5: linear, double coordinates)
 template <class TInterpolator, class TImage> struct IsGpuInterpolator { enum { Value = 0 }; };
 template <class TImage> struct IsGpuInterpolator<LinearInterpolateImageFunction<TImage, double>, TImage> { enum { Value = 1 }; };
@@ -485,11 +503,25 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_LastDownloadSeconds = 0.0;
   m_Context = 0;
   m_ContextDevice = -1;
+  m_Group = 0;
+  m_LastUpdateGrouped = false;
+  m_LastNumberOfSlabs = 0;
+  // the drop-in's one environment variable (the library reads none): the default of SetDevices
+  if (const char *env = std::getenv("CUBERILLE_DEVICES"))
+    if (*env && !cuberille_detail::ParseDeviceList(env, m_Devices))
+      {
+      m_Devices.clear();
+      m_DevicesError = std::string("CUBERILLE_DEVICES=\"") + env + "\" is not a list of device ids separated by commas (e.g. 0,1,2,3)";
+      }
   // The reference's driver constructs the filter, sets its input and only then starts its clock around ONE Update() in a
   // fresh process (Testing/CuberilleTest01.cxx:144-160): the GPU context, the code objects and the runtime's queues are
   // therefore set up here, not inside that Update().  Without a usable device this is silent: GenerateData() tries
   // again and reports.  (SetEagerDeviceSetup(false): not here, inside the first Update().)
-  if (cuberille_detail::EagerDeviceSetup()) this->AcquireContext(false);
+  if (cuberille_detail::EagerDeviceSetup())
+    {
+    if (m_Devices.size() > 1) this->AcquireGroup(false);
+    else this->AcquireContext(false);
+    }
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
@@ -497,6 +529,39 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::~CuberilleI
 {
   if (m_Context) cuberille_destroy(m_Context);
   m_Context = 0;
+  if (m_Group) cuberille_group_destroy(m_Group);
+  m_Group = 0;
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetDevices(const std::vector<int> &devices)
+{
+  m_Devices = devices;
+  m_DevicesError.clear();                    // (the caller's choice replaces the environment's)
+  this->Modified();
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+bool CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::AcquireGroup(bool mustSucceed)
+{
+  if (m_Group && m_GroupDevices != m_Devices)
+    {
+    cuberille_group_destroy(m_Group);
+    m_Group = 0;
+    m_LastUpdateGrouped = false;
+    }
+  if (!m_Group)
+    {
+    if (cuberille_group_create(&m_Group, &m_Devices[0], static_cast<int>(m_Devices.size())) != CUBERILLE_OK)
+      {
+      m_Group = 0;
+      if (mustSucceed) itkExceptionMacro(<< "cuberille_group_create: " << cuberille_group_last_error(0));
+      return false;
+      }
+    m_GroupDevices = m_Devices;
+    (void)cuberille_group_warm_up(m_Group, 0, 0);
+    }
+  return true;
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
@@ -528,8 +593,15 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetInp
   // an image that is buffered already (the driver reads it first, test:113-117): size the device workspace for it now
   cuberille_image_desc desc;
   if (cuberille_detail::EagerDeviceSetup() && cuberille_detail::PixelCode<InputPixelType>::Value >= 0 &&
-      cuberille_detail::DescribeImage(image, desc) && this->AcquireContext(false))
-    (void)cuberille_warm_up(m_Context, &desc, 0);
+      cuberille_detail::DescribeImage(image, desc))
+    {
+    if (m_Devices.size() > 1)
+      {
+      if (this->AcquireGroup(false)) (void)cuberille_group_warm_up(m_Group, &desc, 0);
+      }
+    else if (this->AcquireContext(false))
+      (void)cuberille_warm_up(m_Context, &desc, 0);
+    }
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
@@ -540,6 +612,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   const unsigned int Dim = InputImageType::ImageDimension;
   if (Dim != 3) itkExceptionMacro(<< "the cuberille path is three-dimensional");
   if (cuberille_detail::PixelCode<InputPixelType>::Value < 0) itkExceptionMacro(<< "unsupported pixel type");
+  if (!m_DevicesError.empty()) itkExceptionMacro(<< m_DevicesError);
   // the B-spline interpolator of order 3 walks on the device where the library offers it (SetBSplineOnDevice); any other
   // TInterpolator than the linear one the kernels implement: topology and lattice points on the GPU, the walk on the host
   // through the user's interpolator (see HostWalk above)
@@ -581,26 +654,51 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "USE_ADVANCED_PROJECTION / USE_LINESEARCH_PROJECTION / USE_GRADIENT_RECURSIVE_GAUSSIAN are only "
                          "offered with the default LinearInterpolateImageFunction");
 
-  this->AcquireContext(true);
-  if (cuberille_hold_gradient(m_Context, (m_ReproduceStaleGradient && !hostWalk) ? 1 : 0) != CUBERILLE_OK)
-    itkExceptionMacro(<< "cuberille_hold_gradient: " << cuberille_last_error(m_Context));
-  if (cuberille_set_interpolator(m_Context, deviceBSpline ? CUBERILLE_INTERP_BSPLINE : CUBERILLE_INTERP_LINEAR, 3,
-                                 deviceBSpline ? bsplineBits : 0, deviceBSpline ? bsplineBits : 0) != CUBERILLE_OK)
-    itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
+  // several devices: the context group, for what a slab takes (the host walk included: its device part does not project)
+  const bool grouped = m_Devices.size() > 1 && !deviceBSpline && !m_ReproduceStaleGradient &&
+                       !(prm.project_vertices && prm.gradient_variant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN);
+  m_LastUpdateGrouped = false;
   cuberille_result res;
-  const double extractStart = cuberille_detail::WallSeconds();
-  if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
-    itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
+  double extractStart;
+  if (grouped)
+    {
+    this->AcquireGroup(true);
+    extractStart = cuberille_detail::WallSeconds();
+    if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_group_extract_host: " << cuberille_group_last_error(m_Group));
+    int used = 1;
+    (void)cuberille_group_plan(&desc, &prm, static_cast<int>(m_Devices.size()), 0, &used);
+    m_LastNumberOfSlabs = static_cast<unsigned int>(used);
+    m_LastUpdateGrouped = true;
+    }
+  else
+    {
+    this->AcquireContext(true);
+    if (cuberille_hold_gradient(m_Context, (m_ReproduceStaleGradient && !hostWalk) ? 1 : 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_hold_gradient: " << cuberille_last_error(m_Context));
+    if (cuberille_set_interpolator(m_Context, deviceBSpline ? CUBERILLE_INTERP_BSPLINE : CUBERILLE_INTERP_LINEAR, 3,
+                                   deviceBSpline ? bsplineBits : 0, deviceBSpline ? bsplineBits : 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
+    extractStart = cuberille_detail::WallSeconds();
+    if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
+    m_LastNumberOfSlabs = 1;
+    }
   m_LastDeviceSeconds = 1e-3 * res.ms_total;
 
   m_LastExtractSeconds = cuberille_detail::WallSeconds() - extractStart;
 
-  // the flat buffers, in host memory the context owns and keeps (cuberille_mesh_host): no allocation of ours, no page
-  // fault per 4 KiB of a fresh destination; valid until the next extraction on the context
+  // the flat buffers, in host memory the context (or the group) owns and keeps (cuberille_mesh_host): no allocation of ours,
+  // no page fault per 4 KiB of a fresh destination; valid until the next extraction
   const double downloadStart = cuberille_detail::WallSeconds();
   float *points = 0;
   uint64_t *cells = 0;
-  if (cuberille_mesh_host(m_Context, &points, &cells) != CUBERILLE_OK)
+  if (grouped)
+    {
+    if (cuberille_group_mesh_host(m_Group, &points, &cells) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_group_mesh_host: " << cuberille_group_last_error(m_Group));
+    }
+  else if (cuberille_mesh_host(m_Context, &points, &cells) != CUBERILLE_OK)
     itkExceptionMacro(<< "cuberille_mesh_host: " << cuberille_last_error(m_Context));
   m_LastDownloadSeconds = cuberille_detail::WallSeconds() - downloadStart;
   struct FreeOnExit { void *p; ~FreeOnExit() { std::free(p); } } ownCells = {0};   // the host walk's triangles, when it makes them
@@ -639,12 +737,22 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   if (res.verts_per_cell == 3) cuberille_detail::FillCells<OutputMeshType, TriangleCellType, 3>(mesh.GetPointer(), cells, res.n_cells, CellFillTag());
   else cuberille_detail::FillCells<OutputMeshType, QuadrilateralCellType, 4>(mesh.GetPointer(), cells, res.n_cells, CellFillTag());
   m_LastMeshFillSeconds = cuberille_detail::WallSeconds() - fillStart;
-  if (m_ReleaseHostMeshAfterFill) (void)cuberille_release_host_mesh(m_Context);
+  if (m_ReleaseHostMeshAfterFill)
+    {
+    if (grouped) (void)cuberille_group_release_host_mesh(m_Group);
+    else (void)cuberille_release_host_mesh(m_Context);
+    }
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
 void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::WriteLastMeshAsVTKPolyData(const char *fileName, int threads)
 {
+  if (m_LastUpdateGrouped)
+    {
+    if (cuberille_group_mesh_write_vtk(m_Group, fileName, threads) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_group_mesh_write_vtk: " << cuberille_group_last_error(m_Group));
+    return;
+    }
   if (!m_Context) itkExceptionMacro(<< "WriteLastMeshAsVTKPolyData: no Update() has run on this filter");
   if (cuberille_mesh_write_vtk(m_Context, fileName, threads) != CUBERILLE_OK)
     itkExceptionMacro(<< "cuberille_mesh_write_vtk: " << cuberille_last_error(m_Context));
