@@ -372,6 +372,29 @@ int cuberille_gradient_held(cuberille_ctx *ctx, int64_t dims[3]);
  * context that never calls this, or sets LINEAR again, gives the same bytes as before this symbol existed. */
 enum { CUBERILLE_INTERP_LINEAR = 0, CUBERILLE_INTERP_BSPLINE = 1 };
 int cuberille_set_interpolator(cuberille_ctx *ctx, int kind, int spline_order, int coordinate_bits, int coefficient_bits);
+/* NEW SYMBOL (added within ABI 13: no struct changes).  Close the surface at the image border without a padded copy.
+ * The reference documents one limitation (h:54-57): no iso-surface pixel may lie on the edge of the image, the caller must pad
+ * it by at least one pixel with itk::ConstantPadImageFilter first -- else the mesh has holes wherever the object touches the
+ * border.  With pad_width 1, every later whole-volume extraction on ctx of an image I (dims N, start index s, origin, spacing,
+ * direction) yields exactly the mesh an extraction with the setting off yields for the image P that filter makes of I: dims
+ * N + 2, start index s - 1, the same origin / spacing / direction, P[p] = I[p - 1] inside and pad_value on the one-voxel
+ * ring -- the same point ids, order, float bits, cells and walk counters.  The ring is implied, never stored: no copy of the
+ * voxels, padded or not, is made on the device (cuberille_extract_device, cuberille_count) or on the host
+ * (cuberille_extract_host, cuberille_extract_stream); the 1-bit volume and the rest of the workspace have the padded size
+ * (cuberille_warm_up reserves that).  A pad value that is itself >= the iso value is legal and gives what P gives.
+ * pad_width: 0 (off, the default: the same bytes as before this symbol existed) or 1; anything else CUBERILLE_ERR_ARGUMENT,
+ *   setting unchanged.  (An argument so that a wider border can come without a new symbol.)
+ * pad_value / pad_value_int: convert to the pixel type by the rule of iso_value / iso_value_int, checked at the extraction,
+ *   where the pixel type is known (out of range or NaN for an integer type: CUBERILLE_ERR_ARGUMENT).  The limits on dims and
+ *   index_start then hold for N + 2 and s - 1.
+ * Refused with CUBERILLE_ERR_ARGUMENT and a message, the context left usable -- each of these would need the ring in a second
+ * image or across ranks, and is deliberately not part of this setting: always, a slab that is not the whole volume, the
+ * cuberille_step_* calls and cuberille_group_extract_host with a member that has it set; with project_vertices on, the
+ * B-spline interpolator, a held gradient (cuberille_hold_gradient), CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN and the ADVANCED and
+ * LINESEARCH projection branches.
+ * While the setting is on, cuberille_debug_bits speaks the padded frame (rows of N0 + 2 voxels, N1 + 2 rows, N2 + 2 slices);
+ * so does cuberille_slice_occupancy (N2 + 2 slices, the ring's first); so does cuberille_slice_counts (N2 + 2 entries). */
+int cuberille_set_border(cuberille_ctx *ctx, int pad_width, double pad_value, int64_t pad_value_int);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

@@ -111,6 +111,9 @@ struct cuberille_ctx {
   int interp = CUBERILLE_INTERP_LINEAR;  // cuberille_set_interpolator: the value interpolator of later walks ...
   int bsBits = 0;                        // ... and, for the B-spline, its coordinate / coefficient width (32 or 64)
   DevBuf bsCoef, bsScratch;              // the B-spline coefficient image, and the double scratch of its passes (32-bit only)
+  int padWidth = 0;                      // cuberille_set_border: voxels of constant border implied around every later whole volume
+  double padValue = 0.0;                 // ... and their value, which travels like the iso value
+  long long padValueInt = 0;
   int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
@@ -264,7 +267,42 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
   }
   if (hi != lo && !(prm->iso_value > lo - 1.0 && prm->iso_value < hi + 1.0))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
+  if (c->padWidth) {
+    // cuberille_set_border: the limits above hold for the image with its ring, the ring's value converts like the iso value, and
+    // what would need the ring in a second image (coefficients, a gradient image) is not offered
+    for (int i = 0; i < 3; i++) {
+      if (img->dims[i] + 2 * c->padWidth > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_LIMIT, "image dimension with its border exceeds 2^31-1");
+      if (img->index_start[i] - c->padWidth < -(1LL << 30))
+        return fail(c, CUBERILLE_ERR_LIMIT, "the bordered region's start index must lie within +-2^30");
+    }
+    if (hi != lo && !(c->padValue > lo - 1.0 && c->padValue < hi + 1.0))
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "the border value (cuberille_set_border) is not representable in the pixel type");
+    if (prm->project_vertices) {
+      if (c->interp == CUBERILLE_INTERP_BSPLINE)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is not offered with the B-spline interpolator: its coefficient image would need the ring");
+      if (c->holdGradient)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
+      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would need the ring");
+      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is offered with the default projection branch only (txx:439-474)");
+    }
+  }
   return CUBERILLE_OK;
+}
+
+// cuberille_set_border: the description of the image with its ring of c->padWidth constant voxels -- what the reference is
+// given after itk::ConstantPadImageFilter: the region grown by the pad on every side, its start index moved down by it, the
+// same origin, spacing and direction -- or the caller's own with the setting off.  The one place the two frames meet: the
+// layout, the geometry and every workspace size follow from this description, the sweep and the walk alone read the
+// caller's buffer (Workspace::pad).
+cuberille_image_desc bordered(const cuberille_ctx *c, const cuberille_image_desc *img) {
+  cuberille_image_desc d = *img;
+  for (int i = 0; i < 3; i++) {
+    d.dims[i] += 2 * c->padWidth;
+    d.index_start[i] -= c->padWidth;
+  }
+  return d;
 }
 
 }  // namespace
@@ -489,7 +527,8 @@ struct CountSizes {
   size_t flatBits, vqueue;                                 // optional
 };
 
-CountSizes count_sizes(const Grid &g, const Tuning &t) {
+// bordered (cuberille_set_border): neither padded sweep goes through the flat scratch stream
+CountSizes count_sizes(const Grid &g, const Tuning &t, bool bordered) {
   const size_t slice = (size_t)g.ny * g.W, nwords = (size_t)(g.oz1 - g.cz0) * slice, nblk = (nwords + COUNT_WB - 1) / COUNT_WB;
   CountSizes s;
   s.nwords = nwords; s.nseg = (nwords + 63) / 64;
@@ -499,7 +538,7 @@ CountSizes count_sizes(const Grid &g, const Tuning &t) {
   s.segPre = s.nseg * sizeof(u64);
   s.blockTot = (nblk + 2 * (nblk / 8192 + 1)) * sizeof(u64);   // (+ the sums of its chunks of 8192: k_block_partial)
   s.blockBase = nblk * 2 * sizeof(u64);
-  s.flatBits = g.nx % 64 != 0 ? (slice * g.nzb + 32) * sizeof(u64) : 0;   // ragged rows: one flat stream, then rows
+  s.flatBits = g.nx % 64 != 0 && !bordered ? (slice * g.nzb + 32) * sizeof(u64) : 0;   // ragged rows: one flat stream, then rows
   s.vqueue = nwords < 0xffffffffULL && !t.no_vqueue ? nwords * sizeof(u32) : 0;
   return s;
 }
@@ -560,11 +599,14 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
-  Grid g = whole_grid(img, c->tune);
+  const cuberille_image_desc framed = bordered(c, img);
+  Grid g = whole_grid(&framed, c->tune);
   Geo geo{};
   Params p{};
-  resolve(img, prm, geo, p);
+  resolve(&framed, prm, geo, p);
   const bool whole = !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);   // (all-zero slab = whole volume)
+  if (!whole && c->padWidth)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
   if (!whole) {
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
@@ -598,7 +640,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     g.oz1 = (int)(slab->own_z1 - slab->z_begin);
   }
   g.cz0 = g.oz0 > 0 ? g.oz0 - 1 : 0;
-  const CountSizes sz = count_sizes(g, c->tune);
+  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0);
   if (sz.nseg > 0x7fffffffULL) return fail(c, CUBERILLE_ERR_LIMIT, "volume too large for one device scan");
 
   // ---- workspace ----------------------------------------------------------------------------------
@@ -619,6 +661,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   w.flatBits = (u64 *)optional(c->flatBits, sz.flatBits);
   w.vqueue = (u32 *)optional(c->vqueue, sz.vqueue);
   w.vox = dev_voxels;
+  w.pad = c->padWidth; w.padValue = c->padValue; w.padValueInt = c->padValueInt;
   w.bits = (u64 *)c->bits.p; w.sliceOcc = (u32 *)((char *)c->occ.p + sizeof(Totals));
   w.prefix = (u32 *)c->prefix.p;
   w.segPre = (u64 *)c->segPre.p; w.blockTot = (u64 *)c->blockTot.p; w.blockBase = (u64 *)c->blockBase.p;
@@ -786,7 +829,8 @@ int classify_slab(cuberille_ctx *c, const cuberille_image_desc *img, const cuber
     HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, 0, g.oz0, c->tune, s));
     HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, g.oz1, g.nzb, c->tune, s));
   } else {
-    HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, 0, g.nzb, c->tune, s));
+    // (with a border the grid is two slices taller than the buffer the sweep reads)
+    HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, 0, g.nzb - 2 * c->w.pad, c->tune, s));
   }
   return CUBERILLE_OK;
 }
@@ -1082,6 +1126,8 @@ int cuberille_reproject_escaped(cuberille_ctx *c, const void *dev_voxels, int64_
   if (!c || !dev_voxels) return CUBERILLE_ERR_ARGUMENT;
   if (!c->counted || !c->pointsEmitted || !c->thinHalo)
     return fail(c, CUBERILLE_ERR_STATE, "cuberille_reproject_escaped follows cuberille_emit_points on a THIN_HALO slab");
+  if (c->w.pad)   // (cannot happen: a slab count refuses the border -- said here so that it never becomes a bare launch error)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
   if (c->tot.err & ERRF_ESCAPE_OVERFLOW)
     return fail(c, CUBERILLE_ERR_LIMIT, "more walks left the thin halo than the escape list holds: count the slab again with "
                                         "the full halo (cuberille_required_halo)");
@@ -1205,13 +1251,11 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
   return CUBERILLE_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-// ---- one step without a host round trip between count and emit (the multi-GPU steady state) -------------------------
-int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
-                         const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
+// cuberille_step_begin, and the first half of cuberille_extract_device (the one-wait step with the context as its only rank:
+// a whole volume, so an implied border is at home there while the steps of a driver's ranks refuse it)
+const char *const kNoBorderInSteps = "an implied border (cuberille_set_border) would have to reach across ranks: not offered with the cuberille_step_* calls";
+int step_begin_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
+                    const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
   int rc = validate(c, img, dev_voxels, prm);
   if (rc) return rc;
   if (!dev_row || !row_bytes) return fail(c, CUBERILLE_ERR_ARGUMENT, "null row pointer");
@@ -1222,8 +1266,20 @@ int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, cons
   return step_launch(c, dev_row, row_bytes);
 }
 
+}  // namespace
+
+extern "C" {
+
+// ---- one step without a host round trip between count and emit (the multi-GPU steady state) -------------------------
+int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
+                         const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
+  if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
+  return step_begin_impl(c, img, dev_voxels, prm, slab, dev_row, row_bytes);
+}
+
 int cuberille_step_classify(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                             const cuberille_slab *slab, uint64_t **dev_bits, size_t *words_per_slice) {
+  if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
   int rc = validate(c, img, dev_voxels, prm);
   if (rc) return rc;
   if (!dev_bits || !words_per_slice) return fail(c, CUBERILLE_ERR_ARGUMENT, "null bit-plane pointer");
@@ -1348,7 +1404,7 @@ int cuberille_extract_device(cuberille_ctx *c, const cuberille_image_desc *img, 
     explicit OneCall(cuberille_ctx *ctx) : c(ctx) { c->oneCall = true; }
     ~OneCall() { c->oneCall = false; }
   } guard(c);
-  int rc = cuberille_step_begin(c, img, dev_voxels, prm, slab, &row, &rowBytes);
+  int rc = step_begin_impl(c, img, dev_voxels, prm, slab, &row, &rowBytes);
   if (rc) return rc;
   rc = step_end_impl(c, row, 1, 0, slab ? slab->point_id_offset : 0, res);
   if (rc != CUBERILLE_RETRY) return rc;
@@ -1582,9 +1638,16 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
   if (live) return CUBERILLE_OK;
   // the buffers whose size follows from the description (count_prepare, emit_points_phase, cuberille_extract_host); a
   // reservation that fails here is asked for again, and reported, by the extraction
-  const Grid g = whole_grid(img, c->tune);
-  const CountSizes sz = count_sizes(g, c->tune);
-  const size_t bytes = (size_t)g.nx * g.ny * g.nzb * pixel_size(img->pixel_type);
+  // (cuberille_set_border: the workspace of the image with its ring, the voxel buffer of the image as it is)
+  const cuberille_image_desc framed = bordered(c, img);
+  for (int i = 0; i < 3; i++) {     // (the limits of validate() for the image with its ring)
+    if (framed.dims[i] > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_LIMIT, "image dimension with its border exceeds 2^31-1");
+    if (c->padWidth && framed.index_start[i] < -(1LL << 30))
+      return fail(c, CUBERILLE_ERR_LIMIT, "the bordered region's start index must lie within +-2^30");
+  }
+  const Grid g = whole_grid(&framed, c->tune);
+  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0);
+  const size_t bytes = (size_t)img->dims[0] * (size_t)img->dims[1] * (size_t)img->dims[2] * pixel_size(img->pixel_type);
   const std::pair<DevBuf *, size_t> want[] = {{&c->voxOwn, bytes}, {&c->bits, sz.bits}, {&c->occ, sz.occ}, {&c->prefix, sz.prefix},
                                               {&c->segPre, sz.segPre}, {&c->blockTot, sz.blockTot}, {&c->blockBase, sz.blockBase},
                                               {&c->flatBits, sz.flatBits}, {&c->vqueue, sz.vqueue}, {&c->cmap, cmap_bytes(g, c->tune)}};
@@ -1806,6 +1869,16 @@ int cuberille_set_interpolator(cuberille_ctx *c, int kind, int spline_order, int
     return fail(c, CUBERILLE_ERR_ARGUMENT, "the device B-spline walk implements <float, float> (32, 32) and <double, double> (64, 64)");
   c->interp = CUBERILLE_INTERP_BSPLINE;
   c->bsBits = coordinate_bits;
+  return CUBERILLE_OK;
+}
+
+int cuberille_set_border(cuberille_ctx *c, int pad_width, double pad_value, int64_t pad_value_int) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  if (pad_width != 0 && pad_width != 1) return fail(c, CUBERILLE_ERR_ARGUMENT, "the implied border is 0 (off) or 1 voxel wide");
+  c->padWidth = pad_width;
+  c->padValue = pad_value;
+  c->padValueInt = (long long)pad_value_int;
   return CUBERILLE_OK;
 }
 
@@ -2070,6 +2143,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
   if (group_plan_impl(img, prm, n, b.data(), &used, &why) != CUBERILLE_OK) return gfail(g, CUBERILLE_ERR_ARGUMENT, why);
   for (int i = 0; i < n; i++) {
     const cuberille_ctx *c = g->ctx[(size_t)i];
+    if (c->padWidth)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has an implied border set (cuberille_set_border): "
+                                              "the ring would have to reach across slabs, not offered in a group");
     if (c->interp == CUBERILLE_INTERP_BSPLINE)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has the B-spline interpolator set: its "
                                               "prefilter needs whole lines of the volume, not offered in a group");

@@ -137,13 +137,20 @@ struct Workspace {     // device pointers valid for one count/emit pair
   u32 *escList;        // THIN_HALO: indices (in this rank's point buffer) of the vertices whose walk left the buffer
   u32 escCap;
   const HeldGradient *held;   // (host pointer) the held gradient image the walk follows instead of the volume's own, or null
+  // cuberille_set_border: 1 = the Grid (and the Geo) describe the image with a ring of one constant voxel around it while `vox`
+  // is the caller's buffer, two voxels smaller along every axis -- read by the sweep and the walk only, every other kernel works
+  // on the bit volume; the ring's value travels like the iso value (a double, and an integer for the 64-bit integer types)
+  int pad;
+  double padValue;
+  long long padValueInt;
 };
 
 // Development switches, set per context through cuberille_debug_set_option (never read from the environment).
 // The defaults are the measured best; the parity tests flip the fallbacks on to cover them.
 struct Tuning {
   int no_cmap = 0, no_heads = 0, no_vqueue = 0, no_stream_classify = 0;   // drop a scratch table / the flat-stream path
-  int classify_variant = 0;   // 0: staged spans with write-through stores where the volume is large, 1: always the plain sweep
+  int classify_variant = 0;   // 0: staged spans with write-through stores where the volume is large, 1: always the plain sweep,
+                              // 2: the padded sweep (cuberille_set_border) through its staged spans whatever the size (tests)
   int classify_grid = 0;      // workgroups of the sweep (0 = default)
   int classify_keep_tail = 0; // 1: a partly filled last round of spans stays with the span kernel (A/B of the balancing)
   int proj_chunk64_below = 0; // vertices under which the walk deals batches of 64 (0: the default, 8 M)
@@ -199,6 +206,7 @@ struct Gate {
 
 // launchers (cuberille_kernels.hip); all asynchronous on `s`.  dyn: the launch is sized for an estimate, the kernel
 // reads the real sizes from the device totals and runs only when Totals::go says so.
+// (z0, z1: slices of `vox` -- with Workspace::pad the caller's, the range that holds its first / last slice writes the ring's too)
 hipError_t launch_classify(int pixel_type, const Workspace &w, const Grid &g, const Params &p, int z0, int z1, const Tuning &t,
                            hipStream_t s);
 hipError_t launch_occupancy(int pixel_type, const Workspace &w, const Grid &g, const Tuning &t, hipStream_t s);

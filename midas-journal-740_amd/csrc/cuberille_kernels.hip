@@ -416,6 +416,164 @@ __global__ __launch_bounds__(256) void k_classify_rows(const T *__restrict__ vox
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The padded sweep (cuberille_set_border): the bit volume of the caller's nx x ny x nz image with a ring of one constant
+// voxel around it, in the layout every later kernel expects of an (nx+2) x (ny+2) x (nz+2) image -- rows of W =
+// (nx+2+63)/64 words, bit 0 and bit nx+1 of every row, rows 0 and ny+1 and slices 0 and nz+1 hold inside(ring value),
+// tail bits 0 -- from the caller's buffer as it is: no padded copy of the voxels exists anywhere.
+// ---------------------------------------------------------------------------------------------
+
+// how many rows of the caller's buffer lie below padded row `prow` (row = slice * rows-per-slice + y, in either frame)
+__device__ __forceinline__ u32 pad_rows_below(u32 prow, u32 ny, u32 nz) {
+  const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
+  const u32 full = pz == 0u ? 0u : (pz - 1u < nz ? pz - 1u : nz);
+  const u32 part = (pz >= 1u && pz <= nz) ? (py == 0u ? 0u : (py - 1u < ny ? py - 1u : ny)) : 0u;
+  return full * ny + part;
+}
+__device__ __forceinline__ bool pad_row_is_real(u32 prow, u32 ny, u32 nz) {
+  const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
+  return pz >= 1u && pz <= nz && py >= 1u && py <= ny;
+}
+
+// Any size, any alignment: one wave per output word; lane l tests padded voxel x = 64k + l, the ballot is the word.
+// Words [t0, t1) of the padded bit volume; nx, ny, nz: the caller's dims.
+template <class T>
+__global__ __launch_bounds__(256) void k_classify_pad_words(const T *__restrict__ vox, u64 *__restrict__ bits, u64 t0, u64 t1,
+                                                            int nx, int ny, int nz, int W, double isoD, long long isoI,
+                                                            double padD, long long padI, u32 *__restrict__ sliceOcc) {
+  const T iso = iso_as<T>(isoD, isoI);
+  const bool ringIn = !(iso_as<T>(padD, padI) < iso);
+  const int lane = threadIdx.x & 63;
+  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+  for (u64 t = t0 + wave; t < t1; t += nwaves) {
+    const u64 prow = t / (u64)W;
+    const int k = (int)(t - prow * (u64)W);
+    const u64 pz = prow / (u64)(ny + 2);
+    const int py = (int)(prow - pz * (u64)(ny + 2));
+    const int x = k * 64 + lane;
+    bool in = false;
+    if (x <= nx + 1) {
+      const bool ring = x == 0 || x == nx + 1 || py == 0 || py == ny + 1 || pz == 0 || pz == (u64)nz + 1;
+      in = ring ? ringIn : !(vox[((pz - 1) * (u64)ny + (u64)(py - 1)) * (u64)nx + (u64)(x - 1)] < iso);
+    }
+    const u64 word = __ballot(in);
+    if (lane == 0) {
+      bits[t] = word;
+      if (word) sliceOcc[pz] = 1u;             // benign race: all store 1
+    }
+  }
+}
+
+// Large volumes: k_classify_span_rows with the rows one voxel to the right.  A workgroup owns SPAN_WORDS consecutive words
+// of the PADDED bit volume, a range of (padded row, word) pairs; the rows of the caller's buffer among them follow each other
+// in memory, so the voxels behind those words are still one contiguous range: a flat stream of 16-byte vectors into the LDS
+// stage exactly as there, and every thread cuts two words out of it -- from the bit before the word's first voxel on, so
+// that the row's voxel x lands on bit x + 1 (word 0 of a row: from its first voxel, shifted up by one, the ring's bit
+// below) -- with the ring's bit set behind the row's last voxel and nothing behind that.  Words of the ring's rows and
+// slices are a constant.  Every voxel is read once; occupancy folded in as there.
+// prow0: first padded row of the launch's range (bits and the spans start at its first word), nwordsAll: words of the range.
+template <class T>
+__global__ __launch_bounds__(256) void k_classify_pad_span_rows(const T *__restrict__ vox, u64 *__restrict__ bits, u64 nspans,
+                                                                u64 nwordsAll, u32 prow0, int nx, u32 ny, u32 nz, int W,
+                                                                double isoD, long long isoI, double padD, long long padI,
+                                                                u32 *__restrict__ sliceOcc) {
+  constexpr int U = 4;
+  constexpr int VPL = 16 / sizeof(T);
+  constexpr int LPW = 64 / VPL;
+  // (the voxels behind a span are at most one per bit of its words and the one before its first: the stage of
+  //  k_classify_span_rows holds them with the same slack)
+  constexpr int STAGE = SPAN_WORDS + (4 * U + 1) * VPL + 2;
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
+  const T iso = iso_as<T>(isoD, isoI);
+  const u64 ringBit = !(iso_as<T>(padD, padI) < iso) ? 1ull : 0ull;
+  const int lane = threadIdx.x & 63;
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane % LPW;
+  const bool last = sub == LPW - 1;
+  const u32 qStep = 512u / (u32)W, rStep = 512u % (u32)W;
+  const u32 pny = ny + 2u;
+  for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+    // (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic)
+    const u64 w0 = sp * (u64)SPAN_WORDS;
+    const u64 left = nwordsAll - w0;
+    const u32 nw = left < (u64)SPAN_WORDS ? (u32)left : (u32)SPAN_WORDS;
+    const u32 r0 = prow0 + (u32)w0 / (u32)W;
+    const u32 k0 = (u32)w0 % (u32)W;
+    const u32 wl = (u32)w0 + nw - 1, r1 = prow0 + wl / (u32)W;
+    const u32 k1 = wl % (u32)W;
+    // the stream: from the voxel one before word k0's first (row r0, where that is a row of the buffer) to the last voxel of
+    // word k1 of row r1 (likewise); the buffer's rows between them whole
+    const u32 rr0 = pad_rows_below(r0, ny, nz), rr1 = pad_rows_below(r1, ny, nz);
+    const u32 xs0 = pad_row_is_real(r0, ny, nz) && k0 ? k0 * 64u - 1u : 0u;                      // (<= nx: W = ceil((nx + 2) / 64))
+    const u32 xe1 = pad_row_is_real(r1, ny, nz) ? ((k1 + 1) * 64u - 1u < (u32)nx ? (k1 + 1) * 64u - 1u : (u32)nx) : 0u;
+    const u64 v0 = (u64)rr0 * (u64)nx + xs0;
+    const u32 nvox = (rr1 - rr0) * (u32)nx + xe1 - xs0;
+    const uintptr_t a0 = (uintptr_t)(vox + v0), ab = a0 & ~(uintptr_t)15;
+    const u32 skew = (u32)((a0 - ab) / sizeof(T));
+    const T *abase = reinterpret_cast<const T *>(ab);
+    // (the first and the last vector may reach up to 15 bytes outside the range: the same 16-byte granule as valid voxels,
+    //  so the loads cannot fault, and those bits are never used; a span of the ring alone reads nothing)
+    const u32 nvec = nvox ? (skew + nvox + VPL - 1) / VPL : 0u;
+    const u32 n1k = (nvec + 63) / 64;                      // 1 KiB chunks of the stream
+#pragma unroll 1
+    for (u32 c = (u32)wib * U; c < n1k; c += 4 * U) {      // the waves take the stream's 4 KiB trips in turn
+      Vec16<T> r[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        u32 vi = (c + u) * 64 + lane;
+        vi = vi < nvec ? vi : nvec - 1;
+        const uint4 *src = reinterpret_cast<const uint4 *>(abase + (size_t)vi * VPL);
+        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
+        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const u32 m = inside_bits<T>(r[u], iso);
+        const u64 word = group_or<LPW>((u64)m << (sub * VPL));
+        if (last) stage[(c + u) * VPL + lane / LPW] = word;
+      }
+    }
+    __syncthreads();
+    auto rsrc = __builtin_amdgcn_make_buffer_rsrc(bits + w0, 0, (int)(nw * 8u), 0x00020000);
+    auto cut = [&](u32 rw, u32 kk, bool live) -> u64 {
+      if (!live) return 0ull;
+      const int b = nx + 1 - (int)kk * 64;                 // bit of the ring's voxel behind the row (>= 0: kk < W)
+      const u64 rowMask = b < 63 ? lowmask(b + 1) : ~0ull;
+      if (!pad_row_is_real(rw, ny, nz)) return ringBit ? rowMask : 0ull;
+      // bit of the staged stream at which row rw's voxel x sits: skew + (rows of the buffer since the stream's) * nx + x - xs0
+      const u32 rowRel = skew + (pad_rows_below(rw, ny, nz) - rr0) * (u32)nx - xs0;
+      const u32 rel = rowRel + (kk ? kk * 64u - 1u : 0u);
+      const u32 j = rel >> 6, sh = rel & 63u;
+      const u64 lo = stage[j], hi = stage[j + 1];
+      u64 word = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
+      if (!kk) word = (word << 1) | ringBit;
+      if (b < 64) word = (word & lowmask(b)) | (ringBit << b);
+      return word;
+    };
+    auto mark = [&](u64 word, u32 rw) {
+      if (word) sliceOcc[rw / pny] = 1u;                   // benign race: all store 1
+    };
+    u32 i = threadIdx.x * 2;
+    u32 row = r0 + (k0 + i) / (u32)W;
+    u32 k = (k0 + i) % (u32)W;
+    for (; i < (u32)SPAN_WORDS; i += 512) {
+      const u32 rowB = k + 1 < (u32)W ? row : row + 1;
+      const u32 kB = k + 1 < (u32)W ? k + 1 : 0;
+      const u64 a = cut(row, k, i < nw), b = cut(rowB, kB, i + 1 < nw);
+      u32x4 v;
+      v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, i * 8, 0, 16);          // aux 16 = sc1: write-through; past nw: dropped
+      mark(a, row);
+      mark(b, rowB);
+      k += rStep; row += qStep;
+      if (k >= (u32)W) { k -= (u32)W; row++; }
+    }
+    __syncthreads();
+  }
+}
+
 // Per-slice occupancy (does the slice hold any inside voxel?) from the packed bits: one block per
 // slice, stops at the first non-zero word it sees.
 __global__ __launch_bounds__(256) void k_occupancy(const u64 *__restrict__ bits, size_t wordsPerSlice,
@@ -2297,7 +2455,7 @@ __global__ __launch_bounds__(256) void k_emit_cells(EmitArgs a, Grid g, size_t n
 // Every arithmetic step mirrors the ITK 3.x contract I3..I9 in the same
 // operation order as the oracle, so the float coordinates come out bit-identical.
 // ---------------------------------------------------------------------------------------------
-template <class T>
+template <class T, bool PAD = false>
 struct Sampler {
   const T *vox;
   int nx, ny, nzb;
@@ -2309,6 +2467,37 @@ struct Sampler {
   __device__ __forceinline__ T at(int x, int y, int zg) const {   // global z in
     return vox[((size_t)zlocal(zg) * ny + y) * nx + x];
   }
+  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
+    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
+    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
+    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
+    return at(x, y, zg);
+  }
+};
+
+// cuberille_set_border: the image the walk sees is the caller's with a ring of one constant voxel around it, and the ring
+// is not stored.  nx, ny, nzb are the PADDED dims (a whole volume: zglob0 = 0, gnz = nzb) and every position is one of
+// the padded frame; vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels.  Voxel p is vox[p - 1] where
+// 1 <= p <= n - 2 on every axis and `ring` elsewhere.
+template <class T>
+struct Sampler<T, true> {
+  const T *vox;
+  int nx, ny, nzb;
+  int zglob0, gnz;
+  T ring;
+  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
+  __device__ __forceinline__ T at_buffer(int x, int y, int z) const {   // positions inside the padded frame
+    // (unsigned compare: p - 1 in [0, n - 3])
+    const bool real = (unsigned)(x - 1) < (unsigned)(nx - 2) && (unsigned)(y - 1) < (unsigned)(ny - 2) &&
+                      (unsigned)(z - 1) < (unsigned)(nzb - 2);
+    if (!real) return ring;
+    return vox[((size_t)(z - 1) * (ny - 2) + (y - 1)) * (nx - 2) + (x - 1)];
+  }
+  // a position p of the padded frame (0 .. n - 1) along an axis of padded length n: on the ring?  its place in the buffer,
+  // clamped into it (so that a load is always legal; the ring's taps are replaced afterwards)
+  __device__ __forceinline__ bool on_ring(int p, int n) const { return p == 0 || p == n - 1; }
+  __device__ __forceinline__ int in_buffer(int p, int n) const { return min(max(p - 1, 0), n - 3); }
+  __device__ __forceinline__ T at(int x, int y, int zg) const { return at_buffer(x, y, zlocal(zg)); }
   __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
     x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
     y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
@@ -2408,8 +2597,8 @@ __device__ __forceinline__ void gradient_from_taps(const Geo &geo, bool dirIdent
   }
 }
 
-template <class T>
-__device__ __forceinline__ void gradient_at(const Sampler<T> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
+template <class T, bool PAD = false>
+__device__ __forceinline__ void gradient_at(const Sampler<T, PAD> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
                                             float f0, float out[3]) {
   float fm[3], fp[3];
 #pragma unroll
@@ -2470,12 +2659,18 @@ __device__ __forceinline__ void cell_gradients(const Geo &geo, bool dirIdentity,
 // up to the SIGN OF A ZERO result, and a zero gradient component only ever enters the walk as a term added to a
 // sum that starts at +0 -- so the walk cannot tell.  Non-finite taps always give a non-finite component here too;
 // the caller tests for that and gathers again with LITERAL = true.
-template <class T, bool LITERAL>
-__device__ __forceinline__ void gather_cell(const Sampler<T> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
+// PAD (cuberille_set_border): positions are those of the padded frame; "interior" then means that the cell and its ring lie
+// inside the caller's buffer -- one voxel further in on every side -- and the 12 row segments are read through a base pointer
+// moved back by one voxel per axis, with the buffer's own row and slice pitch.  Only cells that touch the implied ring
+// take the clamped forms, whose taps go through Sampler::at_buffer.
+template <class T, bool LITERAL, bool PAD = false>
+__device__ __forceinline__ void gather_cell(const Sampler<T, PAD> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
                                             float G[8][3], typename SiteValue<T>::type Vd[8]) {
   const bool unit = c.lo[0] + 1 == c.hi[0] && c.lo[1] + 1 == c.hi[1] && c.lo[2] + 1 == c.hi[2];
   const int zl = c.lo[2] - s.zglob0;              // buffer slice of the cell's lower z
-  const bool interior = unit && c.lo[0] >= 1 && c.lo[0] + 2 < s.nx && c.lo[1] >= 1 && c.lo[1] + 2 < s.ny && zl >= 1 && zl + 2 < s.nzb;
+  constexpr int IN = PAD ? 1 : 0;                 // voxels of the frame's rim that are not in memory
+  const bool interior = unit && c.lo[0] >= 1 + IN && c.lo[0] + 2 + IN < s.nx && c.lo[1] >= 1 + IN && c.lo[1] + 2 + IN < s.ny &&
+                        zl >= 1 + IN && zl + 2 + IN < s.nzb;
   // one address form per gather pass: the immediate-offset form only when EVERY lane gathering now sits in the
   // interior; a wave with border cells among them takes the clamped form for all its unit cells (it is the same
   // 32 pixels for an interior cell), instead of running both forms one after the other
@@ -2483,8 +2678,9 @@ __device__ __forceinline__ void gather_cell(const Sampler<T> &s, const Geo &geo,
   if (interior && allInterior) {
     // the cell and its ring of neighbours lie inside the buffer: nothing is clamped, so the 12 row segments are
     // the cell's own address plus wave-uniform strides, and the x neighbours are immediate offsets
-    const T *base = s.vox + ((size_t)zl * s.ny + c.lo[1]) * s.nx + c.lo[0];
-    const ptrdiff_t rowS = (ptrdiff_t)s.nx, sliceS = (ptrdiff_t)s.ny * s.nx;
+    const int pnx = s.nx - 2 * IN, pny = s.ny - 2 * IN;      // row and slice pitch of the buffer in memory
+    const T *base = s.vox + ((size_t)(zl - IN) * pny + (c.lo[1] - IN)) * pnx + (c.lo[0] - IN);
+    const ptrdiff_t rowS = (ptrdiff_t)pnx, sliceS = (ptrdiff_t)pny * pnx;
     T V[4][4][4];
 #pragma unroll
     for (int zi = 0; zi < 4; zi++)
@@ -2515,6 +2711,25 @@ __device__ __forceinline__ void gather_cell(const Sampler<T> &s, const Geo &geo,
       for (int yi = 0; yi < 4; yi++) {
         const bool zin = (zi == 1 || zi == 2), yin = (yi == 1 || yi == 2);
         if (!zin && !yin) continue;
+        if constexpr (PAD) {
+          // every tap is loaded from the buffer at its position clamped into it -- the same unconditional loads as the
+          // unpadded form -- and replaced by the ring's value where an axis says "ring": per axis four flags, per tap a select
+          const bool oyz = s.on_ring(ys[yi], s.ny) || s.on_ring(zs[zi], s.nzb);
+          const T *row = s.vox + ((size_t)s.in_buffer(zs[zi], s.nzb) * (s.ny - 2) + s.in_buffer(ys[yi], s.ny)) * (s.nx - 2);
+          if (zin && yin) {
+#pragma unroll
+            for (int xi = 0; xi < 4; xi++) {
+              const T v = row[s.in_buffer(xs[xi], s.nx)];
+              V[zi][yi][xi] = (oyz || s.on_ring(xs[xi], s.nx)) ? s.ring : v;
+            }
+          } else {
+#pragma unroll
+            for (int xi = 1; xi < 3; xi++) {
+              const T v = row[s.in_buffer(xs[xi], s.nx)];
+              V[zi][yi][xi] = (oyz || s.on_ring(xs[xi], s.nx)) ? s.ring : v;
+            }
+          }
+        } else {
         const T *row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
         if (zin && yin) {
 #pragma unroll
@@ -2522,6 +2737,7 @@ __device__ __forceinline__ void gather_cell(const Sampler<T> &s, const Geo &geo,
         } else {
           V[zi][yi][1] = row[xs[1]];
           V[zi][yi][2] = row[xs[2]];
+        }
         }
       }
     cell_gradients<T, LITERAL>(geo, dirIdentity, V, G, Vd);
@@ -2558,11 +2774,14 @@ __device__ __forceinline__ void gather_cell(const Sampler<T> &s, const Geo &geo,
 // block in SGPRs and spills what does not fit (62 of them before) into the lanes of a vector register its loop reads back.
 // GEOM 2 = that; 1: identity direction, region at 0, ANY spacing (a diagonal matrix: three scalars instead of eighteen -- the
 // anisotropic volumes of CT and MR); 0: anything (a rotation, a region that starts elsewhere).
-template <class T, int MODE, int GEOM>
+// PAD (cuberille_set_border, MODE 0, a whole volume): `g` and `geo` describe the padded image, `vox` is the caller's buffer and
+// the ring's value arrives as padD / padI (the pair the iso value travels as); GEOM 1 and 2 then stand for a caller's image
+// whose region starts at index 0, i.e. a padded one that starts at -1.  The other instantiations never read the two arguments.
+template <class T, int MODE, int GEOM, bool PAD = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentityArg,
                                                  float *__restrict__ points, u64 nPoints, u64 nGhost, u64 chunk,
                                                  int REFILL, int xcdRemap, int forceLiteral, Totals *__restrict__ tot,
-                                                 u32 *__restrict__ escList, u32 escCap, int dyn) {
+                                                 u32 *__restrict__ escList, u32 escCap, int dyn, double padD, long long padI) {
   const int lane = threadIdx.x & 63;
   if (dyn) {
     if (!tot->go) return;
@@ -2597,7 +2816,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   if (wave >= nBatches) return;
   u64 next = 0;                                   // wave-uniform cursor
   const u64 end = ((nBatches - wave + NW - 1) / NW) << lgChunk;
-  Sampler<T> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  Sampler<T, PAD> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  if constexpr (PAD) s.ring = iso_as<T>(padD, padI);
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
   const double iso = (double)iso_as<T>(prm.iso, prm.isoInt);
   unsigned myIters = 0;
@@ -2627,7 +2847,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       geo.dir[i] = (i % 4 == 0) ? 1.0 : 0.0;
       if (IDENT || i % 4 != 0) geo.p2i[i] = (i % 4 == 0) ? 1.0 : 0.0;
     }
-    geo.istart[0] = geo.istart[1] = geo.istart[2] = 0;
+    geo.istart[0] = geo.istart[1] = geo.istart[2] = PAD ? -1 : 0;
     unitP2I = IDENT;
   }
   const int dirIdentity = GEOM ? 1 : dirIdentityArg;
@@ -2673,7 +2893,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       }
       if (!escaped) {
       if (c.bc[0] != kc[0] || c.bc[1] != kc[1] || c.bc[2] != kc[2]) {
-        gather_cell<T, false>(s, geo, dirIdentity != 0, c, G, Vd);
+        gather_cell<T, false, PAD>(s, geo, dirIdentity != 0, c, G, Vd);
 #pragma unroll
         for (int k = 0; k < 3; k++) kc[k] = c.bc[k];
         // all 32 cached numbers finite?  x*0 accumulates to 0 for finite x, to NaN for an infinity or a NaN
@@ -2686,7 +2906,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
           for (int k = 0; k < 3; k++) tf = __builtin_fmaf(G[counter][k], 0.0f, tf);
         }
         cellFinite = (tf == 0.0f) && (td == 0.0);
-        if (!cellFinite) gather_cell<T, true>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
+        if (!cellFinite) gather_cell<T, true, PAD>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
 #pragma unroll
         for (int counter = 0; counter < 8; counter++)
 #pragma unroll
@@ -3435,6 +3655,34 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
   if (z1 <= z0) return hipSuccess;
   const double iso = prm.iso;
   const long long isoI = prm.isoInt;
+  if (wAll.pad)
+    return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+      typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+      // cuberille_set_border: `g` is the padded layout, z0 / z1 are slices of the caller's buffer; the range that holds its
+      // first (last) slice writes the ring's slice below (above) it as well
+      const int nx = g.nx - 2, ny = g.ny - 2, nz = g.nzb - 2;
+      const u64 pz0 = z0 == 0 ? 0 : (u64)z0 + 1, pz1 = z1 == nz ? (u64)nz + 2 : (u64)z1 + 1;
+      const u64 wps = (u64)g.ny * g.W, t0 = pz0 * wps, t1 = pz1 * wps;
+      const T *vox = (const T *)wAll.vox;
+      // the staged spans under the rule of the unpadded sweep: a buffer of 256 MiB and more, fewer than 2^32 words
+      const bool spans = tn.classify_variant != 1 && !tn.no_stream_classify && ((uintptr_t)vox % sizeof(T)) == 0 &&
+                         ((u64)nx * (u64)ny * (u64)nz * sizeof(T) >= (256ull << 20) || tn.classify_variant == 2) &&
+                         (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
+      if (spans) {
+        const u64 nwordsAll = t1 - t0;
+        const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
+        const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;     // two workgroups per CU, whole rounds
+        const u64 rounds = (nspans + want - 1) / want;
+        const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
+        hipLaunchKernelGGL((k_classify_pad_span_rows<T>), dim3(blocks), dim3(256), 0, s, vox, wAll.bits + t0, nspans, nwordsAll,
+                           (u32)(pz0 * (u64)g.ny), nx, (u32)ny, (u32)nz, g.W, iso, isoI, wAll.padValue, wAll.padValueInt, wAll.sliceOcc);
+      } else {
+        const unsigned blocks = grid_for((t1 - t0) * 64, 256, 8192);
+        hipLaunchKernelGGL((k_classify_pad_words<T>), dim3(blocks), dim3(256), 0, s, vox, wAll.bits, t0, t1, nx, ny, nz, g.W, iso, isoI,
+                           wAll.padValue, wAll.padValueInt, wAll.sliceOcc);
+      }
+      return hipGetLastError();
+    });
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
     Workspace w = wAll;
@@ -3529,6 +3777,7 @@ hipError_t launch_occupancy(int pixel_type, const Workspace &w, const Grid &g, c
   size_t elem = 1;
   (void)by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t { elem = sizeof(*tag); return hipSuccess; });
   const bool aligned = g.nx % 64 == 0 && ((uintptr_t)w.vox % 16) == 0;
+  if (w.pad) return hipSuccess;                                      // (both padded sweeps mark the occupancy themselves)
   if (ragged_span_path(w, g, elem, tn)) return hipSuccess;           // (that sweep marks the occupancy itself)
   if ((aligned && occupancy_shift(g) < 0) || ragged_stream_path(w, g, elem, tn))
     hipLaunchKernelGGL(k_occupancy, dim3(g.nzb), dim3(256), 0, s, w.bits, (size_t)g.ny * g.W, w.sliceOcc);
@@ -3867,25 +4116,35 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     } else if (xcd < 0) xcd = 0;
     // the kernel's form by the geometry: 2 identity matrices and a region at index 0; 1 identity direction, any spacing (the
     // inverse of a diagonal matrix by cofactors has exact zeros off its diagonal); 0 anything else
-    bool diag = dirIdentity != 0 && geo.istart[0] == 0 && geo.istart[1] == 0 && geo.istart[2] == 0 && tn.proj_ident != 0;
+    // (cuberille_set_border: the padded region starts one index below the caller's; the padded kernels' forms 1 and 2 hold -1)
+    const int at0 = w.pad ? -1 : 0;
+    bool diag = dirIdentity != 0 && geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0 && tn.proj_ident != 0;
     bool unit = diag;
     for (int i = 0; i < 9; i++) {
       if (i % 4 != 0) diag = diag && geo.p2i[i] == 0.0;
       unit = unit && geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0);
     }
     const int geom = unit ? 2 : diag ? 1 : 0;
-#define CUBERILLE_LAUNCH_PROJECT(MODE, GEOM)                                                                                 \
-    hipLaunchKernelGGL((k_project<T, MODE, GEOM>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
+#define CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, PAD)                                                                        \
+    hipLaunchKernelGGL((k_project<T, MODE, GEOM, PAD>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
                        w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
-                       w.escCap, dyn)
+                       w.escCap, dyn, w.padValue, w.padValueInt)
+#define CUBERILLE_LAUNCH_PROJECT(MODE, GEOM) CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, false)
 #define CUBERILLE_LAUNCH_PROJECT_GEOM(MODE)                                                                                  \
     do { if (geom == 2) CUBERILLE_LAUNCH_PROJECT(MODE, 2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT(MODE, 1);            \
          else CUBERILLE_LAUNCH_PROJECT(MODE, 0); } while (0)
+    if (w.pad) {
+      // a whole volume, every slice in the (implied) buffer: MODE 0, the only one offered with a border (count_prepare)
+      if (mode != 0) return hipErrorInvalidValue;
+      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_PAD(0, 2, true); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_PAD(0, 1, true);
+      else CUBERILLE_LAUNCH_PROJECT_PAD(0, 0, true);
+    } else
     if (mode == 1) CUBERILLE_LAUNCH_PROJECT_GEOM(1);
     else if (mode == 2) CUBERILLE_LAUNCH_PROJECT_GEOM(2);
     else CUBERILLE_LAUNCH_PROJECT_GEOM(0);
 #undef CUBERILLE_LAUNCH_PROJECT_GEOM
 #undef CUBERILLE_LAUNCH_PROJECT
+#undef CUBERILLE_LAUNCH_PROJECT_PAD
     return hipGetLastError();
   });
 }

@@ -119,6 +119,17 @@ def check_iso(pixel_type, params):
         raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "iso value is not representable in the pixel type")
 
 
+def check_border(pixel_type, border):
+    """64-bit integer pixels: the border value of Extractor.set_border must be one the pixel type holds (the library checks
+    the other integer types itself, as it does the iso value)."""
+    if pixel_type not in (8, 9) or not border or not border[0]:
+        return
+    v = border[1]
+    lo, hi = (-(1 << 63), 1 << 63) if pixel_type == 8 else (0, 1 << 64)
+    if v is None or not (lo <= v < hi):
+        raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "the border value is not representable in the pixel type")
+
+
 def make_desc(np_dtype, dims_xyz, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=None, index_start=(0, 0, 0)):
     d = _abi.ImageDesc()
     d.pixel_type = PIXEL_CODES[np.dtype(np_dtype)]
@@ -144,6 +155,7 @@ class Extractor:
             raise _abi.CuberilleError(rc, text.decode() if text else "")
         self.device = int(device)
         self.result = None
+        self._border = (0, 0)               # set_border: width, and the value as a 64-bit integer pixel type would hold it
 
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx:
@@ -182,6 +194,7 @@ class Extractor:
         vox = np.ascontiguousarray(vol.voxels)
         desc = make_desc(vox.dtype, vol.dims, vol.spacing, vol.origin, vol.direction, getattr(vol, "index_start", (0, 0, 0)))
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_host(
             self._ctx, C.byref(desc), C.c_void_p(vox.ctypes.data), C.byref(params), C.byref(res)))
@@ -196,6 +209,7 @@ class Extractor:
         nx, ny, _ = (int(v) for v in desc.dims)
         dtype = np.dtype(PIXEL_DTYPES[int(desc.pixel_type)])
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         raised = []
 
         def trampoline(_user, dst, z0, z1):
@@ -228,6 +242,7 @@ class Extractor:
 
     def extract_device(self, dev_ptr, desc, params, slab=None):
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_device(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -237,6 +252,7 @@ class Extractor:
 
     def count(self, dev_ptr, desc, params, slab=None):
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         npnt, ncell = C.c_uint64(), C.c_uint64()
         _abi.check(self._ctx, self._lib.cuberille_count(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -257,6 +273,7 @@ class Extractor:
         """Count and the offset-free part of the emit, launched back to back without waiting (cuberille_step_begin).
         Returns (device pointer, bytes) of this rank's row, to be all-gathered in rank order."""
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         p, n = C.c_void_p(), C.c_size_t()
         _abi.check(self._ctx, self._lib.cuberille_step_begin(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -267,6 +284,7 @@ class Extractor:
         """First half of step_begin for the bits-first halo (cuberille_step_classify): thresholds the owned slices and
         returns (device pointer of the buffer's bit volume, words per slice) without waiting."""
         check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._border)
         p, n = C.c_void_p(), C.c_size_t()
         _abi.check(self._ctx, self._lib.cuberille_step_classify(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -350,6 +368,18 @@ class Extractor:
         extractor keeps the gradient image (and geometry) of its next projecting extraction and walks every later volume
         along it.  hold=False drops the image and returns to the default: each volume's own gradient."""
         _abi.check(self._ctx, self._lib.cuberille_hold_gradient(self._ctx, 1 if hold else 0))
+
+    def set_border(self, width, value=0):
+        """Close the surface at the image border without a padded copy (cuberille_set_border): every later whole-volume
+        extraction gives the mesh of the image with a ring of `width` (0: off, or 1) voxels of `value` around it -- dims + 2,
+        index_start - 1, the same origin, spacing and direction: what itk::ConstantPadImageFilter hands the reference.  The
+        value converts to the pixel type like the iso value (an integer past 2^53 reaches the 64-bit integer types whole).
+        Slabs, steps, groups, the B-spline interpolator, a held or recursive-Gaussian gradient and the two projection
+        variants are refused at the extraction."""
+        exact = iso_int_of(value)
+        as_int = 0 if exact is None else ((exact + (1 << 63)) % (1 << 64)) - (1 << 63)
+        _abi.check(self._ctx, self._lib.cuberille_set_border(self._ctx, int(width), float(value), as_int))
+        self._border = (int(width), exact)
 
     def set_interpolator(self, kind, spline_order=3, coordinate_bits=32, coefficient_bits=32):
         """The value interpolator of the walk for the later extractions (cuberille_set_interpolator): _abi.INTERP_LINEAR
@@ -517,6 +547,13 @@ class ExtractorGroup:
         ctx = self.context(i)
         _abi.check(ctx, self._lib.cuberille_debug_set_option(ctx, name.encode(), int(value)))
 
+    def set_border(self, width, value=0):
+        """An implied border (Extractor.set_border) on every member: the group's extraction then raises the library's
+        refusal -- the ring would have to reach across the slabs."""
+        for i in range(len(self.devices)):
+            ctx = self.context(i)
+            _abi.check(ctx, self._lib.cuberille_set_border(ctx, int(width), float(value), 0))
+
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
         (slab -1: every slab's; n < 0: off)."""
@@ -596,6 +633,8 @@ class CuberilleImageToMeshFilter:
         self._gradient = GRADIENT_CENTRAL         # h:21: and so is the recursive-Gaussian gradient
         self._stale_gradient = False
         self._bspline = None                      # (coordinate bits, coefficient bits) of SetBSplineInterpolator, or None
+        self._pad_border = False                  # SetPadBorder: off, like the reference
+        self._border_pad_value = 0                # SetBorderPadValue: NumericTraits<InputPixelType>::Zero
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -742,6 +781,29 @@ class CuberilleImageToMeshFilter:
             raise ValueError("the device B-spline walk implements order 3 with float32/float32 or float64/float64")
         self._bspline = (cb, kb)
 
+    def SetPadBorder(self, b):
+        """Not in the reference -- what its class comment (h:54-57) tells the caller to do by hand: treat the input as if
+        itk::ConstantPadImageFilter had padded it by one pixel of GetBorderPadValue() on every side, so that a surface that
+        meets the image border is closed there.  No padded copy is made (cuberille_set_border).  Default off."""
+        self._pad_border = bool(b)
+
+    def GetPadBorder(self):
+        return self._pad_border
+
+    def PadBorderOn(self):
+        self.SetPadBorder(True)
+
+    def PadBorderOff(self):
+        self.SetPadBorder(False)
+
+    def SetBorderPadValue(self, v):
+        """The constant of the implied border, an InputPixelType (default 0, ConstantPadImageFilter's; signed CT data wants
+        its minimum)."""
+        self._border_pad_value = v
+
+    def GetBorderPadValue(self):
+        return self._border_pad_value
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -750,6 +812,10 @@ class CuberilleImageToMeshFilter:
         if self._input is None:
             # the ITK pipeline throws for a missing required input (txx:33)
             raise RuntimeError("CuberilleImageToMeshFilter: input 0 is required but not set")
+        if len(self._devices) > 1 and self._pad_border:
+            # (before a device is touched: the ring would have to reach across the slabs)
+            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "an implied border (SetPadBorder / cuberille_set_border) is not "
+                                      "offered in a group: the ring would have to reach across slabs")
         self._acquire(True)
         vol = self._input
         if self._step < 0.0:                      # txx:82-85, sticky like the reference (quirk Q3)
@@ -769,6 +835,7 @@ class CuberilleImageToMeshFilter:
             self._extractor.set_interpolator(_abi.INTERP_BSPLINE, 3, *self._bspline)
         else:
             self._extractor.set_interpolator(_abi.INTERP_LINEAR)
+        self._extractor.set_border(1 if self._pad_border else 0, self._border_pad_value)
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
         self.last_number_of_slabs = 1

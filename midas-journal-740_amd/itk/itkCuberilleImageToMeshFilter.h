@@ -212,6 +212,22 @@ public:
   itkSetMacro(BSplineOnDevice, bool);
   itkBooleanMacro(BSplineOnDevice);
 
+  /** Not in the reference -- what its class comment (above) tells the caller to do by hand.  PadBorderOn(): Update() gives the
+   *  mesh the filter gives for the output of itk::ConstantPadImageFilter with a pad of one pixel of GetBorderPadValue() on
+   *  every side of the input (the region grown by one, its start index one lower, the same origin, spacing and direction):
+   *  a surface that meets the image border is closed there -- the same points, bit for bit, and cells as pad-then-filter.
+   *  No padded copy of the image is made, on the host or on the device (cuberille_set_border).  BorderPadValue defaults
+   *  to NumericTraits<InputPixelType>::Zero like the pad filter's constant; signed CT data wants its minimum instead.
+   *  Offered where the device walks (or nothing is projected): with SetDevices of more than one device, the B-spline
+   *  interpolator, ReproduceStaleGradient, the compiled-out projection / gradient variants or an interpolator that takes
+   *  the host walk (the user's object is bound to the unpadded image) Update() throws with the library's message.
+   *  Default off: the reference's behaviour. */
+  itkGetMacro(PadBorder, bool);
+  itkSetMacro(PadBorder, bool);
+  itkBooleanMacro(PadBorder);
+  itkGetMacro(BorderPadValue, InputPixelType);
+  itkSetMacro(BorderPadValue, InputPixelType);
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -250,6 +266,8 @@ private:
   bool m_ReleaseHostMeshAfterFill;
   bool m_ReproduceStaleGradient;
   bool m_BSplineOnDevice;
+  bool m_PadBorder;
+  InputPixelType m_BorderPadValue;
   double m_LastDeviceSeconds;
   double m_LastMeshFillSeconds;
   double m_LastExtractSeconds;

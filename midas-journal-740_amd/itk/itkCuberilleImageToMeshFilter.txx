@@ -497,6 +497,8 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_ReleaseHostMeshAfterFill = false;
   m_ReproduceStaleGradient = false;
   m_BSplineOnDevice = true;
+  m_PadBorder = false;
+  m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
   m_LastDeviceSeconds = 0.0;
   m_LastMeshFillSeconds = 0.0;
   m_LastExtractSeconds = 0.0;
@@ -600,7 +602,12 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetInp
       if (this->AcquireGroup(false)) (void)cuberille_group_warm_up(m_Group, &desc, 0);
       }
     else if (this->AcquireContext(false))
+      {
+      // (PadBorderOn() ahead of SetInput: the workspace of the image with its border)
+      (void)cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
+                                 cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
       (void)cuberille_warm_up(m_Context, &desc, 0);
+      }
     }
 }
 
@@ -654,6 +661,10 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "USE_ADVANCED_PROJECTION / USE_LINESEARCH_PROJECTION / USE_GRADIENT_RECURSIVE_GAUSSIAN are only "
                          "offered with the default LinearInterpolateImageFunction");
 
+  if (m_PadBorder && hostWalk)
+    itkExceptionMacro(<< "an implied border (PadBorderOn / cuberille_set_border) is not offered with an interpolator that takes "
+                         "the host walk: the caller's interpolator object is bound to the unpadded image");
+
   // several devices: the context group, for what a slab takes (the host walk included: its device part does not project)
   const bool grouped = m_Devices.size() > 1 && !deviceBSpline && !m_ReproduceStaleGradient &&
                        !(prm.project_vertices && prm.gradient_variant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN);
@@ -663,6 +674,10 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   if (grouped)
     {
     this->AcquireGroup(true);
+    // (an implied border on the members: the group's extraction refuses it, and that message is what the caller sees)
+    for (int i = 0; i < static_cast<int>(m_Devices.size()); i++)
+      (void)cuberille_set_border(cuberille_group_context(m_Group, i), m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
+                                 cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_group_extract_host: " << cuberille_group_last_error(m_Group));
@@ -679,6 +694,9 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_set_interpolator(m_Context, deviceBSpline ? CUBERILLE_INTERP_BSPLINE : CUBERILLE_INTERP_LINEAR, 3,
                                    deviceBSpline ? bsplineBits : 0, deviceBSpline ? bsplineBits : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
+    if (cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
+                             cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue)) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_border: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
