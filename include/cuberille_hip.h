@@ -83,7 +83,8 @@ typedef struct {
   int32_t generate_triangles;    /* m_GenerateTriangleFaces (default 1) */
   int32_t project_vertices;      /* m_ProjectVerticesToIsoSurface (default 1) */
   double distance_threshold;     /* m_ProjectVertexSurfaceDistanceThreshold (0.5) */
-  double step_length;            /* m_ProjectVertexStepLength (-1 => 0.25*max spacing, txx:82-85) */
+  double step_length;            /* m_ProjectVertexStepLength (-1 => 0.25*max spacing, txx:82-85; on a context that holds a
+                                    gradient, cuberille_hold_gradient: of the FIRST extraction's image, kept like the reference keeps it) */
   double relaxation;             /* m_ProjectVertexStepLengthRelaxationFactor (0.95) */
   uint32_t max_steps;            /* m_ProjectVertexMaximumNumberOfSteps (50) */
   int32_t emulate_empty_slice_aliasing; /* 1: reproduce the two-plane lookup quirk of txx:156-161

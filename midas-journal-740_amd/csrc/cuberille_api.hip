@@ -108,6 +108,7 @@ struct cuberille_ctx {
   DevBuf heldGrad;                       // cuberille_hold_gradient: the float gradient image of the first projecting extraction
   HeldGradient held{};                   // ... with its geometry (img == null: none yet); what every later walk follows
   bool holdGradient = false;             // ... asked for
+  double heldStep = -1.0;                // ... and the default step length that "filter object" resolved at its first extraction
   int interp = CUBERILLE_INTERP_LINEAR;  // cuberille_set_interpolator: the value interpolator of later walks ...
   int bsBits = 0;                        // ... and, for the B-spline, its coordinate / coefficient width (32 or 64)
   DevBuf bsCoef, bsScratch;              // the B-spline coefficient image, and the double scratch of its passes (32-bit only)
@@ -604,6 +605,13 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   Geo geo{};
   Params p{};
   resolve(&framed, prm, geo, p);
+  if (c->holdGradient && prm->step_length < 0.0) {
+    // cuberille_hold_gradient stands for one filter OBJECT: m_ProjectVertexStepLength is replaced by its default once, at the
+    // first Update(), from THAT input's spacing, and stays (txx:82-85) -- like the gradient image, the default step of every
+    // later extraction is the first one's
+    if (c->heldStep < 0.0) c->heldStep = p.step;
+    p.step = c->heldStep;
+  }
   const bool whole = !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);   // (all-zero slab = whole volume)
   if (!whole && c->padWidth)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
@@ -1839,6 +1847,7 @@ int cuberille_mesh_host(cuberille_ctx *c, float **points, uint64_t **cells) {
 int cuberille_hold_gradient(cuberille_ctx *c, int hold) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  if (!hold || !c->holdGradient) c->heldStep = -1.0;       // (asked again while holding: the same filter object goes on)
   c->holdGradient = hold != 0;
   if (!hold && c->held.img) {
     (void)hipSetDevice(c->device);

@@ -658,6 +658,7 @@ template <class TImage> class ImageFileWriter;
 template <class TImage, class TCoordRep = double, class TCoefficientType = double> class BSplineInterpolateImageFunction;   // (defined in itkBSplineLite.h)
 template <class TIn, class TOut, class TCriterion> class QuadEdgeMeshQuadricDecimation;
 template <class TMesh> class NumberOfFacesCriterion;
+#ifndef ITK_LITE_HOST_FILTER   // (with it: itkLiteHostFilter.h, included below, defines these three for the host)
 template <class TImage> class ConstShapedNeighborhoodIterator;
 template <class TImage, class TOperatorValue = float, class TOutputValue = float> class GradientImageFilter {
 public:
@@ -666,7 +667,9 @@ public:
   typedef CovariantVector<TOutputValue, TImage::ImageDimension> OutputPixelType;
   typedef Image<OutputPixelType, TImage::ImageDimension> OutputImageType;
 };
+#endif
 template <class TImage> class GradientRecursiveGaussianImageFilter;
+#ifndef ITK_LITE_HOST_FILTER
 template <class TImage, class TCoordRep = double> class VectorLinearInterpolateImageFunction {
 public:
   typedef VectorLinearInterpolateImageFunction Self;
@@ -716,6 +719,12 @@ protected:
   LinearInterpolateImageFunction() : m_Image(0) {}
   const TInputImage *m_Image;
 };
+
+#else
+}  // namespace itk
+#include "itkLiteHostFilter.h"
+namespace itk {
+#endif
 
 // ------------------------------------------------------------------------------------------
 // ImageToMeshFilter

@@ -6,6 +6,10 @@
 //       the interpolator's coefficient image (x fastest, coefBits wide); needs no GPU
 //   bspline_walk eval <in.raw> <pixel> <nx> <ny> <nz> <coordBits> <coefBits> <geometry> <points.raw> <n> <out.raw> [order]
 //       Evaluate() at n points (float64 xyz in, float64 values out); needs no GPU
+//   bspline_walk walk <in.raw> <pixel> <nx> <ny> <nz> <bits> <geometry> <iso> <thr> <step> <relax> <maxSteps> <start.raw> <n> <out.raw>
+//       the drop-in's host walk alone (HostGradient + HostWalk, what `filter ... host` runs after the device's sweep) through
+//       BSplineInterpolateImageFunction<Image, T, T> of order 3: n start points (float32 xyz) -> walked points; needs no GPU
+//       (<pixel>: u8 i16 f32)
 //   bspline_walk filter <volume> host|device <threads> <bits> <iso> <tri> <project> <thr> <step> <relax> <maxSteps>
 //                <outPoints.raw> <outCells.raw> [raw <pixel> <nx> <ny> <nz>] [geometry <geometry>] [order <k>] [repeat <r>]
 //       the whole filter with BSplineInterpolateImageFunction<Image, T, T> (T = float for 32, double for 64 bits): `host`
@@ -153,6 +157,27 @@ template <class T, class C> int eval(char **argv, int argc)
   return 0;
 }
 
+template <class T, class C> int walk(char **argv)
+{
+  typedef itk::Image<T, 3> ImageType;
+  typename ImageType::Pointer image = raw_image<T>(argv[2], std::atol(argv[4]), std::atol(argv[5]), std::atol(argv[6]));
+  apply_geometry(image.GetPointer(), parse_geometry(argv[8]));
+  typedef itk::BSplineInterpolateImageFunction<ImageType, C, C> Interp;
+  typename Interp::Pointer interp = Interp::New();
+  interp->SetSplineOrder(3);
+  interp->SetInputImage(image);
+  const size_t n = (size_t)std::atoll(argv[15]);
+  std::vector<char> buf = slurp(argv[14], n * 3 * sizeof(float));
+  float *pts = reinterpret_cast<float *>(&buf[0]);
+  itk::cuberille_detail::HostGradient<ImageType> gradient(image.GetPointer());
+  itk::cuberille_detail::HostWalk<ImageType, Interp> w =
+    {&gradient, interp.GetPointer(), pts, static_cast<double>(static_cast<T>(std::atof(argv[9]))), std::atof(argv[10]), std::atof(argv[11]),
+     std::atof(argv[12]), (unsigned int)std::atoi(argv[13])};
+  itk::cuberille_detail::ParallelRanges(n, w, 1u);
+  dump(argv[16], pts, n * 3 * sizeof(float));
+  return 0;
+}
+
 template <class T, class C> int filter(int argc, char **argv)
 {
   typedef itk::Image<T, 3> ImageType;
@@ -263,6 +288,17 @@ int main(int argc, char **argv)
       if (px == "i64") return by_bits<long long>(mode, bits, argc, argv);
       if (px == "u64") return by_bits<unsigned long long>(mode, bits, argc, argv);
       std::fprintf(stderr, "unknown pixel type %s\n", px.c_str());
+      return 1;
+      }
+    if (!std::strcmp(mode, "walk"))
+      {
+      if (argc < 17) { std::fprintf(stderr, "too few arguments\n"); return 1; }
+      const std::string px = argv[3];
+      const bool wide = std::atoi(argv[7]) == 64;
+      if (px == "u8") return wide ? walk<unsigned char, double>(argv) : walk<unsigned char, float>(argv);
+      if (px == "i16") return wide ? walk<short, double>(argv) : walk<short, float>(argv);
+      if (px == "f32") return wide ? walk<float, double>(argv) : walk<float, float>(argv);
+      std::fprintf(stderr, "walk: unsupported pixel type %s\n", px.c_str());
       return 1;
       }
     if (!std::strcmp(mode, "filter"))

@@ -627,8 +627,11 @@ struct Filter {
   // txx:59-216
   void GenerateData() {
     const Geometry &g = im.g;
-    double maxSpacing = g.spacing[0];                                         // txx:75-79
-    for (int i = 1; i < 3; i++) maxSpacing = maxSpacing > g.spacing[i] ? maxSpacing : g.spacing[i];
+    // txx:75-85: the default replaces m_ProjectVertexStepLength itself, so it is taken ONCE per filter object, from the
+    // spacing of the input of its first Update(), and stays: on a later update (cuberille_oracle_run_after) that is `first`
+    const Geometry &sg = gim.g;
+    double maxSpacing = sg.spacing[0];                                        // txx:75-79
+    for (int i = 1; i < 3; i++) maxSpacing = maxSpacing > sg.spacing[i] ? maxSpacing : sg.spacing[i];
     step_length = prm.step_length;
     if (step_length < 0.0) step_length = maxSpacing * 0.25;                   // txx:82-85
 

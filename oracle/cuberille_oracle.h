@@ -10,12 +10,14 @@
  * load or call anything declared here.  The product library
  * (midas-journal-740_amd/csrc) never does, and fails loudly without a GPU.
  *
- * PARITY STATUS: topology (ids, order, counts) is pinned by the 19 known-answer
- * (points, cells) pairs of the reference's Testing/CMakeLists.txt:10-331
- * (tests/golden/ctest_cases.json).  Vertex coordinates and the triangle split are
- * "parity unpinned": no reference test or fixture holds them and ITK is not
- * buildable in this image, so they follow the ITK 3.x contract adopted in
- * DESIGN.md, not verified reference output.
+ * PARITY STATUS: the FILTER's own logic -- traversal, lookup maps, ids, vertex and cell order, the triangle split,
+ * casts and promotions, the control flow of all three walk branches, a second Update() -- is pinned, bit for bit, to
+ * the reference's own itkCuberilleImageToMeshFilter.{h,txx}, compiled unchanged into oracle/_ref/ref_filter*
+ * (oracle/Makefile, target `ref`; tests/test_reference_filter.py; recorded in
+ * tests/golden/reference_filter_digests.json), besides the 19 (points, cells) pairs of the reference's
+ * Testing/CMakeLists.txt:10-331.  STILL UNPINNED: ITK's own bytes for the primitives both sides restate from the
+ * contract (I3..I8, the B-spline classes), the recursive-Gaussian gradient, the VTK number format, proj_iterations and
+ * the stop counters (the reference's need DEBUG_PRINT).  DESIGN.md section 3.
  */
 #ifndef CUBERILLE_ORACLE_H
 #define CUBERILLE_ORACLE_H
@@ -80,7 +82,8 @@ typedef struct {
 int cuberille_oracle_run(const oracle_image *img, const oracle_params *prm, oracle_mesh *out);
 /* A LATER Update() of a filter object whose first projecting Update() ran on `first` (same pixel type; size and geometry
  * may differ): quirk Q3 -- ComputeGradientImage() only builds the gradient interpolator while it is null (txx:484), so
- * the walk of every later update follows the gradient image, and the geometry, of that first input.  first == NULL: the
+ * the walk of every later update follows the gradient image, and the geometry, of that first input -- and a negative
+ * step_length is a quarter of THAT input's largest spacing (txx:82-85 replace the member once).  first == NULL: the
  * first update itself (= cuberille_oracle_run). */
 int cuberille_oracle_run_after(const oracle_image *img, const oracle_image *first, const oracle_params *prm, oracle_mesh *out);
 void cuberille_oracle_free(oracle_mesh *m);

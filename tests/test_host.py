@@ -148,6 +148,16 @@ def test_product_never_imports_the_oracle():
             if fn.endswith((".py", ".hip", ".h", ".cpp", ".cxx", ".txx")) or fn == "Makefile":
                 text = open(os.path.join(dirpath, fn), errors="replace").read()
                 assert "oracle/" not in text and "import oracle" not in text and "cuberille_oracle" not in text, fn
+                assert "ref_filter" not in text and "_ref/" not in text, fn
+
+
+def test_product_and_bench_never_reach_the_reference_filter_binaries():
+    """oracle/_ref/ref_filter* -- the reference's own filter text compiled for the tests -- are checkers like the oracle: neither
+    the package nor bench.py may run, load or name them (bench.py's cpu_baseline leg times the oracle, not them)."""
+    text = open(os.path.join(ROOT, "bench.py"), errors="replace").read()
+    assert "ref_filter" not in text and "_ref" not in text
+    text = open(os.path.join(ROOT, "__graft_entry__.py"), errors="replace").read()
+    assert "ref_filter" not in text
 
 
 def test_filter_defaults_and_clamps(pkg):
