@@ -187,7 +187,7 @@ typedef struct cuberille_ctx cuberille_ctx;
 int cuberille_abi_version(void);
 /* number of usable gfx950 devices (0 when there is none; never fails) */
 int cuberille_device_count(void);
-const char *cuberille_last_error(const cuberille_ctx *ctx); /* ctx may be NULL: last create error */
+const char *cuberille_last_error(const cuberille_ctx *ctx); /* ctx may be NULL: last create (or cuberille_region_desc) error */
 
 /* context: owns a stream and the device workspace (re-used across calls) */
 int cuberille_create(cuberille_ctx **out, int device_id);
@@ -396,6 +396,37 @@ int cuberille_set_interpolator(cuberille_ctx *ctx, int kind, int spline_order, i
  * While the setting is on, cuberille_debug_bits speaks the padded frame (rows of N0 + 2 voxels, N1 + 2 rows, N2 + 2 slices);
  * so does cuberille_slice_occupancy (N2 + 2 slices, the ring's first); so does cuberille_slice_counts (N2 + 2 entries). */
 int cuberille_set_border(cuberille_ctx *ctx, int pad_width, double pad_value, int64_t pad_value_int);
+/* NEW SYMBOLS (added within ABI 13: no struct changes).  Extract a box of a larger volume in place, without a cropped copy.
+ * With a region set, `img` still describes the whole buffer the caller hands over -- its dims, its index_start s, origin,
+ * spacing and direction -- and every later whole-volume extraction on ctx yields exactly the mesh an extraction with the
+ * setting off yields for the image C that itk::ExtractImageFilter / RegionOfInterestImageFilter (the index kept) makes of it:
+ * dims `size`, start index s + start, the same origin / spacing / direction, C[p] = I[p + start] -- the same point ids, order,
+ * float bits, cells and walk counters.  `start` is a position in the buffer (x, y, z).  Voxels outside the box never enter a
+ * result: every clamp (ZeroFluxNeumann, the interpolators' Start/EndIndex) happens at the box's faces, as it would on the copy.
+ * No copy of the voxels, cropped or not, is made on the device (cuberille_extract_device, cuberille_count + cuberille_emit):
+ * the 1-bit volume and the rest of the workspace have the box's size, a pitched threshold sweep and a walk that knows the
+ * buffer's row and slice pitch read the caller's buffer.  cuberille_extract_host uploads the box alone, straight from the
+ * caller's image (one strided copy below a GiB, from there the chunk pipeline, its staging threads gathering the box's rows);
+ * no host-side crop is allocated.  cuberille_warm_up reserves for `size`, not for dims.
+ * cuberille_set_region: size all zero, or both pointers null, turns the region off (the default: the same bytes as before the
+ *   symbol existed); a box equal to the whole buffer is legal and gives the same bytes as off.  CUBERILLE_ERR_ARGUMENT, the
+ *   setting unchanged, for a negative start or a non-positive size.  The box is checked against the buffer at the extraction,
+ *   where dims is known, by cuberille_region_desc.
+ * cuberille_region_desc (needs no GPU, no context): writes C's description; the single validator.  CUBERILLE_ERR_ARGUMENT for
+ *   a negative start, a non-positive size or a box that leaves the buffer; CUBERILLE_ERR_LIMIT when s + start leaves +-2^30 or
+ *   s + start + size exceeds 2^31 - 1 (the kernels add a start index and a position in `int`).  Region off: *cropped = *img.
+ *   The text of a refusal: cuberille_last_error(NULL), kept per thread like that of a failed cuberille_create.
+ * Refused with CUBERILLE_ERR_ARGUMENT and a message, the context left usable, each deliberately not part of this setting: a slab
+ * that is not the whole volume; the cuberille_step_* calls; cuberille_extract_stream; cuberille_group_extract_host with a
+ * member that has a region; cuberille_set_border together with a region; with project_vertices on, the B-spline interpolator,
+ * a held gradient (cuberille_hold_gradient), CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN and the ADVANCED and LINESEARCH branches.
+ * Region + border is the obvious follow-up and NOT part of this: a box that cuts through the object leaves the surface open at
+ * the box's faces, exactly as the reference leaves it open at the faces of the cropped copy.
+ * While the setting is on, cuberille_debug_bits, cuberille_slice_occupancy and cuberille_slice_counts speak the box's frame
+ * (rows of size[0] voxels, size[1] rows, size[2] slices). */
+int cuberille_set_region(cuberille_ctx *ctx, const int64_t start[3], const int64_t size[3]);
+int cuberille_region_desc(const cuberille_image_desc *img, const int64_t start[3], const int64_t size[3],
+                          cuberille_image_desc *cropped);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

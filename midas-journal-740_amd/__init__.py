@@ -13,5 +13,5 @@ The directory name carries a hyphen, so import it through `__graft_entry__.load_
 """
 from . import _abi, mha, volumes  # noqa: F401
 from .cuberille import (CuberilleImageToMeshFilter, Extractor, ExtractorGroup, Mesh, group_plan, make_desc, make_params,  # noqa: F401
-                        required_halo)
+                        region_desc, required_halo)
 from .mha import MhaStream, Volume, open_stream, read_mha, write_mha  # noqa: F401

@@ -115,6 +115,11 @@ struct cuberille_ctx {
   int padWidth = 0;                      // cuberille_set_border: voxels of constant border implied around every later whole volume
   double padValue = 0.0;                 // ... and their value, which travels like the iso value
   long long padValueInt = 0;
+  bool regionOn = false;                 // cuberille_set_region: every later whole-volume extraction meshes this box of its buffer ...
+  int64_t regionStart[3] = {0, 0, 0};    // ... its first voxel, as a position in the buffer (x, y, z) ...
+  int64_t regionSize[3] = {0, 0, 0};     // ... and its size
+  bool regionApplied = false;            // inside cuberille_extract_host: the box has been uploaded on its own, the description
+                                         // handed on is the box's already
   int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
@@ -225,6 +230,50 @@ void invert3(const double m[9], double inv[9]) {
   inv[8] = (m[0] * m[4] - m[1] * m[3]) / det;
 }
 
+// cuberille_region_desc: the description of the box [start, start + size) of the buffer `img` describes -- what the reference
+// is given after itk::ExtractImageFilter / RegionOfInterestImageFilter with the index kept: the box's size, its start index the
+// buffer's plus the box's place in it, the same origin, spacing and direction.  The single validator of a box: the public symbol,
+// validate(), count_prepare and cuberille_warm_up all come here.  *why: the text of a refusal.
+int region_check(const cuberille_image_desc *img, const int64_t start[3], const int64_t size[3], cuberille_image_desc *out,
+                 const char **why) {
+  const char *dummy;
+  if (!why) why = &dummy;
+  *why = "";
+  if (!img || !out) { *why = "null image description"; return CUBERILLE_ERR_ARGUMENT; }
+  if ((start == nullptr) != (size == nullptr)) { *why = "a region needs both its start and its size"; return CUBERILLE_ERR_ARGUMENT; }
+  for (int i = 0; i < 3; i++)
+    if (img->dims[i] < 1) { *why = "image dimensions must be >= 1"; return CUBERILLE_ERR_ARGUMENT; }
+  if (!size || (size[0] == 0 && size[1] == 0 && size[2] == 0)) { *out = *img; return CUBERILLE_OK; }   // (off: the buffer itself)
+  for (int i = 0; i < 3; i++) {
+    if (start[i] < 0) { *why = "the region (cuberille_set_region) starts at a negative buffer position"; return CUBERILLE_ERR_ARGUMENT; }
+    if (size[i] < 1) { *why = "the region (cuberille_set_region) must hold at least one voxel along every axis"; return CUBERILLE_ERR_ARGUMENT; }
+    if (start[i] > img->dims[i] || size[i] > img->dims[i] - start[i]) {
+      *why = "the region (cuberille_set_region) leaves the buffer";
+      return CUBERILLE_ERR_ARGUMENT;
+    }
+  }
+  cuberille_image_desc d = *img;
+  for (int i = 0; i < 3; i++) {
+    // (a box inside the buffer: its size passes the limit on dims when the buffer's does)
+    if (img->dims[i] > 0x7fffffffLL) { *why = "image dimension exceeds 2^31-1"; return CUBERILLE_ERR_LIMIT; }
+    if (img->index_start[i] < -(1LL << 30) || img->index_start[i] > (1LL << 30)) {
+      *why = "the buffered region's start index must lie within +-2^30";
+      return CUBERILLE_ERR_LIMIT;
+    }
+    const int64_t at = img->index_start[i] + start[i];
+    if (at < -(1LL << 30) || at > (1LL << 30)) { *why = "the region's start index (the buffer's + the box's) must lie within +-2^30"; return CUBERILLE_ERR_LIMIT; }
+    // the kernels add the start index and a position in `int`: the index one past the box's last, and the one before its first
+    if (at + size[i] > 0x7fffffffLL || at - 1 < -0x80000000LL) {
+      *why = "the region's start index + size exceeds 2^31-1";
+      return CUBERILLE_ERR_LIMIT;
+    }
+    d.dims[i] = size[i];
+    d.index_start[i] = at;
+  }
+  *out = d;
+  return CUBERILLE_OK;
+}
+
 int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!img || !vox || !prm) return fail(c, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
@@ -268,6 +317,26 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
   }
   if (hi != lo && !(prm->iso_value > lo - 1.0 && prm->iso_value < hi + 1.0))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
+  if (c->regionOn && !c->regionApplied) {
+    // cuberille_set_region: the box against this buffer, and what would need a second image of the box's shape (coefficients, a
+    // gradient image) or is simply not part of the setting
+    if (c->padWidth)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) together with an implied border (cuberille_set_border) is not offered: the box's faces inside the buffer would need a ring of their own");
+    cuberille_image_desc box;
+    const char *why = "";
+    const int rrc = region_check(img, c->regionStart, c->regionSize, &box, &why);
+    if (rrc) return fail(c, rrc, why);
+    if (prm->project_vertices) {
+      if (c->interp == CUBERILLE_INTERP_BSPLINE)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered with the B-spline interpolator: its coefficient image would be the box's");
+      if (c->holdGradient)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
+      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would be the box's");
+      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the default projection branch only (txx:439-474)");
+    }
+  }
   if (c->padWidth) {
     // cuberille_set_border: the limits above hold for the image with its ring, the ring's value converts like the iso value, and
     // what would need the ring in a second image (coefficients, a gradient image) is not offered
@@ -306,9 +375,31 @@ cuberille_image_desc bordered(const cuberille_ctx *c, const cuberille_image_desc
   return d;
 }
 
+// Is a box in force for the description an entry point was handed?  (Not inside cuberille_extract_host behind its upload of the
+// box: what travels on from there IS the box.)
+bool boxed(const cuberille_ctx *c) { return c->regionOn && !c->regionApplied; }
+
+// The frame the layout, the geometry and every workspace size follow from: the caller's image, with its implied ring
+// (cuberille_set_border) or cut to its box (cuberille_set_region; validate() has passed the box, and refuses the two together).
+cuberille_image_desc framed_desc(const cuberille_ctx *c, const cuberille_image_desc *img) {
+  if (boxed(c)) {
+    cuberille_image_desc d;
+    if (region_check(img, c->regionStart, c->regionSize, &d, nullptr) == CUBERILLE_OK) return d;
+    return *img;
+  }
+  return bordered(c, img);
+}
+
 }  // namespace
 
 extern "C" {
+
+int cuberille_region_desc(const cuberille_image_desc *img, const int64_t start[3], const int64_t size[3], cuberille_image_desc *cropped) {
+  const char *why = "";
+  const int rc = region_check(img, start, size, cropped, &why);
+  if (rc) g_create_error = why;     // (no context to keep the text: cuberille_last_error(NULL), per thread like a failed create's)
+  return rc;
+}
 
 int cuberille_abi_version(void) { return CUBERILLE_ABI_VERSION; }
 
@@ -600,11 +691,13 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
-  const cuberille_image_desc framed = bordered(c, img);
+  const cuberille_image_desc framed = framed_desc(c, img);
   Grid g = whole_grid(&framed, c->tune);
   Geo geo{};
   Params p{};
   resolve(&framed, prm, geo, p);
+  // cuberille_set_region: are the box's rows apart in memory (else the box is a pointer offset into the buffer)?
+  const bool pitched = boxed(c) && (framed.dims[0] != img->dims[0] || framed.dims[1] != img->dims[1]);
   if (c->holdGradient && prm->step_length < 0.0) {
     // cuberille_hold_gradient stands for one filter OBJECT: m_ProjectVertexStepLength is replaced by its default once, at the
     // first Update(), from THAT input's spacing, and stays (txx:82-85) -- like the gradient image, the default step of every
@@ -615,6 +708,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   const bool whole = !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);   // (all-zero slab = whole volume)
   if (!whole && c->padWidth)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
+  if (!whole && c->regionOn)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is a box of a whole volume: not offered on slabs");
   if (!whole) {
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
@@ -648,7 +743,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     g.oz1 = (int)(slab->own_z1 - slab->z_begin);
   }
   g.cz0 = g.oz0 > 0 ? g.oz0 - 1 : 0;
-  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0);
+  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0 || pitched);
   if (sz.nseg > 0x7fffffffULL) return fail(c, CUBERILLE_ERR_LIMIT, "volume too large for one device scan");
 
   // ---- workspace ----------------------------------------------------------------------------------
@@ -670,6 +765,17 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   w.vqueue = (u32 *)optional(c->vqueue, sz.vqueue);
   w.vox = dev_voxels;
   w.pad = c->padWidth; w.padValue = c->padValue; w.padValueInt = c->padValueInt;
+  w.rowPitch = g.nx; w.slicePitch = (long long)g.nx * g.ny;
+  if (boxed(c)) {
+    // the sweep and the walk start at the box's first voxel and step by the BUFFER's pitches; nothing else reads voxels
+    const long long Nx = (long long)img->dims[0], NxNy = Nx * (long long)img->dims[1];
+    w.vox = (const char *)dev_voxels + (size_t)(c->regionStart[0] + c->regionStart[1] * Nx + c->regionStart[2] * NxNy) * pixel_size(img->pixel_type);
+    w.rowPitch = Nx; w.slicePitch = NxNy;
+    w.regionSweep = pitched ? 1 : 0;
+  }
+  // (the walk with a runtime start index in its axis-aligned forms too: where the rows are pitched, and wherever a box left its
+  //  start index away from 0 -- the uploaded box of cuberille_extract_host included)
+  w.region = c->regionOn && whole && (pitched || geo.istart[0] != 0 || geo.istart[1] != 0 || geo.istart[2] != 0) ? 1 : 0;
   w.bits = (u64 *)c->bits.p; w.sliceOcc = (u32 *)((char *)c->occ.p + sizeof(Totals));
   w.prefix = (u32 *)c->prefix.p;
   w.segPre = (u64 *)c->segPre.p; w.blockTot = (u64 *)c->blockTot.p; w.blockBase = (u64 *)c->blockBase.p;
@@ -1262,6 +1368,7 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
 // cuberille_step_begin, and the first half of cuberille_extract_device (the one-wait step with the context as its only rank:
 // a whole volume, so an implied border is at home there while the steps of a driver's ranks refuse it)
 const char *const kNoBorderInSteps = "an implied border (cuberille_set_border) would have to reach across ranks: not offered with the cuberille_step_* calls";
+const char *const kNoRegionInSteps = "a region (cuberille_set_region) is a box of one context's whole volume: not offered with the cuberille_step_* calls";
 int step_begin_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                     const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
   int rc = validate(c, img, dev_voxels, prm);
@@ -1282,12 +1389,14 @@ extern "C" {
 int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                          const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
   if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
+  if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
   return step_begin_impl(c, img, dev_voxels, prm, slab, dev_row, row_bytes);
 }
 
 int cuberille_step_classify(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                             const cuberille_slab *slab, uint64_t **dev_bits, size_t *words_per_slice) {
   if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
+  if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
   int rc = validate(c, img, dev_voxels, prm);
   if (rc) return rc;
   if (!dev_bits || !words_per_slice) return fail(c, CUBERILLE_ERR_ARGUMENT, "null bit-plane pointer");
@@ -1530,17 +1639,37 @@ int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cub
 // Large volumes from pageable host memory: z-chunks of whole slices; chunk i is thresholded on the context's stream while
 // chunk i+1 crosses the link and the host threads (c->poolThreads) stage chunk i+2.  The buffer (img) starts `base` bytes
 // into host_voxels.
+// srcRowBytes / srcSliceBytes (cuberille_set_region): the buffer (img) is a box of the caller's image whose rows and slices
+// lie that far apart in host memory, `base` its first voxel -- the staging threads gather the box's rows of each chunk straight
+// from the caller's image, no host-side crop exists; 0: the buffer is contiguous there.
+// chunkBytes: 0 = kUploadChunk (Tuning::upload_chunk_kib: smaller chunks, for tests of the pipeline on small volumes).
 constexpr size_t kUploadChunk = 32u << 20;
 int count_host_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels, size_t base,
-                       const cuberille_params *prm, const cuberille_slab *slab) {
-  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+                       const cuberille_params *prm, const cuberille_slab *slab, size_t srcRowBytes = 0, size_t srcSliceBytes = 0,
+                       size_t chunkBytes = 0) {
+  const size_t rowBytes = (size_t)img->dims[0] * pixel_size(img->pixel_type), ny = (size_t)img->dims[1];
+  const size_t sliceBytes = rowBytes * ny;
   const size_t bytes = sliceBytes * (size_t)img->dims[2];
-  const size_t chunk = kUploadChunk / sliceBytes * sliceBytes;
+  size_t want = kUploadChunk;
+  if (chunkBytes && chunkBytes < kUploadChunk) want = chunkBytes < sliceBytes ? sliceBytes : chunkBytes;   // (the test switch: a slice at least)
+  const size_t slices = want / sliceBytes;
+  if (slices < 1) return fail(c, CUBERILLE_ERR_LIMIT, "a slice of the image does not fit a chunk of the upload pipeline");   // (the callers' rule)
+  const size_t chunk = slices * sliceBytes;
   const char *src = (const char *)host_voxels + base;
   StagePool pool(bytes, chunk, [&](size_t i, size_t a, size_t b) {
-    std::memcpy((char *)c->stage[i & 1] + a, src + i * chunk + a, b - a);
+    char *dst = (char *)c->stage[i & 1];
+    if (!srcRowBytes) {
+      std::memcpy(dst + a, src + i * chunk + a, b - a);
+      return;
+    }
+    for (size_t off = i * chunk + a, end = i * chunk + b; off < end;) {     // bytes [off, end) of the box, row piece by row piece
+      const size_t r = off / rowBytes, o = off - r * rowBytes, n = rowBytes - o < end - off ? rowBytes - o : end - off;
+      const size_t z = r / ny, y = r - z * ny;
+      std::memcpy(dst + (off - i * chunk), src + z * srcSliceBytes + y * srcRowBytes + o, n);
+      off += n;
+    }
   }, c->poolThreads);
-  return extract_chunked(c, img, prm, slab, kUploadChunk, kUploadChunk / sliceBytes, "overlapped upload: ",
+  return extract_chunked(c, img, prm, slab, kUploadChunk, slices, "overlapped upload: ",
                          [&](size_t i, void *, size_t, size_t) {
                            pool.release(i);
                            pool.wait(i);
@@ -1561,23 +1690,51 @@ int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, co
   int rc = validate(c, img, host_voxels, prm);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
+  // cuberille_set_region: only the box crosses the link, straight from the caller's image -- the device copy is the box,
+  // contiguous, and from here on the image IS the box (its description cuberille_region_desc's; validate() has passed it)
+  const bool box = boxed(c);
+  const cuberille_image_desc whole = *img, cut = framed_desc(c, img);
+  if (box) img = &cut;
+  struct Applied {
+    cuberille_ctx *c; bool on;
+    Applied(cuberille_ctx *ctx, bool b) : c(ctx), on(b) { if (on) c->regionApplied = true; }
+    ~Applied() { if (on) c->regionApplied = false; }
+  } applied(c, box);
+  const size_t pix = pixel_size(img->pixel_type);
+  const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pix;
   const size_t bytes = sliceBytes * (size_t)img->dims[2];
+  const size_t srcRow = (size_t)whole.dims[0] * pix, srcSlice = srcRow * (size_t)whole.dims[1];
+  const size_t base = box ? (size_t)c->regionStart[0] * pix + (size_t)c->regionStart[1] * srcRow + (size_t)c->regionStart[2] * srcSlice : 0;
+  const bool rowsApart = box && (img->dims[0] != whole.dims[0] || img->dims[1] != whole.dims[1]);
   HIP_TRY(c, c->voxOwn.reserve(bytes));
   // below a GiB: one plain copy (the runtime stages pageable memory itself, at link rate once the copy is large; the
   // chunk pipeline below needs some tens of chunks to amortise its start -- measured 34 ms against 11 ms at 512^3 f32);
   // the extraction follows on the stream
-  if (!upload_in_chunks(sliceBytes, bytes)) {
-    HIP_TRY(c, hipMemcpyAsync(c->voxOwn.p, host_voxels, bytes, hipMemcpyHostToDevice, c->stream));
+  const bool chunks = c->tune.upload_chunk_kib > 0 ? sliceBytes <= kUploadChunk : upload_in_chunks(sliceBytes, bytes);
+  if (!chunks) {
+    if (rowsApart) {
+      // (one strided copy: the box's rows from the caller's image into the contiguous device buffer)
+      hipMemcpy3DParms cp{};
+      cp.srcPtr = make_hipPitchedPtr(const_cast<char *>((const char *)host_voxels + base), srcRow, srcRow, (size_t)whole.dims[1]);
+      cp.dstPtr = make_hipPitchedPtr(c->voxOwn.p, (size_t)img->dims[0] * pix, (size_t)img->dims[0] * pix, (size_t)img->dims[1]);
+      cp.extent = make_hipExtent((size_t)img->dims[0] * pix, (size_t)img->dims[1], (size_t)img->dims[2]);
+      cp.kind = hipMemcpyHostToDevice;
+      HIP_TRY(c, hipMemcpy3DAsync(&cp, c->stream));
+    } else {
+      HIP_TRY(c, hipMemcpyAsync(c->voxOwn.p, (const char *)host_voxels + base, bytes, hipMemcpyHostToDevice, c->stream));
+    }
     return cuberille_extract_device(c, img, c->voxOwn.p, prm, nullptr, res);
   }
-  rc = count_host_chunked(c, img, host_voxels, 0, prm, nullptr);
+  rc = count_host_chunked(c, img, host_voxels, base, prm, nullptr, rowsApart ? srcRow : 0, rowsApart ? srcSlice : 0,
+                          (size_t)(c->tune.upload_chunk_kib > 0 ? c->tune.upload_chunk_kib : 0) << 10);
   return rc ? rc : cuberille_emit(c, 0, res);
 }
 
 int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, cuberille_chunk_source source, void *user,
                              const cuberille_params *prm, cuberille_result *res) {
   if (c && !source) return fail(c, CUBERILLE_ERR_ARGUMENT, "null chunk source");
+  if (c && c->regionOn)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered with cuberille_extract_stream: the source produces whole slices");
   int rc = validate(c, img, (const void *)source, prm);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1616,10 +1773,13 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     cuberille_params p = dflt;
     p.iso_value = 100.0;
     cuberille_result r{};
+    const bool applied = c->regionApplied;
+    c->regionApplied = true;                 // (cuberille_set_region speaks of the caller's volumes, not of this one)
     for (int i = 0; i < 2; i++) {            // twice: the second one takes the blind launches of the one-wait step
       const int rc = cuberille_extract_host(c, &d, tiny, &p, &r);
-      if (rc) return rc;
+      if (rc) { c->regionApplied = applied; return rc; }
     }
+    c->regionApplied = applied;
     // the runtime sets up its staging for copies from and to PAGEABLE memory at the first copy that needs it (measured
     // through the reference's driver: 7.2 ms inside the first hipMemcpyAsync of nucleon.mha's 69 KB, profiles/
     // r4_cold_update.log): one round trip of a size that takes its staging buffers, one of a size it pins in place
@@ -1647,15 +1807,25 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
   // the buffers whose size follows from the description (count_prepare, emit_points_phase, cuberille_extract_host); a
   // reservation that fails here is asked for again, and reported, by the extraction
   // (cuberille_set_border: the workspace of the image with its ring, the voxel buffer of the image as it is)
-  const cuberille_image_desc framed = bordered(c, img);
+  // (cuberille_set_region: the workspace AND the voxel buffer of the box -- cuberille_extract_host uploads nothing else)
+  if (boxed(c)) {
+    if (c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) together with an implied border (cuberille_set_border) is not offered");
+    cuberille_image_desc box;
+    const char *why = "";
+    const int rrc = region_check(img, c->regionStart, c->regionSize, &box, &why);
+    if (rrc) return fail(c, rrc, why);
+  }
+  const cuberille_image_desc framed = framed_desc(c, img);
   for (int i = 0; i < 3; i++) {     // (the limits of validate() for the image with its ring)
     if (framed.dims[i] > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_LIMIT, "image dimension with its border exceeds 2^31-1");
     if (c->padWidth && framed.index_start[i] < -(1LL << 30))
       return fail(c, CUBERILLE_ERR_LIMIT, "the bordered region's start index must lie within +-2^30");
   }
   const Grid g = whole_grid(&framed, c->tune);
-  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0);
-  const size_t bytes = (size_t)img->dims[0] * (size_t)img->dims[1] * (size_t)img->dims[2] * pixel_size(img->pixel_type);
+  const bool pitched = boxed(c) && (framed.dims[0] != img->dims[0] || framed.dims[1] != img->dims[1]);
+  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0 || pitched);
+  const cuberille_image_desc *held = boxed(c) ? &framed : img;     // the image a host-resident extraction keeps on the device
+  const size_t bytes = (size_t)held->dims[0] * (size_t)held->dims[1] * (size_t)held->dims[2] * pixel_size(img->pixel_type);
   const std::pair<DevBuf *, size_t> want[] = {{&c->voxOwn, bytes}, {&c->bits, sz.bits}, {&c->occ, sz.occ}, {&c->prefix, sz.prefix},
                                               {&c->segPre, sz.segPre}, {&c->blockTot, sz.blockTot}, {&c->blockBase, sz.blockBase},
                                               {&c->flatBits, sz.flatBits}, {&c->vqueue, sz.vqueue}, {&c->cmap, cmap_bytes(g, c->tune)}};
@@ -1712,7 +1882,7 @@ int cuberille_slab_info(cuberille_ctx *c, cuberille_slab_status *out) {
 static bool set_opt(Tuning &t, const char *name, long long v) {
 #define OPT(field) if (!std::strcmp(name, #field)) { t.field = (int)v; return true; }
   OPT(no_cmap) OPT(no_heads) OPT(no_vqueue) OPT(no_stream_classify) OPT(classify_variant) OPT(classify_grid)
-  OPT(points_variant) OPT(points_no_split) OPT(count_variant) OPT(cmap_linear) OPT(proj_chunk) OPT(proj_waves) OPT(proj_refill) OPT(proj_xcd) OPT(proj_literal) OPT(stage_timing) OPT(classify_keep_tail) OPT(proj_chunk64_below) OPT(points_split) OPT(count_no_fold) OPT(proj_short) OPT(proj_ident)
+  OPT(points_variant) OPT(points_no_split) OPT(count_variant) OPT(cmap_linear) OPT(proj_chunk) OPT(proj_waves) OPT(proj_refill) OPT(proj_xcd) OPT(proj_literal) OPT(stage_timing) OPT(classify_keep_tail) OPT(proj_chunk64_below) OPT(points_split) OPT(count_no_fold) OPT(proj_short) OPT(proj_ident) OPT(upload_chunk_kib)
 #undef OPT
   return false;
 }
@@ -1888,6 +2058,26 @@ int cuberille_set_border(cuberille_ctx *c, int pad_width, double pad_value, int6
   c->padWidth = pad_width;
   c->padValue = pad_value;
   c->padValueInt = (long long)pad_value_int;
+  return CUBERILLE_OK;
+}
+
+int cuberille_set_region(cuberille_ctx *c, const int64_t start[3], const int64_t size[3]) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  if ((start == nullptr) != (size == nullptr)) return fail(c, CUBERILLE_ERR_ARGUMENT, "a region needs both its start and its size");
+  if (!size || (size[0] == 0 && size[1] == 0 && size[2] == 0)) {
+    c->regionOn = false;
+    for (int i = 0; i < 3; i++) c->regionStart[i] = c->regionSize[i] = 0;
+    return CUBERILLE_OK;
+  }
+  // (what can be said without the buffer's dims; the rest at the extraction, by the same validator)
+  cuberille_image_desc any{}, box;
+  for (int i = 0; i < 3; i++) any.dims[i] = 0x7fffffffLL;
+  const char *why = "";
+  const int rc = region_check(&any, start, size, &box, &why);
+  if (rc == CUBERILLE_ERR_ARGUMENT) return fail(c, rc, why);
+  c->regionOn = true;
+  for (int i = 0; i < 3; i++) { c->regionStart[i] = start[i]; c->regionSize[i] = size[i]; }
   return CUBERILLE_OK;
 }
 
@@ -2152,6 +2342,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
   if (group_plan_impl(img, prm, n, b.data(), &used, &why) != CUBERILLE_OK) return gfail(g, CUBERILLE_ERR_ARGUMENT, why);
   for (int i = 0; i < n; i++) {
     const cuberille_ctx *c = g->ctx[(size_t)i];
+    if (c->regionOn)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has a region set (cuberille_set_region): "
+                                              "a box of one context's whole volume, not offered in a group");
     if (c->padWidth)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has an implied border set (cuberille_set_border): "
                                               "the ring would have to reach across slabs, not offered in a group");

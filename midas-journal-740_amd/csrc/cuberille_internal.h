@@ -143,6 +143,13 @@ struct Workspace {     // device pointers valid for one count/emit pair
   int pad;
   double padValue;
   long long padValueInt;
+  // cuberille_set_region: the Grid (and the Geo) describe a BOX of the caller's buffer and `vox` points at the box's first
+  // voxel; its rows and slices lie rowPitch / slicePitch voxels apart (the buffer's Nx and Nx * Ny; the box's own nx and
+  // nx * ny where the box is contiguous in memory or was uploaded on its own).  region: the walk takes the pitches and a
+  // runtime start index in all three geometry forms; regionSweep: the rows are not contiguous, the pitched sweep reads
+  // them.  Read by the sweep and the walk only, every other kernel works on the bit volume.
+  int region, regionSweep;
+  long long rowPitch, slicePitch;
 };
 
 // Development switches, set per context through cuberille_debug_set_option (never read from the environment).
@@ -173,6 +180,8 @@ struct Tuning {
   int proj_short = -1;        // the launch shapes of SHORT walks (1) or of long ones (0); -1: by the previous extraction's passes per vertex
   int count_no_fold = 0;      // 1: the block scan always as a launch of its own (A/B of the scan folded into small count launches)
   int stage_timing = 0;       // 1: events between the stages too (cuberille_result::ms_classify ... ms_emit_cells)
+  int upload_chunk_kib = 0;   // > 0: cuberille_extract_host takes the chunk pipeline whatever the size, in chunks of that many KiB
+                              // (at least a slice each, at most the staging slot) -- tests of the chunked routes on small volumes
 };
 
 struct Params {

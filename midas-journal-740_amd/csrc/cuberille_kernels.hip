@@ -574,6 +574,167 @@ __global__ __launch_bounds__(256) void k_classify_pad_span_rows(const T *__restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The pitched sweep (cuberille_set_region): the bit volume of an nx x ny x nz BOX of a larger x-fastest buffer, in the layout
+// every later kernel expects of an nx x ny x nz image, from the caller's buffer as it is: no cropped copy of the voxels exists
+// anywhere.  `box` points at the box's first voxel; row y of slice z of the box starts at box + z * slicePitch + y * rowPitch
+// (in voxels: the buffer's Nx and Nx * Ny) and is aligned to nothing but the pixel type.
+// ---------------------------------------------------------------------------------------------
+
+// Any size: one wave per output word; lane l tests voxel x = 64k + l of its row, the ballot is the word.
+// Words [t0, t1) of the box's bit volume.
+template <class T>
+__global__ __launch_bounds__(256) void k_classify_region_words(const T *__restrict__ box, u64 *__restrict__ bits, u64 t0, u64 t1,
+                                                               int nx, int ny, int W, long long rowPitch, long long slicePitch,
+                                                               double isoD, long long isoI, u32 *__restrict__ sliceOcc) {
+  const T iso = iso_as<T>(isoD, isoI);
+  const int lane = threadIdx.x & 63;
+  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+  for (u64 t = t0 + wave; t < t1; t += nwaves) {
+    const u64 row = t / (u64)W;
+    const int k = (int)(t - row * (u64)W);
+    const u64 z = row / (u64)ny;
+    const u64 y = row - z * (u64)ny;
+    const int x = k * 64 + lane;
+    bool in = false;
+    if (x < nx) in = !(box[(long long)z * slicePitch + (long long)y * rowPitch + x] < iso);
+    const u64 word = __ballot(in);
+    if (lane == 0) {
+      bits[t] = word;
+      if (word) sliceOcc[z] = 1u;              // benign race: all store 1
+    }
+  }
+}
+
+// Large boxes: k_classify_span_rows with the rows a pitch apart.  A workgroup owns SPAN_WORDS consecutive words of the BOX's
+// bit volume, a range of (row, word) pairs; the voxels behind them are no longer one stream but one stream per row.  Every
+// row's stream is read as that kernel reads its one: 16-byte nontemporal vectors from the 16-byte boundary at or below the
+// row's first voxel to the one that holds its last (the first and the last vector of a row may reach up to 15 bytes outside
+// the row -- the same 16-byte granule as voxels of the box, so the loads cannot fault, and those bits are never used; no
+// vector lies wholly outside the box's rows).  The streams are staged back to back in LDS: the span's first row takes the vectors
+// it has, every further row a slot of VR vectors -- what a row can touch at its worst alignment -- so that a lane finds its
+// row and its vector with one division.  Then every thread cuts two row words out of the stage (two LDS words,
+// funnel-shifted, the row's last word masked to the voxels it has) and the span leaves as 16-byte write-through stores,
+// occupancy folded in.  row0: first row of the launch's range (bits and the spans start at its first word).
+template <class T>
+__global__ __launch_bounds__(256) void k_classify_region_span_rows(const T *__restrict__ box, u64 *__restrict__ bits, u64 nspans,
+                                                                   u64 nwordsAll, u32 row0, int nx, int W, u32 ny,
+                                                                   long long rowPitch, long long slicePitch, double isoD,
+                                                                   long long isoI, u32 *__restrict__ sliceOcc) {
+  constexpr int U = 4;
+  constexpr int VPL = 16 / sizeof(T);
+  constexpr int LPW = 64 / VPL;
+  // bits of the stage: the voxels behind the span's words (64 a word at most) + under 2 * VPL a row for the skew to the 16-byte
+  // boundaries (a span has SPAN_WORDS rows at most), + the trips' rounding to whole 1 KiB chunks, + the word a funnel shift
+  // looks ahead
+  constexpr int STAGE = SPAN_WORDS + SPAN_WORDS * 2 * VPL / 64 + VPL + 2;
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
+  const T iso = iso_as<T>(isoD, isoI);
+  const int lane = threadIdx.x & 63;
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane % LPW;
+  const bool last = sub == LPW - 1;
+  const u32 qStep = 512u / (u32)W, rStep = 512u % (u32)W;
+  const u32 VR = (u32)(((u64)nx * sizeof(T) + 15 - sizeof(T)) / 16 + 1);     // vectors a whole row touches at most
+  for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+    // (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic)
+    const u64 w0 = sp * (u64)SPAN_WORDS;
+    const u64 left = nwordsAll - w0;
+    const u32 nw = left < (u64)SPAN_WORDS ? (u32)left : (u32)SPAN_WORDS;
+    const u32 r0 = row0 + (u32)w0 / (u32)W;
+    const u32 k0 = (u32)w0 % (u32)W;
+    const u32 wl = (u32)w0 + nw - 1, r1 = row0 + wl / (u32)W;
+    const u32 k1 = wl % (u32)W;
+    const u32 xaFirst = k0 * 64u;                                             // the first row from word k0 on ...
+    const u32 xbLast = (k1 + 1) * 64u < (u32)nx ? (k1 + 1) * 64u : (u32)nx;   // ... the last one up to word k1
+    // the stream of row rw (a row of the span): the address of the vector that holds its first voxel, how many vectors it
+    // has, the voxels of that first vector that lie before the row's, and the row's first voxel
+    auto stream = [&](u32 rw, uintptr_t &first, u32 &nvec, u32 &skew, u32 &xa) {
+      const u32 z = rw / ny, y = rw - z * ny;
+      const T *row = box + (long long)z * slicePitch + (long long)y * rowPitch;
+      xa = rw == r0 ? xaFirst : 0u;
+      const u32 xb = rw == r1 ? xbLast : (u32)nx;
+      const uintptr_t a = (uintptr_t)(row + xa), e = (uintptr_t)(row + xb) - 1;
+      first = a & ~(uintptr_t)15;
+      nvec = (u32)((e >> 4) - (a >> 4)) + 1u;
+      skew = (u32)((a & 15) / sizeof(T));
+    };
+    uintptr_t f0, fl;
+    u32 nvec0, nvecL, sk, xx;
+    stream(r0, f0, nvec0, sk, xx);
+    stream(r1, fl, nvecL, sk, xx);
+    // vectors of the whole span, and the first vector of row rw's slot
+    const u32 nvTot = r1 == r0 ? nvec0 : nvec0 + (r1 - r0 - 1) * VR + nvecL;
+    auto slot = [&](u32 rw) -> u32 { return rw == r0 ? 0u : nvec0 + (rw - r0 - 1) * VR; };
+    const u32 n1k = (nvTot + 63) / 64;                     // 1 KiB chunks of the staged streams
+#pragma unroll 1
+    for (u32 c = (u32)wib * U; c < n1k; c += 4 * U) {      // the waves take the 4 KiB trips in turn
+      Vec16<T> r[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        u32 v = (c + u) * 64 + lane;
+        v = v < nvTot ? v : nvTot - 1;
+        u32 rw = r0, i = v;
+        if (v >= nvec0) {
+          const u32 t = v - nvec0, q = t / VR;
+          rw = r0 + 1 + q;
+          i = t - q * VR;
+        }
+        uintptr_t first;
+        u32 nvec, skew, xa;
+        stream(rw, first, nvec, skew, xa);
+        i = i < nvec ? i : nvec - 1;                       // (a slot's spare vectors repeat the row's last: never read back)
+        const uint4 *src = reinterpret_cast<const uint4 *>(first + (uintptr_t)i * 16);
+        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
+        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const u32 m = inside_bits<T>(r[u], iso);
+        const u64 word = group_or<LPW>((u64)m << (sub * VPL));
+        const u32 at = (c + u) * VPL + lane / LPW;
+        if (last && at < (u32)STAGE) stage[at] = word;
+      }
+    }
+    __syncthreads();
+    auto rsrc = __builtin_amdgcn_make_buffer_rsrc(bits + w0, 0, (int)(nw * 8u), 0x00020000);
+    auto cut = [&](u32 rw, u32 kk, bool live) -> u64 {
+      if (!live) return 0ull;
+      uintptr_t first;
+      u32 nvec, skew, xa;
+      stream(rw, first, nvec, skew, xa);
+      const u32 rel = slot(rw) * VPL + skew + kk * 64u - xa;                  // bit of the stage the word starts at
+      const u32 j = rel >> 6, sh = rel & 63u;
+      const u64 lo = stage[j], hi = stage[j + 1];
+      u64 word = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
+      const int n = nx - (int)kk * 64;
+      if (n < 64) word &= lowmask(n);
+      return word;
+    };
+    auto mark = [&](u64 word, u32 rw) {
+      if (word) sliceOcc[rw / ny] = 1u;                    // benign race: all store 1
+    };
+    u32 i = threadIdx.x * 2;
+    u32 row = r0 + (k0 + i) / (u32)W;
+    u32 k = (k0 + i) % (u32)W;
+    for (; i < (u32)SPAN_WORDS; i += 512) {
+      const u32 rowB = k + 1 < (u32)W ? row : row + 1;
+      const u32 kB = k + 1 < (u32)W ? k + 1 : 0;
+      const u64 a = cut(row, k, i < nw), b = cut(rowB, kB, i + 1 < nw);
+      u32x4 v;
+      v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, i * 8, 0, 16);          // aux 16 = sc1: write-through; past nw: dropped
+      mark(a, row);
+      mark(b, rowB);
+      k += rStep; row += qStep;
+      if (k >= (u32)W) { k -= (u32)W; row++; }
+    }
+    __syncthreads();
+  }
+}
+
 // Per-slice occupancy (does the slice hold any inside voxel?) from the packed bits: one block per
 // slice, stops at the first non-zero word it sees.
 __global__ __launch_bounds__(256) void k_occupancy(const u64 *__restrict__ bits, size_t wordsPerSlice,
@@ -2455,7 +2616,7 @@ __global__ __launch_bounds__(256) void k_emit_cells(EmitArgs a, Grid g, size_t n
 // Every arithmetic step mirrors the ITK 3.x contract I3..I9 in the same
 // operation order as the oracle, so the float coordinates come out bit-identical.
 // ---------------------------------------------------------------------------------------------
-template <class T, bool PAD = false>
+template <class T, bool PAD = false, bool REGION = false>
 struct Sampler {
   const T *vox;
   int nx, ny, nzb;
@@ -2480,7 +2641,7 @@ struct Sampler {
 // the padded frame; vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels.  Voxel p is vox[p - 1] where
 // 1 <= p <= n - 2 on every axis and `ring` elsewhere.
 template <class T>
-struct Sampler<T, true> {
+struct Sampler<T, true, false> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
@@ -2498,6 +2659,26 @@ struct Sampler<T, true> {
   __device__ __forceinline__ bool on_ring(int p, int n) const { return p == 0 || p == n - 1; }
   __device__ __forceinline__ int in_buffer(int p, int n) const { return min(max(p - 1, 0), n - 3); }
   __device__ __forceinline__ T at(int x, int y, int zg) const { return at_buffer(x, y, zlocal(zg)); }
+  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
+    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
+    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
+    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
+    return at(x, y, zg);
+  }
+};
+
+// cuberille_set_region: the image the walk sees is a box of a larger buffer.  nx, ny, nzb are the BOX's dims (a whole volume:
+// zglob0 = 0, gnz = nzb), every position is one of the box's frame and every clamp happens at the box's faces, as it would on a
+// cropped copy; vox points at the box's first voxel and rows / slices lie rowS / sliceS voxels apart -- the buffer's Nx and
+// Nx * Ny.  Nothing outside the box is ever addressed.
+template <class T>
+struct Sampler<T, false, true> {
+  const T *vox;
+  int nx, ny, nzb;
+  int zglob0, gnz;
+  long long rowS, sliceS;
+  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
+  __device__ __forceinline__ T at(int x, int y, int zg) const { return vox[zlocal(zg) * sliceS + y * rowS + x]; }
   __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
     x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
     y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
@@ -2597,8 +2778,8 @@ __device__ __forceinline__ void gradient_from_taps(const Geo &geo, bool dirIdent
   }
 }
 
-template <class T, bool PAD = false>
-__device__ __forceinline__ void gradient_at(const Sampler<T, PAD> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
+template <class T, bool PAD = false, bool REGION = false>
+__device__ __forceinline__ void gradient_at(const Sampler<T, PAD, REGION> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
                                             float f0, float out[3]) {
   float fm[3], fp[3];
 #pragma unroll
@@ -2663,8 +2844,9 @@ __device__ __forceinline__ void cell_gradients(const Geo &geo, bool dirIdentity,
 // inside the caller's buffer -- one voxel further in on every side -- and the 12 row segments are read through a base pointer
 // moved back by one voxel per axis, with the buffer's own row and slice pitch.  Only cells that touch the implied ring
 // take the clamped forms, whose taps go through Sampler::at_buffer.
-template <class T, bool LITERAL, bool PAD = false>
-__device__ __forceinline__ void gather_cell(const Sampler<T, PAD> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
+// REGION (cuberille_set_region): positions are those of the box, whose rows and slices lie the BUFFER's pitch apart in memory.
+template <class T, bool LITERAL, bool PAD = false, bool REGION = false>
+__device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
                                             float G[8][3], typename SiteValue<T>::type Vd[8]) {
   const bool unit = c.lo[0] + 1 == c.hi[0] && c.lo[1] + 1 == c.hi[1] && c.lo[2] + 1 == c.hi[2];
   const int zl = c.lo[2] - s.zglob0;              // buffer slice of the cell's lower z
@@ -2679,8 +2861,15 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD> &s, const Geo 
     // the cell and its ring of neighbours lie inside the buffer: nothing is clamped, so the 12 row segments are
     // the cell's own address plus wave-uniform strides, and the x neighbours are immediate offsets
     const int pnx = s.nx - 2 * IN, pny = s.ny - 2 * IN;      // row and slice pitch of the buffer in memory
-    const T *base = s.vox + ((size_t)(zl - IN) * pny + (c.lo[1] - IN)) * pnx + (c.lo[0] - IN);
-    const ptrdiff_t rowS = (ptrdiff_t)pnx, sliceS = (ptrdiff_t)pny * pnx;
+    const T *base;
+    ptrdiff_t rowS, sliceS;
+    if constexpr (REGION) {
+      rowS = (ptrdiff_t)s.rowS; sliceS = (ptrdiff_t)s.sliceS;
+      base = s.vox + zl * sliceS + c.lo[1] * rowS + c.lo[0];
+    } else {
+      base = s.vox + ((size_t)(zl - IN) * pny + (c.lo[1] - IN)) * pnx + (c.lo[0] - IN);
+      rowS = (ptrdiff_t)pnx; sliceS = (ptrdiff_t)pny * pnx;
+    }
     T V[4][4][4];
 #pragma unroll
     for (int zi = 0; zi < 4; zi++)
@@ -2730,7 +2919,9 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD> &s, const Geo 
             }
           }
         } else {
-        const T *row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
+        const T *row;
+        if constexpr (REGION) row = s.vox + zs[zi] * s.sliceS + ys[yi] * s.rowS;
+        else row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
         if (zin && yin) {
 #pragma unroll
           for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = row[xs[xi]];
@@ -2777,11 +2968,17 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD> &s, const Geo 
 // PAD (cuberille_set_border, MODE 0, a whole volume): `g` and `geo` describe the padded image, `vox` is the caller's buffer and
 // the ring's value arrives as padD / padI (the pair the iso value travels as); GEOM 1 and 2 then stand for a caller's image
 // whose region starts at index 0, i.e. a padded one that starts at -1.  The other instantiations never read the two arguments.
-template <class T, int MODE, int GEOM, bool PAD = false>
+// REGION (cuberille_set_region, MODE 0, a whole volume): `g` and `geo` describe the box, `vox` points at the box's first voxel
+// and its rows and slices lie rowPitch / slicePitch voxels apart (the buffer's Nx and Nx * Ny).  GEOM 1 and 2 then speak of the
+// MATRICES alone: the start index of the box -- the input's plus the box's place in the buffer, rarely 0 -- stays the three runtime
+// scalars geo.istart in every form (it enters only through integer clamps in make_cell), so that a box of an axis-aligned image keeps
+// the axis-aligned walk.  The other instantiations never read the two pitches.
+template <class T, int MODE, int GEOM, bool PAD = false, bool REGION = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentityArg,
                                                  float *__restrict__ points, u64 nPoints, u64 nGhost, u64 chunk,
                                                  int REFILL, int xcdRemap, int forceLiteral, Totals *__restrict__ tot,
-                                                 u32 *__restrict__ escList, u32 escCap, int dyn, double padD, long long padI) {
+                                                 u32 *__restrict__ escList, u32 escCap, int dyn, double padD, long long padI,
+                                                 long long rowPitch, long long slicePitch) {
   const int lane = threadIdx.x & 63;
   if (dyn) {
     if (!tot->go) return;
@@ -2816,8 +3013,9 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   if (wave >= nBatches) return;
   u64 next = 0;                                   // wave-uniform cursor
   const u64 end = ((nBatches - wave + NW - 1) / NW) << lgChunk;
-  Sampler<T, PAD> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  Sampler<T, PAD, REGION> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
   if constexpr (PAD) s.ring = iso_as<T>(padD, padI);
+  if constexpr (REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
   const double iso = (double)iso_as<T>(prm.iso, prm.isoInt);
   unsigned myIters = 0;
@@ -2847,7 +3045,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       geo.dir[i] = (i % 4 == 0) ? 1.0 : 0.0;
       if (IDENT || i % 4 != 0) geo.p2i[i] = (i % 4 == 0) ? 1.0 : 0.0;
     }
-    geo.istart[0] = geo.istart[1] = geo.istart[2] = PAD ? -1 : 0;
+    if constexpr (!REGION) geo.istart[0] = geo.istart[1] = geo.istart[2] = PAD ? -1 : 0;
     unitP2I = IDENT;
   }
   const int dirIdentity = GEOM ? 1 : dirIdentityArg;
@@ -2893,7 +3091,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       }
       if (!escaped) {
       if (c.bc[0] != kc[0] || c.bc[1] != kc[1] || c.bc[2] != kc[2]) {
-        gather_cell<T, false, PAD>(s, geo, dirIdentity != 0, c, G, Vd);
+        gather_cell<T, false, PAD, REGION>(s, geo, dirIdentity != 0, c, G, Vd);
 #pragma unroll
         for (int k = 0; k < 3; k++) kc[k] = c.bc[k];
         // all 32 cached numbers finite?  x*0 accumulates to 0 for finite x, to NaN for an infinity or a NaN
@@ -2906,7 +3104,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
           for (int k = 0; k < 3; k++) tf = __builtin_fmaf(G[counter][k], 0.0f, tf);
         }
         cellFinite = (tf == 0.0f) && (td == 0.0);
-        if (!cellFinite) gather_cell<T, true, PAD>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
+        if (!cellFinite) gather_cell<T, true, PAD, REGION>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
 #pragma unroll
         for (int counter = 0; counter < 8; counter++)
 #pragma unroll
@@ -3683,6 +3881,31 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       }
       return hipGetLastError();
     });
+  if (wAll.regionSweep)
+    return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+      typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+      // cuberille_set_region: `g` is the box's layout, wAll.vox its first voxel in the caller's buffer, z0 / z1 slices of the box
+      const u64 wps = (u64)g.ny * g.W, t0 = (u64)z0 * wps, t1 = (u64)z1 * wps;
+      const T *box = (const T *)wAll.vox;
+      // the staged spans under the rule of the unpadded sweep: a box of 256 MiB and more, fewer than 2^32 words
+      const bool spans = tn.classify_variant != 1 && !tn.no_stream_classify && ((uintptr_t)box % sizeof(T)) == 0 &&
+                         ((u64)g.nx * (u64)g.ny * (u64)g.nzb * sizeof(T) >= (256ull << 20) || tn.classify_variant == 2) &&
+                         (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
+      if (spans) {
+        const u64 nwordsAll = t1 - t0;
+        const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
+        const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;     // two workgroups per CU, whole rounds
+        const u64 rounds = (nspans + want - 1) / want;
+        const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
+        hipLaunchKernelGGL((k_classify_region_span_rows<T>), dim3(blocks), dim3(256), 0, s, box, wAll.bits + t0, nspans, nwordsAll,
+                           (u32)((u64)z0 * (u64)g.ny), g.nx, g.W, (u32)g.ny, wAll.rowPitch, wAll.slicePitch, iso, isoI, wAll.sliceOcc);
+      } else {
+        const unsigned blocks = grid_for((t1 - t0) * 64, 256, 8192);
+        hipLaunchKernelGGL((k_classify_region_words<T>), dim3(blocks), dim3(256), 0, s, box, wAll.bits, t0, t1, g.nx, g.ny, g.W,
+                           wAll.rowPitch, wAll.slicePitch, iso, isoI, wAll.sliceOcc);
+      }
+      return hipGetLastError();
+    });
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
     Workspace w = wAll;
@@ -3777,7 +4000,7 @@ hipError_t launch_occupancy(int pixel_type, const Workspace &w, const Grid &g, c
   size_t elem = 1;
   (void)by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t { elem = sizeof(*tag); return hipSuccess; });
   const bool aligned = g.nx % 64 == 0 && ((uintptr_t)w.vox % 16) == 0;
-  if (w.pad) return hipSuccess;                                      // (both padded sweeps mark the occupancy themselves)
+  if (w.pad || w.regionSweep) return hipSuccess;                     // (the padded and the pitched sweeps mark the occupancy themselves)
   if (ragged_span_path(w, g, elem, tn)) return hipSuccess;           // (that sweep marks the occupancy itself)
   if ((aligned && occupancy_shift(g) < 0) || ragged_stream_path(w, g, elem, tn))
     hipLaunchKernelGGL(k_occupancy, dim3(g.nzb), dim3(256), 0, s, w.bits, (size_t)g.ny * g.W, w.sliceOcc);
@@ -4117,18 +4340,20 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     // the kernel's form by the geometry: 2 identity matrices and a region at index 0; 1 identity direction, any spacing (the
     // inverse of a diagonal matrix by cofactors has exact zeros off its diagonal); 0 anything else
     // (cuberille_set_border: the padded region starts one index below the caller's; the padded kernels' forms 1 and 2 hold -1)
+    // (cuberille_set_region: the region kernels take the start index at run time in every form: the matrices alone decide)
     const int at0 = w.pad ? -1 : 0;
-    bool diag = dirIdentity != 0 && geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0 && tn.proj_ident != 0;
+    bool diag = dirIdentity != 0 && (w.region || (geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0)) && tn.proj_ident != 0;
     bool unit = diag;
     for (int i = 0; i < 9; i++) {
       if (i % 4 != 0) diag = diag && geo.p2i[i] == 0.0;
       unit = unit && geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0);
     }
     const int geom = unit ? 2 : diag ? 1 : 0;
-#define CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, PAD)                                                                        \
-    hipLaunchKernelGGL((k_project<T, MODE, GEOM, PAD>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
+#define CUBERILLE_LAUNCH_PROJECT_FRAME(MODE, GEOM, PAD, REGION)                                                              \
+    hipLaunchKernelGGL((k_project<T, MODE, GEOM, PAD, REGION>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
                        w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
-                       w.escCap, dyn, w.padValue, w.padValueInt)
+                       w.escCap, dyn, w.padValue, w.padValueInt, w.rowPitch, w.slicePitch)
+#define CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, PAD) CUBERILLE_LAUNCH_PROJECT_FRAME(MODE, GEOM, PAD, false)
 #define CUBERILLE_LAUNCH_PROJECT(MODE, GEOM) CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, false)
 #define CUBERILLE_LAUNCH_PROJECT_GEOM(MODE)                                                                                  \
     do { if (geom == 2) CUBERILLE_LAUNCH_PROJECT(MODE, 2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT(MODE, 1);            \
@@ -4139,12 +4364,19 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
       if (geom == 2) CUBERILLE_LAUNCH_PROJECT_PAD(0, 2, true); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_PAD(0, 1, true);
       else CUBERILLE_LAUNCH_PROJECT_PAD(0, 0, true);
     } else
+    if (w.region) {
+      // a whole volume (the box), every slice in the buffer: MODE 0, the only one offered with a region (count_prepare)
+      if (mode != 0) return hipErrorInvalidValue;
+      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_FRAME(0, 2, false, true); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_FRAME(0, 1, false, true);
+      else CUBERILLE_LAUNCH_PROJECT_FRAME(0, 0, false, true);
+    } else
     if (mode == 1) CUBERILLE_LAUNCH_PROJECT_GEOM(1);
     else if (mode == 2) CUBERILLE_LAUNCH_PROJECT_GEOM(2);
     else CUBERILLE_LAUNCH_PROJECT_GEOM(0);
 #undef CUBERILLE_LAUNCH_PROJECT_GEOM
 #undef CUBERILLE_LAUNCH_PROJECT
 #undef CUBERILLE_LAUNCH_PROJECT_PAD
+#undef CUBERILLE_LAUNCH_PROJECT_FRAME
     return hipGetLastError();
   });
 }

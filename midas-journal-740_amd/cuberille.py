@@ -130,6 +130,29 @@ def check_border(pixel_type, border):
         raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "the border value is not representable in the pixel type")
 
 
+def region_desc(desc, start_xyz, size_xyz):
+    """The description of the box [start, start + size) of the buffer `desc` describes (cuberille_region_desc, no GPU): dims
+    = size, index_start = the buffer's + start, the same origin, spacing and direction -- the image
+    itk::ExtractImageFilter would hand the reference, its index kept.  start is a position in the buffer (x, y, z).  Raises
+    CuberilleError: ERR_ARGUMENT for a negative start, an empty size or a box that leaves the buffer, ERR_LIMIT where the
+    box's start index leaves +-2^30 or start index + size exceeds 2^31 - 1.  size (0, 0, 0): the buffer itself."""
+    out = _abi.ImageDesc()
+    start = (C.c_int64 * 3)(*[int(v) for v in start_xyz])
+    size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
+    rc = _abi.lib().cuberille_region_desc(C.byref(desc), start, size, C.byref(out))
+    if rc:
+        text = _abi.lib().cuberille_last_error(None)      # (the library's own words, kept per thread)
+        raise _abi.CuberilleError(rc, text.decode() if text else "")
+    return out
+
+
+def check_region(desc, region):
+    """The box of Extractor.set_region against the buffer an extraction is about to be handed: raises what the library
+    would (region_desc), before a device is touched.  region: None, or (start_xyz, size_xyz)."""
+    if region is not None:
+        region_desc(desc, region[0], region[1])
+
+
 def make_desc(np_dtype, dims_xyz, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=None, index_start=(0, 0, 0)):
     d = _abi.ImageDesc()
     d.pixel_type = PIXEL_CODES[np.dtype(np_dtype)]
@@ -156,6 +179,7 @@ class Extractor:
         self.device = int(device)
         self.result = None
         self._border = (0, 0)               # set_border: width, and the value as a 64-bit integer pixel type would hold it
+        self._region = None                 # set_region: (start_xyz, size_xyz) of the box, or None
 
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx:
@@ -195,6 +219,7 @@ class Extractor:
         desc = make_desc(vox.dtype, vol.dims, vol.spacing, vol.origin, vol.direction, getattr(vol, "index_start", (0, 0, 0)))
         check_iso(int(desc.pixel_type), params)
         check_border(int(desc.pixel_type), self._border)
+        check_region(desc, self._region)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_host(
             self._ctx, C.byref(desc), C.c_void_p(vox.ctypes.data), C.byref(params), C.byref(res)))
@@ -243,6 +268,7 @@ class Extractor:
     def extract_device(self, dev_ptr, desc, params, slab=None):
         check_iso(int(desc.pixel_type), params)
         check_border(int(desc.pixel_type), self._border)
+        check_region(desc, self._region)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_device(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -253,6 +279,7 @@ class Extractor:
     def count(self, dev_ptr, desc, params, slab=None):
         check_iso(int(desc.pixel_type), params)
         check_border(int(desc.pixel_type), self._border)
+        check_region(desc, self._region)
         npnt, ncell = C.c_uint64(), C.c_uint64()
         _abi.check(self._ctx, self._lib.cuberille_count(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -380,6 +407,23 @@ class Extractor:
         as_int = 0 if exact is None else ((exact + (1 << 63)) % (1 << 64)) - (1 << 63)
         _abi.check(self._ctx, self._lib.cuberille_set_border(self._ctx, int(width), float(value), as_int))
         self._border = (int(width), exact)
+
+    def set_region(self, start_xyz, size_xyz):
+        """Extract a box of a larger volume in place (cuberille_set_region): every later whole-volume extraction still takes
+        the description and the pointer of the WHOLE buffer and gives the mesh of the box [start, start + size) -- that of
+        the cropped copy with its index kept (region_desc), bit for bit, without the copy: on the device the sweep and the
+        walk read the caller's buffer by its pitches, extract_host uploads the box alone.  start is a position in the buffer
+        (x, y, z).  Slabs, steps, groups, extract_stream, set_border, the B-spline interpolator, a held or
+        recursive-Gaussian gradient and the two projection variants are refused at the extraction."""
+        start = (C.c_int64 * 3)(*[int(v) for v in start_xyz])
+        size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
+        _abi.check(self._ctx, self._lib.cuberille_set_region(self._ctx, start, size))
+        self._region = None if not any(int(v) for v in size_xyz) else (tuple(int(v) for v in start_xyz), tuple(int(v) for v in size_xyz))
+
+    def clear_region(self):
+        """Back to the default: the buffer handed over is the image."""
+        _abi.check(self._ctx, self._lib.cuberille_set_region(self._ctx, None, None))
+        self._region = None
 
     def set_interpolator(self, kind, spline_order=3, coordinate_bits=32, coefficient_bits=32):
         """The value interpolator of the walk for the later extractions (cuberille_set_interpolator): _abi.INTERP_LINEAR
@@ -554,6 +598,15 @@ class ExtractorGroup:
             ctx = self.context(i)
             _abi.check(ctx, self._lib.cuberille_set_border(ctx, int(width), float(value), 0))
 
+    def set_region(self, start_xyz, size_xyz):
+        """A region (Extractor.set_region) on every member: the group's extraction then raises the library's refusal -- a
+        box belongs to one context's whole volume."""
+        start = (C.c_int64 * 3)(*[int(v) for v in start_xyz])
+        size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
+        for i in range(len(self.devices)):
+            ctx = self.context(i)
+            _abi.check(ctx, self._lib.cuberille_set_region(ctx, start, size))
+
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
         (slab -1: every slab's; n < 0: off)."""
@@ -635,6 +688,7 @@ class CuberilleImageToMeshFilter:
         self._bspline = None                      # (coordinate bits, coefficient bits) of SetBSplineInterpolator, or None
         self._pad_border = False                  # SetPadBorder: off, like the reference
         self._border_pad_value = 0                # SetBorderPadValue: NumericTraits<InputPixelType>::Zero
+        self._region = None                       # SetExtractionRegion: (index_xyz, size_xyz) in ITK index space, or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -804,6 +858,27 @@ class CuberilleImageToMeshFilter:
     def GetBorderPadValue(self):
         return self._border_pad_value
 
+    def SetExtractionRegion(self, index_xyz, size_xyz):
+        """Not in the reference -- what a caller does there with itk::ExtractImageFilter first: mesh the box of the input that
+        starts at ITK index `index_xyz` and has `size_xyz` voxels, as if that filter's output (its index kept) were the
+        input.  No cropped copy is made; Update() uploads the box alone (cuberille_set_region).  The box must lie inside the
+        input's buffered region: Update() raises the library's message otherwise."""
+        self._region = (tuple(int(v) for v in index_xyz), tuple(int(v) for v in size_xyz))
+
+    def ClearExtractionRegion(self):
+        self._region = None
+
+    def GetExtractionRegion(self):
+        """(index_xyz, size_xyz), or None."""
+        return self._region
+
+    def _buffer_region(self, vol):
+        """The region as the library takes it: a position in the buffer = ITK index - start index of the input."""
+        if self._region is None:
+            return None
+        s = getattr(vol, "index_start", (0, 0, 0))
+        return tuple(int(i) - int(b) for i, b in zip(self._region[0], s)), self._region[1]
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -816,6 +891,12 @@ class CuberilleImageToMeshFilter:
             # (before a device is touched: the ring would have to reach across the slabs)
             raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "an implied border (SetPadBorder / cuberille_set_border) is not "
                                       "offered in a group: the ring would have to reach across slabs")
+        if len(self._devices) > 1 and self._region is not None:
+            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "a region (SetExtractionRegion / cuberille_set_region) is not "
+                                      "offered in a group: a box belongs to one context's whole volume")
+        if self._region is not None:
+            # (before a device is touched: the box against the input's buffered region)
+            check_region(self._group_desc(self._input), self._buffer_region(self._input))
         self._acquire(True)
         vol = self._input
         if self._step < 0.0:                      # txx:82-85, sticky like the reference (quirk Q3)
@@ -836,6 +917,10 @@ class CuberilleImageToMeshFilter:
         else:
             self._extractor.set_interpolator(_abi.INTERP_LINEAR)
         self._extractor.set_border(1 if self._pad_border else 0, self._border_pad_value)
+        if self._region is not None:
+            self._extractor.set_region(*self._buffer_region(vol))
+        else:
+            self._extractor.clear_region()
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
         self.last_number_of_slabs = 1

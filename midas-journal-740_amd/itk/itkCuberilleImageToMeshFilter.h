@@ -228,6 +228,22 @@ public:
   itkGetMacro(BorderPadValue, InputPixelType);
   itkSetMacro(BorderPadValue, InputPixelType);
 
+  /** Not in the reference -- what a caller does there with itk::ExtractImageFilter / RegionOfInterestImageFilter first.
+   *  SetExtractionRegion(r): Update() gives the mesh the filter gives for the box r of the input as an image of its own
+   *  whose region keeps the index (size r.GetSize(), index r.GetIndex(), the same origin, spacing and direction): the same
+   *  points, bit for bit, and cells as crop-then-filter.  r is in ITK index space and must lie inside the input's
+   *  GetBufferedRegion(), else Update() throws.  No cropped copy of the image is made, on the host or on the device: only
+   *  the box's rows cross the link, straight from the input's buffer (cuberille_set_region).  Offered where the device
+   *  walks (or nothing is projected): with SetDevices of more than one device, the B-spline interpolator,
+   *  ReproduceStaleGradient, PadBorderOn(), the compiled-out projection / gradient variants or an interpolator that takes
+   *  the host walk (the user's object is bound to the whole image) Update() throws.  ClearExtractionRegion(): the default,
+   *  the whole buffered region. */
+  typedef typename InputImageType::RegionType RegionType;
+  void SetExtractionRegion(const RegionType &region) { m_ExtractionRegion = region; m_HasExtractionRegion = true; this->Modified(); }
+  void ClearExtractionRegion() { m_HasExtractionRegion = false; this->Modified(); }
+  const RegionType &GetExtractionRegion() const { return m_ExtractionRegion; }
+  bool HasExtractionRegion() const { return m_HasExtractionRegion; }
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -268,6 +284,8 @@ private:
   bool m_BSplineOnDevice;
   bool m_PadBorder;
   InputPixelType m_BorderPadValue;
+  RegionType m_ExtractionRegion;
+  bool m_HasExtractionRegion;
   double m_LastDeviceSeconds;
   double m_LastMeshFillSeconds;
   double m_LastExtractSeconds;

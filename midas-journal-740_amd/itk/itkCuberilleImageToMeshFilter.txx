@@ -498,6 +498,7 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_ReproduceStaleGradient = false;
   m_BSplineOnDevice = true;
   m_PadBorder = false;
+  m_HasExtractionRegion = false;
   m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
   m_LastDeviceSeconds = 0.0;
   m_LastMeshFillSeconds = 0.0;
@@ -606,6 +607,15 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetInp
       // (PadBorderOn() ahead of SetInput: the workspace of the image with its border)
       (void)cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
                                  cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
+      // (SetExtractionRegion ahead of SetInput: the workspace of the box; a box outside this image is Update()'s to report)
+      int64_t boxStart[3] = {0, 0, 0}, boxSize[3] = {0, 0, 0};
+      if (m_HasExtractionRegion)
+        for (int i = 0; i < 3; i++)
+          {
+          boxStart[i] = static_cast<int64_t>(m_ExtractionRegion.GetIndex()[i]) - desc.index_start[i];
+          boxSize[i] = static_cast<int64_t>(m_ExtractionRegion.GetSize()[i]);
+          }
+      if (cuberille_set_region(m_Context, boxStart, boxSize) != CUBERILLE_OK) (void)cuberille_set_region(m_Context, 0, 0);
       (void)cuberille_warm_up(m_Context, &desc, 0);
       }
     }
@@ -665,6 +675,30 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "an implied border (PadBorderOn / cuberille_set_border) is not offered with an interpolator that takes "
                          "the host walk: the caller's interpolator object is bound to the unpadded image");
 
+  // SetExtractionRegion: ITK index space -> a position in the buffer; inside the buffered region, and on the device's walk
+  int64_t boxStart[3] = {0, 0, 0}, boxSize[3] = {0, 0, 0};
+  if (m_HasExtractionRegion)
+    {
+    cuberille_image_desc box;
+    for (int i = 0; i < 3; i++)
+      {
+      boxStart[i] = static_cast<int64_t>(m_ExtractionRegion.GetIndex()[i]) - desc.index_start[i];
+      boxSize[i] = static_cast<int64_t>(m_ExtractionRegion.GetSize()[i]);
+      }
+    const int rc = cuberille_region_desc(&desc, boxStart, boxSize, &box);
+    if (rc == CUBERILLE_ERR_LIMIT)
+      itkExceptionMacro(<< "the extraction region's index must lie within +-2^30 and, with its size, below 2^31");
+    if (rc != CUBERILLE_OK || boxSize[0] < 1 || boxSize[1] < 1 || boxSize[2] < 1)
+      itkExceptionMacro(<< "the extraction region (SetExtractionRegion) must hold at least one pixel along every axis and lie "
+                           "inside the input's buffered region");
+    if (hostWalk)
+      itkExceptionMacro(<< "an extraction region (SetExtractionRegion / cuberille_set_region) is not offered with an interpolator "
+                           "that takes the host walk: the caller's interpolator object is bound to the whole image");
+    if (m_Devices.size() > 1)
+      itkExceptionMacro(<< "an extraction region (SetExtractionRegion / cuberille_set_region) is not offered with SetDevices of "
+                           "more than one device: a box belongs to one context's whole volume");
+    }
+
   // several devices: the context group, for what a slab takes (the host walk included: its device part does not project)
   const bool grouped = m_Devices.size() > 1 && !deviceBSpline && !m_ReproduceStaleGradient &&
                        !(prm.project_vertices && prm.gradient_variant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN);
@@ -697,6 +731,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
                              cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue)) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_border: " << cuberille_last_error(m_Context));
+    if (cuberille_set_region(m_Context, boxStart, boxSize) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_region: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));

@@ -9,7 +9,8 @@ false for every instantiation that existed) and two trailing kernel arguments th
 Result for the change that added the border (parent aab1e2c): 157 kernels identical; the 90 unpadded k_project instantiations
 differ in ONE immediate only -- the offset of the hidden kernel arguments behind the explicit ones, 0x1f8 -> 0x208 (the two
 new 8-byte arguments) in `s_load_dword s6, s[0:1], ...` and `s_add_u32 sN, s0, ...` -- and in nothing else; 30 padded
-instantiations are new.
+instantiations are new.  The change that added the region (cuberille_set_region: a REGION template parameter and two more
+trailing arguments, the pitches): profiles/region_walk_isa.txt.
 """
 import glob
 import os
@@ -46,9 +47,14 @@ def kernels(lib):
 
 
 def renamed(name):
-    """The parent's k_project<T, MODE, GEOM>(...) is this tree's k_project<T, MODE, GEOM, false>(..., double, long long)."""
+    """The parent's name of a k_project instantiation in this tree.  The border change: k_project<T, MODE, GEOM>(...) became
+    k_project<T, MODE, GEOM, false>(..., double, long long); the region change: k_project<T, MODE, GEOM, PAD>(..., double, long
+    long) became k_project<T, MODE, GEOM, PAD, false>(..., double, long long, long long, long long)."""
     if "k_project<" not in name:
         return name
+    if name.endswith("double, long long)"):
+        return re.sub(r"k_project<([^>]*)>", lambda m: "k_project<%s, false>" % m.group(1), name).replace(
+            "double, long long)", "double, long long, long long, long long)")
     return re.sub(r"k_project<([^>]*)>", lambda m: "k_project<%s, false>" % m.group(1), name).replace("int)", "int, double, long long)")
 
 
