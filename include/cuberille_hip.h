@@ -427,6 +427,32 @@ int cuberille_set_border(cuberille_ctx *ctx, int pad_width, double pad_value, in
 int cuberille_set_region(cuberille_ctx *ctx, const int64_t start[3], const int64_t size[3]);
 int cuberille_region_desc(const cuberille_image_desc *img, const int64_t start[3], const int64_t size[3],
                           cuberille_image_desc *cropped);
+/* Mesh a label or a value band in place (new symbols within ABI 13, no struct changed).  With a band set, every later
+ * whole-volume extraction of an image I of pixel type T gives exactly the mesh the same context with the band off gives for
+ *   B(u) = (lower <= I(u) && I(u) <= upper) ? inside : outside        -- all four values are T; a NaN pixel is outside --
+ * the image itk::BinaryThresholdImageFilter<Image<T>, Image<T>> makes of I: the same dims, start index, origin, spacing and
+ * direction; the iso value and every other parameter stay the caller's and apply to B.  The same counts, ids, order and cells,
+ * and with project_vertices on the same coordinate bytes: the walk interpolates B, not I.  B is never stored and nothing the
+ * size of the voxels is allocated: the sweep evaluates the band in place of the threshold (!(B < iso) takes two values, so the
+ * bit is "in the band" XOR !(outside < iso); where !(inside < iso) says the same the bit volume is constant and the mesh empty),
+ * the walk turns every pixel it loads into inside or outside, in T, before any arithmetic.
+ * v = {lower, upper, inside, outside}; the 64-bit integer pixel types take vi (the same 64 bits for a uint64 past 2^63), like
+ * the iso value; the floating types convert v like the iso value (a C cast).
+ * cuberille_set_band: on = 0 restores the default (the same bytes as before the symbol existed; v and vi may be null).  A NaN
+ *   bound is refused at once; the rest is checked at the extraction, where the pixel type is known, by cuberille_band_check.
+ * cuberille_band_check (needs no GPU, no context): the single validator.  CUBERILLE_ERR_ARGUMENT for a value the pixel type
+ *   does not hold -- outside its range, or a fraction for an integer type: a bound cut off like a C cast would move the band
+ *   by a label --, for lower > upper (ITK throws there) and for a NaN bound.  The text of a refusal:
+ *   cuberille_last_error(NULL), kept per thread like that of a failed cuberille_create.
+ * Offered: cuberille_extract_device, cuberille_extract_host (the chunked upload included) and cuberille_count +
+ * cuberille_emit on a whole volume, project_vertices off and on, quads and triangles, every pixel type.
+ * Refused with CUBERILLE_ERR_ARGUMENT and a message that names the band, the context left usable, each because it would need
+ * B in a second image or across ranks: a slab that is not the whole volume; the cuberille_step_* calls;
+ * cuberille_group_extract_host with a member that has a band; cuberille_extract_stream; cuberille_set_border or
+ * cuberille_set_region together with a band; with project_vertices on, the B-spline interpolator, a held gradient
+ * (cuberille_hold_gradient), CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN and the ADVANCED and LINESEARCH branches. */
+int cuberille_set_band(cuberille_ctx *ctx, int on, const double v[4], const int64_t vi[4]);
+int cuberille_band_check(int pixel_type, const double v[4], const int64_t vi[4]);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

@@ -12,6 +12,6 @@ The directory name carries a hyphen, so import it through `__graft_entry__.load_
   itk/             C++ drop-in: itkCuberilleImageToMeshFilter.h + the ITK-lite shim headers
 """
 from . import _abi, mha, volumes  # noqa: F401
-from .cuberille import (CuberilleImageToMeshFilter, Extractor, ExtractorGroup, Mesh, group_plan, make_desc, make_params,  # noqa: F401
-                        region_desc, required_halo)
+from .cuberille import (CuberilleImageToMeshFilter, Extractor, ExtractorGroup, Mesh, check_band, group_plan, make_desc,  # noqa: F401
+                        make_params, region_desc, required_halo)
 from .mha import MhaStream, Volume, open_stream, read_mha, write_mha  # noqa: F401

@@ -31,7 +31,7 @@ EXPORTS = [
     "cuberille_slice_counts", "cuberille_failed_row", "cuberille_warm_up", "cuberille_mesh_host", "cuberille_step_classify", "cuberille_step_count",
     "cuberille_release_host_mesh", "cuberille_hold_gradient", "cuberille_gradient_held",
     "cuberille_set_interpolator", "cuberille_bspline_coefficients", "cuberille_bspline_coefficients_info",
-    "cuberille_set_border", "cuberille_set_region", "cuberille_region_desc",
+    "cuberille_set_border", "cuberille_set_region", "cuberille_region_desc", "cuberille_set_band", "cuberille_band_check",
     "cuberille_group_create", "cuberille_group_destroy", "cuberille_group_last_error", "cuberille_group_context",
     "cuberille_group_plan", "cuberille_group_warm_up", "cuberille_group_extract_host", "cuberille_group_slab_result",
     "cuberille_group_mesh_host", "cuberille_group_release_host_mesh", "cuberille_group_mesh_write_vtk",
@@ -140,6 +140,8 @@ def lib():
     L.cuberille_set_border.argtypes = [vp, C.c_int, C.c_double, C.c_int64]
     L.cuberille_set_region.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.cuberille_region_desc.argtypes = [C.POINTER(ImageDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(ImageDesc)]
+    L.cuberille_set_band.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.cuberille_band_check.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

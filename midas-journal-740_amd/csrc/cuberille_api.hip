@@ -115,6 +115,9 @@ struct cuberille_ctx {
   int padWidth = 0;                      // cuberille_set_border: voxels of constant border implied around every later whole volume
   double padValue = 0.0;                 // ... and their value, which travels like the iso value
   long long padValueInt = 0;
+  bool bandOn = false;                   // cuberille_set_band: every later whole-volume extraction meshes the binary image a band of the pixel values makes ...
+  double bandV[4] = {0.0, 0.0, 0.0, 0.0};      // ... lower, upper, inside, outside, each travelling like the iso value
+  long long bandVi[4] = {0, 0, 0, 0};
   bool regionOn = false;                 // cuberille_set_region: every later whole-volume extraction meshes this box of its buffer ...
   int64_t regionStart[3] = {0, 0, 0};    // ... its first voxel, as a position in the buffer (x, y, z) ...
   int64_t regionSize[3] = {0, 0, 0};     // ... and its size
@@ -274,6 +277,52 @@ int region_check(const cuberille_image_desc *img, const int64_t start[3], const 
   return CUBERILLE_OK;
 }
 
+// cuberille_band_check: lower, upper, inside, outside against a pixel type.  All four are values OF the pixel type in
+// itk::BinaryThresholdImageFilter<Image<T>, Image<T>>: each must be one the type holds -- an integer type takes no fraction and
+// nothing beyond its range (the window of the iso and the ring value, lo - 1 < v < hi + 1, with the fraction refused as well: a
+// bound cut off like a C cast would move the band by a label); the 64-bit integer types are judged by the double for the range
+// and carry the value in vi -- and the filter throws for lower > upper.  A NaN bound is refused for the floating types too:
+// it makes an empty band by accident.  The floating types convert a double like the iso value does (a C cast), and NaN and
+// infinite VALUES are a float image's to hold.
+int band_check(int pixel_type, const double v[4], const int64_t vi[4], const char **why) {
+  static const char *const names[4] = {"lower bound", "upper bound", "inside value", "outside value"};
+  static thread_local std::string text;
+  auto no = [&](const std::string &m) { text = "band (cuberille_set_band): " + m; if (why) *why = text.c_str(); return CUBERILLE_ERR_ARGUMENT; };
+  if (pixel_size(pixel_type) == 0) return no("unknown pixel type");
+  if (!v || !vi) return no("null value pointer");
+  double lo = 0.0, hi = 0.0;
+  bool integer = true, wide = false;
+  switch (pixel_type) {
+    case CUBERILLE_PIX_U8: hi = 255.0; break;
+    case CUBERILLE_PIX_I8: lo = -128.0; hi = 127.0; break;
+    case CUBERILLE_PIX_U16: hi = 65535.0; break;
+    case CUBERILLE_PIX_I16: lo = -32768.0; hi = 32767.0; break;
+    case CUBERILLE_PIX_U32: hi = 4294967295.0; break;
+    case CUBERILLE_PIX_I32: lo = -2147483648.0; hi = 2147483647.0; break;
+    case CUBERILLE_PIX_I64: lo = -9223372036854775808.0; hi = 9223372036854775808.0; wide = true; break;      // [lo, hi)
+    case CUBERILLE_PIX_U64: lo = 0.0; hi = 18446744073709551616.0; wide = true; break;
+    default: integer = false; break;
+  }
+  for (int k = 0; k < 4; k++) {
+    if (integer) {
+      // (a 64-bit value rounds as a double -- one just under the type's top UP to it, one just below an int64's bottom up
+      //  to that: vi, which wraps what the type does not hold to its other end, tells them apart by its sign)
+      const bool atTop = wide && v[k] == hi && (pixel_type == CUBERILLE_PIX_I64 ? vi[k] > 0 : vi[k] < 0);
+      const bool wrapped = pixel_type == CUBERILLE_PIX_I64 && ((v[k] < 0.0 && vi[k] >= 0) || (v[k] > 0.0 && vi[k] <= 0));
+      const bool inRange = wide ? (v[k] >= lo && (v[k] < hi || atTop) && !wrapped) : (v[k] > lo - 1.0 && v[k] < hi + 1.0);
+      if (!inRange || v[k] != std::floor(v[k])) return no(std::string("the ") + names[k] + " is not representable in the pixel type");
+    } else if (k < 2 && v[k] != v[k]) {
+      return no(std::string("the ") + names[k] + " is NaN");
+    }
+  }
+  bool ordered;
+  if (pixel_type == CUBERILLE_PIX_U64) ordered = (uint64_t)vi[0] <= (uint64_t)vi[1];
+  else if (pixel_type == CUBERILLE_PIX_I64) ordered = vi[0] <= vi[1];
+  else ordered = v[0] <= v[1];
+  if (!ordered) return no("the lower bound is above the upper bound (itk::BinaryThresholdImageFilter throws there)");
+  return CUBERILLE_OK;
+}
+
 int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!img || !vox || !prm) return fail(c, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
@@ -335,6 +384,27 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
         return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would be the box's");
       if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
         return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the default projection branch only (txx:439-474)");
+    }
+  }
+  if (c->bandOn) {
+    // cuberille_set_band: the four values against THIS image's pixel type, and what would need the binary image B in a second
+    // image (coefficients, a gradient image) or is simply not part of the setting -- the border's list, for the border's reasons
+    const char *why = "";
+    const int brc = band_check(img->pixel_type, c->bandV, (const int64_t *)c->bandVi, &why);
+    if (brc) return fail(c, brc, why);
+    if (c->padWidth)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) together with an implied border (cuberille_set_border) is not offered: the ring's value would have to be one of the band's two");
+    if (c->regionOn)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) together with a region (cuberille_set_region) is not offered: the pitched sweep and walk have no band form");
+    if (prm->project_vertices) {
+      if (c->interp == CUBERILLE_INTERP_BSPLINE)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered with the B-spline interpolator: its coefficient image would be the binary image's");
+      if (c->holdGradient)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
+      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would be the binary image's");
+      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
+        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is offered with the default projection branch only (txx:439-474)");
     }
   }
   if (c->padWidth) {
@@ -710,6 +780,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
   if (!whole && c->regionOn)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is a box of a whole volume: not offered on slabs");
+  if (!whole && c->bandOn)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) belongs to a whole volume: not offered on slabs");
   if (!whole) {
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
@@ -766,6 +838,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   w.vox = dev_voxels;
   w.pad = c->padWidth; w.padValue = c->padValue; w.padValueInt = c->padValueInt;
   w.rowPitch = g.nx; w.slicePitch = (long long)g.nx * g.ny;
+  w.band = c->bandOn ? 1 : 0;
+  for (int k = 0; k < 4; k++) { w.bandV[k] = c->bandV[k]; w.bandVi[k] = c->bandVi[k]; }
   if (boxed(c)) {
     // the sweep and the walk start at the box's first voxel and step by the BUFFER's pitches; nothing else reads voxels
     const long long Nx = (long long)img->dims[0], NxNy = Nx * (long long)img->dims[1];
@@ -1368,6 +1442,7 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
 // cuberille_step_begin, and the first half of cuberille_extract_device (the one-wait step with the context as its only rank:
 // a whole volume, so an implied border is at home there while the steps of a driver's ranks refuse it)
 const char *const kNoBorderInSteps = "an implied border (cuberille_set_border) would have to reach across ranks: not offered with the cuberille_step_* calls";
+const char *const kNoBandInSteps = "a band (cuberille_set_band) belongs to one context's whole volume: not offered with the cuberille_step_* calls";
 const char *const kNoRegionInSteps = "a region (cuberille_set_region) is a box of one context's whole volume: not offered with the cuberille_step_* calls";
 int step_begin_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                     const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
@@ -1390,6 +1465,7 @@ int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, cons
                          const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
   if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
   if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
+  if (c && c->bandOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBandInSteps);
   return step_begin_impl(c, img, dev_voxels, prm, slab, dev_row, row_bytes);
 }
 
@@ -1397,6 +1473,7 @@ int cuberille_step_classify(cuberille_ctx *c, const cuberille_image_desc *img, c
                             const cuberille_slab *slab, uint64_t **dev_bits, size_t *words_per_slice) {
   if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
   if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
+  if (c && c->bandOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBandInSteps);
   int rc = validate(c, img, dev_voxels, prm);
   if (rc) return rc;
   if (!dev_bits || !words_per_slice) return fail(c, CUBERILLE_ERR_ARGUMENT, "null bit-plane pointer");
@@ -1735,6 +1812,8 @@ int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, 
   if (c && !source) return fail(c, CUBERILLE_ERR_ARGUMENT, "null chunk source");
   if (c && c->regionOn)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered with cuberille_extract_stream: the source produces whole slices");
+  if (c && c->bandOn)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered with cuberille_extract_stream");
   int rc = validate(c, img, (const void *)source, prm);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1773,13 +1852,15 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     cuberille_params p = dflt;
     p.iso_value = 100.0;
     cuberille_result r{};
-    const bool applied = c->regionApplied;
+    const bool applied = c->regionApplied, banded = c->bandOn;
     c->regionApplied = true;                 // (cuberille_set_region speaks of the caller's volumes, not of this one)
+    c->bandOn = false;                       // (... and so does cuberille_set_band, whose values are those of the caller's pixel type)
     for (int i = 0; i < 2; i++) {            // twice: the second one takes the blind launches of the one-wait step
       const int rc = cuberille_extract_host(c, &d, tiny, &p, &r);
-      if (rc) { c->regionApplied = applied; return rc; }
+      if (rc) { c->regionApplied = applied; c->bandOn = banded; return rc; }
     }
     c->regionApplied = applied;
+    c->bandOn = banded;
     // the runtime sets up its staging for copies from and to PAGEABLE memory at the first copy that needs it (measured
     // through the reference's driver: 7.2 ms inside the first hipMemcpyAsync of nucleon.mha's 69 KB, profiles/
     // r4_cold_update.log): one round trip of a size that takes its staging buffers, one of a size it pins in place
@@ -2058,6 +2139,29 @@ int cuberille_set_border(cuberille_ctx *c, int pad_width, double pad_value, int6
   c->padWidth = pad_width;
   c->padValue = pad_value;
   c->padValueInt = (long long)pad_value_int;
+  return CUBERILLE_OK;
+}
+
+int cuberille_band_check(int pixel_type, const double v[4], const int64_t vi[4]) {
+  const char *why = "";
+  const int rc = band_check(pixel_type, v, vi, &why);
+  if (rc) g_create_error = why;     // (no context to keep the text: cuberille_last_error(NULL), per thread like a failed create's)
+  return rc;
+}
+
+int cuberille_set_band(cuberille_ctx *c, int on, const double v[4], const int64_t vi[4]) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  if (!on) {
+    c->bandOn = false;
+    for (int k = 0; k < 4; k++) { c->bandV[k] = 0.0; c->bandVi[k] = 0; }
+    return CUBERILLE_OK;
+  }
+  if (!v || !vi) return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) needs its four values both ways");
+  // (what can be said without the pixel type; the rest at the extraction, by the same validator)
+  if (v[0] != v[0] || v[1] != v[1]) return fail(c, CUBERILLE_ERR_ARGUMENT, "band (cuberille_set_band): a bound is NaN");
+  c->bandOn = true;
+  for (int k = 0; k < 4; k++) { c->bandV[k] = v[k]; c->bandVi[k] = (long long)vi[k]; }
   return CUBERILLE_OK;
 }
 
@@ -2345,6 +2449,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
     if (c->regionOn)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has a region set (cuberille_set_region): "
                                               "a box of one context's whole volume, not offered in a group");
+    if (c->bandOn)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has a band set (cuberille_set_band): "
+                                              "it belongs to one context's whole volume, not offered in a group");
     if (c->padWidth)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has an implied border set (cuberille_set_border): "
                                               "the ring would have to reach across slabs, not offered in a group");

@@ -150,6 +150,12 @@ struct Workspace {     // device pointers valid for one count/emit pair
   // them.  Read by the sweep and the walk only, every other kernel works on the bit volume.
   int region, regionSweep;
   long long rowPitch, slicePitch;
+  // cuberille_set_band: the sweep and the walk see B = (lower <= pixel && pixel <= upper) ? inside : outside in place of the
+  // pixel -- itk::BinaryThresholdImageFilter's output, never stored.  bandV / bandVi: lower, upper, inside, outside, each the
+  // pair the iso value travels as.  Read by the unpadded, unpitched sweep and the default walk only.
+  int band;
+  double bandV[4];
+  long long bandVi[4];
 };
 
 // Development switches, set per context through cuberille_debug_set_option (never read from the environment).

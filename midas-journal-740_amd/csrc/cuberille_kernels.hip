@@ -110,16 +110,86 @@ __device__ __forceinline__ u32 inside_bits(const Vec16<T> &r, T iso) {
   }
 }
 
+// cuberille_set_band: the sweep of the image B = (lower <= pixel && pixel <= upper) ? inside : outside that
+// itk::BinaryThresholdImageFilter would make, without B.  !(B(u) < iso) takes two values only -- bin for a pixel in the band,
+// bout for one outside it, both worked out on the host in T -- so the bit is band(u) XOR bout where they differ (invert = bout);
+// where they are equal the host hands over the empty band lower = 1 > upper = 0 and the same code writes the constant.
+// bit j = (lower <= pixel j && pixel j <= upper) != invert; a NaN pixel fails both comparisons: outside the band.
+template <class T>
+__device__ __forceinline__ u32 inside_bits_band(const Vec16<T> &r, T lower, T upper, bool invert) {
+  constexpr u32 ALL = (u32)((1ull << Vec16<T>::N) - 1ull);
+  const u32 flip = invert ? ALL : 0u;                     // wave-uniform
+  if constexpr (sizeof(T) == 1) {
+    // 1-byte pixels: two of inside_bits' SWAR comparisons per packed dword.  x >= lower as there; upper >= x with the
+    // roles swapped: bit 7 of ((ul | 0x80) - xl) says ul >= xl, and upper >= x is (~x7 | that) when upper >= 128,
+    // (~x7 & that) when upper < 128.  The second v_bitop3 takes the first comparison's masked bit 7s as its third
+    // input, which is the AND; then the same ONE v_dot4_u32_u8 gather per dword.
+    const u32 bias = std::is_signed<T>::value ? 0x80808080u : 0u;
+    const u32 lo = ((u32)(unsigned char)lower) ^ (bias & 0x80u), up = ((u32)(unsigned char)upper) ^ (bias & 0x80u);
+    const u32 ll = (lo & 0x7fu) * 0x01010101u;
+    const u32 ul = ((up & 0x7fu) * 0x01010101u) | 0x80808080u;
+    const bool lhigh = (lo & 0x80u) != 0, uhigh = (up & 0x80u) != 0;      // wave-uniform
+    const u32 w[4] = {r.raw.x, r.raw.y, r.raw.z, r.raw.w};
+    u32 acc[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const u32 x = w[j] ^ bias;
+      const u32 d = bop3_32<0xEA>(x, 0x7f7f7f7fu, 0x80808080u) - ll;              // (x & 0x7f..) | 0x80.. - lower's low bits
+      const u32 ge = lhigh ? bop3_32<0x80>(x, d, 0x80808080u) : bop3_32<0xA8>(x, d, 0x80808080u);   // x >= lower, bit 7s
+      const u32 e = ul - (x & 0x7f7f7f7fu);
+      const u32 in = uhigh ? bop3_32<0x8A>(x, e, ge) : bop3_32<0x08>(x, e, ge);   // (~x |& e) & ge
+      acc[j >> 1] = __builtin_amdgcn_udot4(in, (j & 1) ? 0x80402010u : 0x08040201u, acc[j >> 1], false);
+    }
+    return ((acc[0] >> 7) | (acc[1] << 1)) ^ flip;
+  } else {
+    u32 m = 0;
+#pragma unroll
+    for (int j = 0; j < Vec16<T>::N; j++) m |= ((lower <= r.v[j] && r.v[j] <= upper) ? 1u : 0u) << j;
+    return m ^ flip;
+  }
+}
+
+// What a sweep kernel is handed to decide by, in the two argument slots the iso value always travelled in (a double, and an
+// integer for the 64-bit integer types): the plain instantiations keep their argument block to the letter; the BAND
+// instantiations take the two bounds the same way, and the inversion, in the same two places.
+struct BandBoundsD { double lower, upper; };
+struct BandBoundsI { long long lower, upper; int invert; };
+template <bool BAND> struct SweepD { typedef double type; };
+template <> struct SweepD<true> { typedef BandBoundsD type; };
+template <bool BAND> struct SweepI { typedef long long type; };
+template <> struct SweepI<true> { typedef BandBoundsI type; };
+
+// ... and what the kernels make of them: the value compared against (the iso value, or the band's lower bound), the band's
+// upper bound and inversion (unused constants in the plain instantiations, whose code stays what it was), and the scalar
+// twin of inside_bits / inside_bits_band for the one-voxel-per-lane kernels
+template <class T>
+__device__ __forceinline__ T sweep_lower(double isoD, long long isoI) { return iso_as<T>(isoD, isoI); }
+template <class T>
+__device__ __forceinline__ T sweep_lower(const BandBoundsD &d, const BandBoundsI &i) { return iso_as<T>(d.lower, i.lower); }
+template <class T>
+__device__ __forceinline__ T sweep_upper(double, long long) { return T(); }
+template <class T>
+__device__ __forceinline__ T sweep_upper(const BandBoundsD &d, const BandBoundsI &i) { return iso_as<T>(d.upper, i.upper); }
+__device__ __forceinline__ bool sweep_invert(long long) { return false; }
+__device__ __forceinline__ bool sweep_invert(const BandBoundsI &i) { return i.invert != 0; }
+template <class T, bool BAND>
+__device__ __forceinline__ bool sweep_one(T v, T iso, T upper, bool invert) {
+  if constexpr (BAND) return (iso <= v && v <= upper) != invert;
+  else return !(v < iso);
+}
+
 // Fast path: nx % 64 == 0, so the volume is a flat array of 64-voxel words.  Each lane
 // loads 16 B (VPL voxels), builds VPL bits; LPW = 64/VPL adjacent lanes OR their partial
 // words together.  One wave turns U KiB of voxels into U*VPL words per trip.
-template <class T, int U, bool NT>
+template <class T, int U, bool NT, bool BAND = false>
 __global__ __launch_bounds__(256) void k_classify_flat(const T *__restrict__ vox, u64 *__restrict__ bits,
-                                                       u64 nchunks, double isoD, long long isoI, u32 *__restrict__ sliceOcc,
+                                                       u64 nchunks, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI, u32 *__restrict__ sliceOcc,
                                                        int lgWordsPerSlice, u64 wordBase) {
   constexpr int VPL = 16 / sizeof(T);
   constexpr int LPW = 64 / VPL;
-  const T iso = iso_as<T>(isoD, isoI);
+  const T iso = sweep_lower<T>(isoD, isoI);
+  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
+  [[maybe_unused]] const bool invert = sweep_invert(isoI);
   const int lane = threadIdx.x & 63;
   const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -141,7 +211,9 @@ __global__ __launch_bounds__(256) void k_classify_flat(const T *__restrict__ vox
 #pragma unroll
     for (int u = 0; u < U; u++) {
       if (c + u >= nchunks) break;            // wave-uniform
-      const u32 m = inside_bits<T>(r[u], iso);
+      u32 m;
+      if constexpr (BAND) m = inside_bits_band<T>(r[u], iso, upper, invert);
+      else m = inside_bits<T>(r[u], iso);
       u64 part = (u64)m << (sub * VPL);
 #pragma unroll
       for (int s = 1; s < LPW; s <<= 1) part |= __shfl_xor(part, s, 64);
@@ -186,9 +258,9 @@ constexpr int SPAN_WORDS = 4096;
 // SPAN: words per span -- SPAN_WORDS, or a quarter of it where the volume is fewer than two rounds of such spans (a 512^3 float32
 // volume is ONE: every workgroup then ends in its 32 KiB store burst at the same moment, behind the last read; with four
 // rounds of 8 KiB bursts the stores of a round leave beside the next round's reads)
-template <class T, int SPAN = SPAN_WORDS>
+template <class T, int SPAN = SPAN_WORDS, bool BAND = false>
 __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox, u64 *__restrict__ bits, u64 nspans,
-                                                       double isoD, long long isoI, u32 *__restrict__ sliceOcc,
+                                                       typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI, u32 *__restrict__ sliceOcc,
                                                        int lgWordsPerSlice) {
   constexpr int U = 4;
   constexpr int VPL = 16 / sizeof(T);
@@ -196,7 +268,9 @@ __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox
   constexpr int TRIPS = SPAN / (4 * U * VPL);      // trips of U KiB per wave and span
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) u64 stage[SPAN];
-  const T iso = iso_as<T>(isoD, isoI);
+  const T iso = sweep_lower<T>(isoD, isoI);
+  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
+  [[maybe_unused]] const bool invert = sweep_invert(isoI);
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane % LPW;
@@ -214,7 +288,9 @@ __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox
     auto pack = [&](const Vec16<T> (&r)[U], int tl) {
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        const u32 m = inside_bits<T>(r[u], iso);
+        u32 m;
+        if constexpr (BAND) m = inside_bits_band<T>(r[u], iso, upper, invert);
+        else m = inside_bits<T>(r[u], iso);
         const u64 word = group_or<LPW>((u64)m << (sub * VPL));
         if (last) stage[(tl * U + u) * VPL + lane / LPW] = word;
       }
@@ -251,9 +327,9 @@ __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox
 // (two LDS words, funnel-shifted, the row's last word masked to the voxels it has) and the span leaves as the same 16-byte
 // write-through stores, occupancy folded in.  No flat scratch stream in memory, no second trip of the bits through L2, no
 // repack and occupancy launches (round-4 review: 1000^3 f32 swept at 5.15 TB/s through those, against 6.7 for whole-word rows).
-template <class T>
+template <class T, bool BAND = false>
 __global__ __launch_bounds__(256) void k_classify_span_rows(const T *__restrict__ vox, u64 *__restrict__ bits, u64 nspans,
-                                                            u64 nwordsAll, int nx, int W, u32 ny, double isoD, long long isoI,
+                                                            u64 nwordsAll, int nx, int W, u32 ny, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI,
                                                             u32 *__restrict__ sliceOcc) {
   constexpr int U = 4;
   constexpr int VPL = 16 / sizeof(T);
@@ -263,7 +339,9 @@ __global__ __launch_bounds__(256) void k_classify_span_rows(const T *__restrict_
   constexpr int STAGE = SPAN_WORDS + (4 * U + 1) * VPL + 2;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
-  const T iso = iso_as<T>(isoD, isoI);
+  const T iso = sweep_lower<T>(isoD, isoI);
+  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
+  [[maybe_unused]] const bool invert = sweep_invert(isoI);
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane % LPW;
@@ -301,7 +379,9 @@ __global__ __launch_bounds__(256) void k_classify_span_rows(const T *__restrict_
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        const u32 m = inside_bits<T>(r[u], iso);
+        u32 m;
+        if constexpr (BAND) m = inside_bits_band<T>(r[u], iso, upper, invert);
+        else m = inside_bits<T>(r[u], iso);
         const u64 word = group_or<LPW>((u64)m << (sub * VPL));
         if (last) stage[(c + u) * VPL + lane / LPW] = word;
       }
@@ -350,19 +430,22 @@ __global__ __launch_bounds__(256) void k_classify_span_rows(const T *__restrict_
 // Ragged rows (nx % 64 != 0), the fast way: k_classify_flat thresholds the slices as ONE flat stream of 16-byte
 // vectors starting at the 16-byte boundary at or below the first voxel (`skew` voxels earlier); this kernel
 // finishes the last, partial 1 KiB chunk ...
-template <class T>
+template <class T, bool BAND = false>
 __global__ __launch_bounds__(64) void k_classify_tail(const T *__restrict__ abase, u64 *__restrict__ flat, u64 firstVec,
-                                                      u64 nvec, double isoD, long long isoI) {
+                                                      u64 nvec, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI) {
   constexpr int VPL = 16 / sizeof(T);
   constexpr int LPW = 64 / VPL;
-  const T iso = iso_as<T>(isoD, isoI);
+  const T iso = sweep_lower<T>(isoD, isoI);
+  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
+  [[maybe_unused]] const bool invert = sweep_invert(isoI);
   const int lane = threadIdx.x & 63;
   const u64 v = firstVec + lane;
   u32 m = 0;
   if (v < nvec) {
     Vec16<T> r;
     r.raw = *reinterpret_cast<const uint4 *>(abase + v * VPL);
-    m = inside_bits<T>(r, iso);
+    if constexpr (BAND) m = inside_bits_band<T>(r, iso, upper, invert);
+    else m = inside_bits<T>(r, iso);
   }
   const int sub = lane % LPW;
   u64 part = (u64)m << (sub * VPL);
@@ -393,11 +476,13 @@ __global__ __launch_bounds__(256) void k_repack_rows(const u64 *__restrict__ fla
 
 // Generic path (any nx): one wave per (row, word); lane l tests voxel x = 64k + l; the
 // wave ballot IS the packed word.
-template <class T>
+template <class T, bool BAND = false>
 __global__ __launch_bounds__(256) void k_classify_rows(const T *__restrict__ vox, u64 *__restrict__ bits,
-                                                       int nx, int W, u64 t0, u64 nrows, u64 rowsPerSlice, double isoD,
-                                                       long long isoI, u32 *__restrict__ sliceOcc) {
-  const T iso = iso_as<T>(isoD, isoI);
+                                                       int nx, int W, u64 t0, u64 nrows, u64 rowsPerSlice, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI,
+                                                       u32 *__restrict__ sliceOcc) {
+  const T iso = sweep_lower<T>(isoD, isoI);
+  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
+  [[maybe_unused]] const bool invert = sweep_invert(isoI);
   const int lane = threadIdx.x & 63;
   const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -407,7 +492,7 @@ __global__ __launch_bounds__(256) void k_classify_rows(const T *__restrict__ vox
     const int k = (int)(t % W);
     const int x = k * 64 + lane;
     bool in = false;
-    if (x < nx) in = !(vox[row * (u64)nx + x] < iso);
+    if (x < nx) in = sweep_one<T, BAND>(vox[row * (u64)nx + x], iso, upper, invert);
     const u64 word = __ballot(in);
     if (lane == 0) {
       bits[t] = word;
@@ -2616,11 +2701,12 @@ __global__ __launch_bounds__(256) void k_emit_cells(EmitArgs a, Grid g, size_t n
 // Every arithmetic step mirrors the ITK 3.x contract I3..I9 in the same
 // operation order as the oracle, so the float coordinates come out bit-identical.
 // ---------------------------------------------------------------------------------------------
-template <class T, bool PAD = false, bool REGION = false>
+template <class T, bool PAD = false, bool REGION = false, bool BAND = false>
 struct Sampler {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
+  __device__ __forceinline__ T map(T v) const { return v; }       // (what a loaded pixel stands for: itself; see the BAND form)
   __device__ __forceinline__ int zlocal(int zg) const {          // global z -> buffer slice
     const int z = zg - zglob0;
     return z < 0 ? 0 : (z > nzb - 1 ? nzb - 1 : z);
@@ -2641,11 +2727,12 @@ struct Sampler {
 // the padded frame; vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels.  Voxel p is vox[p - 1] where
 // 1 <= p <= n - 2 on every axis and `ring` elsewhere.
 template <class T>
-struct Sampler<T, true, false> {
+struct Sampler<T, true, false, false> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
   T ring;
+  __device__ __forceinline__ T map(T v) const { return v; }
   __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
   __device__ __forceinline__ T at_buffer(int x, int y, int z) const {   // positions inside the padded frame
     // (unsigned compare: p - 1 in [0, n - 3])
@@ -2672,13 +2759,35 @@ struct Sampler<T, true, false> {
 // cropped copy; vox points at the box's first voxel and rows / slices lie rowS / sliceS voxels apart -- the buffer's Nx and
 // Nx * Ny.  Nothing outside the box is ever addressed.
 template <class T>
-struct Sampler<T, false, true> {
+struct Sampler<T, false, true, false> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
   long long rowS, sliceS;
+  __device__ __forceinline__ T map(T v) const { return v; }
   __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
   __device__ __forceinline__ T at(int x, int y, int zg) const { return vox[zlocal(zg) * sliceS + y * rowS + x]; }
+  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
+    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
+    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
+    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
+    return at(x, y, zg);
+  }
+};
+
+// cuberille_set_band: the image the walk sees is B = (lower <= pixel && pixel <= upper) ? inside : outside, what
+// itk::BinaryThresholdImageFilter makes of the volume, and B is not stored: every pixel the walk loads -- the 12 row segments
+// of an interior cell like the clamped taps -- becomes one of the two values, in T, before any conversion or arithmetic.  A NaN
+// pixel fails both comparisons and is `outside`.  A whole volume (zglob0 = 0, gnz = nzb), no ring, no pitches.
+template <class T>
+struct Sampler<T, false, false, true> {
+  const T *vox;
+  int nx, ny, nzb;
+  int zglob0, gnz;
+  T lower, upper, inside, outside;
+  __device__ __forceinline__ T map(T v) const { return (lower <= v && v <= upper) ? inside : outside; }
+  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
+  __device__ __forceinline__ T at(int x, int y, int zg) const { return map(vox[((size_t)zlocal(zg) * ny + y) * nx + x]); }
   __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
     x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
     y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
@@ -2778,8 +2887,8 @@ __device__ __forceinline__ void gradient_from_taps(const Geo &geo, bool dirIdent
   }
 }
 
-template <class T, bool PAD = false, bool REGION = false>
-__device__ __forceinline__ void gradient_at(const Sampler<T, PAD, REGION> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
+template <class T, bool PAD = false, bool REGION = false, bool BAND = false>
+__device__ __forceinline__ void gradient_at(const Sampler<T, PAD, REGION, BAND> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
                                             float f0, float out[3]) {
   float fm[3], fp[3];
 #pragma unroll
@@ -2845,8 +2954,8 @@ __device__ __forceinline__ void cell_gradients(const Geo &geo, bool dirIdentity,
 // moved back by one voxel per axis, with the buffer's own row and slice pitch.  Only cells that touch the implied ring
 // take the clamped forms, whose taps go through Sampler::at_buffer.
 // REGION (cuberille_set_region): positions are those of the box, whose rows and slices lie the BUFFER's pitch apart in memory.
-template <class T, bool LITERAL, bool PAD = false, bool REGION = false>
-__device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
+template <class T, bool LITERAL, bool PAD = false, bool REGION = false, bool BAND = false>
+__device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
                                             float G[8][3], typename SiteValue<T>::type Vd[8]) {
   const bool unit = c.lo[0] + 1 == c.hi[0] && c.lo[1] + 1 == c.hi[1] && c.lo[2] + 1 == c.hi[2];
   const int zl = c.lo[2] - s.zglob0;              // buffer slice of the cell's lower z
@@ -2880,10 +2989,10 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION> &s, co
         const T *row = base + (zi - 1) * sliceS + (yi - 1) * rowS;
         if (zin && yin) {
 #pragma unroll
-          for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = row[xi - 1];
+          for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = s.map(row[xi - 1]);
         } else {
-          V[zi][yi][1] = row[0];
-          V[zi][yi][2] = row[1];
+          V[zi][yi][1] = s.map(row[0]);
+          V[zi][yi][2] = s.map(row[1]);
         }
       }
     cell_gradients<T, LITERAL>(geo, dirIdentity, V, G, Vd);
@@ -2924,10 +3033,10 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION> &s, co
         else row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
         if (zin && yin) {
 #pragma unroll
-          for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = row[xs[xi]];
+          for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = s.map(row[xs[xi]]);
         } else {
-          V[zi][yi][1] = row[xs[1]];
-          V[zi][yi][2] = row[xs[2]];
+          V[zi][yi][1] = s.map(row[xs[1]]);
+          V[zi][yi][2] = s.map(row[xs[2]]);
         }
         }
       }
@@ -2973,12 +3082,21 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION> &s, co
 // MATRICES alone: the start index of the box -- the input's plus the box's place in the buffer, rarely 0 -- stays the three runtime
 // scalars geo.istart in every form (it enters only through integer clamps in make_cell), so that a box of an axis-aligned image keeps
 // the axis-aligned walk.  The other instantiations never read the two pitches.
-template <class T, int MODE, int GEOM, bool PAD = false, bool REGION = false>
+// BAND (cuberille_set_band, MODE 0, a whole volume, PAD and REGION off): every pixel the walk loads is mapped to the band's
+// `inside` or `outside` first (Sampler's BAND form); the two bounds and the two values arrive as four scalars of T in the place
+// of the four arguments above, which that form has no use for -- the other instantiations keep their argument block to the letter.
+template <class T, bool BAND, class A> struct WalkArg { typedef A type; };
+template <class T, class A> struct WalkArg<T, true, A> { typedef T type; };
+
+template <class T, int MODE, int GEOM, bool PAD = false, bool REGION = false, bool BAND = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentityArg,
                                                  float *__restrict__ points, u64 nPoints, u64 nGhost, u64 chunk,
                                                  int REFILL, int xcdRemap, int forceLiteral, Totals *__restrict__ tot,
-                                                 u32 *__restrict__ escList, u32 escCap, int dyn, double padD, long long padI,
-                                                 long long rowPitch, long long slicePitch) {
+                                                 u32 *__restrict__ escList, u32 escCap, int dyn,
+                                                 typename WalkArg<T, BAND, double>::type padD, typename WalkArg<T, BAND, long long>::type padI,
+                                                 typename WalkArg<T, BAND, long long>::type rowPitch,
+                                                 typename WalkArg<T, BAND, long long>::type slicePitch) {
+  // (BAND: the four are lower, upper, inside, outside)
   const int lane = threadIdx.x & 63;
   if (dyn) {
     if (!tot->go) return;
@@ -3013,9 +3131,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   if (wave >= nBatches) return;
   u64 next = 0;                                   // wave-uniform cursor
   const u64 end = ((nBatches - wave + NW - 1) / NW) << lgChunk;
-  Sampler<T, PAD, REGION> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  Sampler<T, PAD, REGION, BAND> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
   if constexpr (PAD) s.ring = iso_as<T>(padD, padI);
   if constexpr (REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
+  if constexpr (BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
   const double iso = (double)iso_as<T>(prm.iso, prm.isoInt);
   unsigned myIters = 0;
@@ -3091,7 +3210,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       }
       if (!escaped) {
       if (c.bc[0] != kc[0] || c.bc[1] != kc[1] || c.bc[2] != kc[2]) {
-        gather_cell<T, false, PAD, REGION>(s, geo, dirIdentity != 0, c, G, Vd);
+        gather_cell<T, false, PAD, REGION, BAND>(s, geo, dirIdentity != 0, c, G, Vd);
 #pragma unroll
         for (int k = 0; k < 3; k++) kc[k] = c.bc[k];
         // all 32 cached numbers finite?  x*0 accumulates to 0 for finite x, to NaN for an infinity or a NaN
@@ -3104,7 +3223,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
           for (int k = 0; k < 3; k++) tf = __builtin_fmaf(G[counter][k], 0.0f, tf);
         }
         cellFinite = (tf == 0.0f) && (td == 0.0);
-        if (!cellFinite) gather_cell<T, true, PAD, REGION>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
+        if (!cellFinite) gather_cell<T, true, PAD, REGION, BAND>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
 #pragma unroll
         for (int counter = 0; counter < 8; counter++)
 #pragma unroll
@@ -3847,6 +3966,25 @@ static bool ragged_span_path(const Workspace &w, const Grid &g, size_t elem, con
          (u64)g.nx * (u64)g.ny * (u64)g.nzb * (u64)elem >= (256ull << 20) && (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
 }
 
+// a (double, integer) pair in the pixel type, as iso_as does on the device
+template <class T>
+static T value_as(double d, long long i) {
+  if constexpr (std::is_integral<T>::value && sizeof(T) == 8) return (T)i;
+  else return (T)d;
+}
+
+// cuberille_set_band: what the band instantiations of the sweep take.  The image B holds two values, so !(B(u) < iso) is
+// `bin` inside the band and `bout` outside it, both evaluated here, in T.  Where they differ the bit is band(u) XOR bout;
+// where they are equal the bit volume is constant and the kernels get the empty band 1 .. 0 with the same inversion.
+template <class T>
+static void band_sweep_args(const Workspace &w, const Params &prm, BandBoundsD &d, BandBoundsI &i) {
+  const T iso = value_as<T>(prm.iso, prm.isoInt);
+  const bool bin = !(value_as<T>(w.bandV[2], w.bandVi[2]) < iso), bout = !(value_as<T>(w.bandV[3], w.bandVi[3]) < iso);
+  if (bin != bout) { d.lower = w.bandV[0]; d.upper = w.bandV[1]; i.lower = w.bandVi[0]; i.upper = w.bandVi[1]; }
+  else { d.lower = 1.0; d.upper = 0.0; i.lower = 1; i.upper = 0; }
+  i.invert = bout ? 1 : 0;
+}
+
 // classify slices [z0, z1) of the buffer (a z-range is a contiguous range of voxels and of words)
 hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g, const Params &prm, int z0, int z1,
                            const Tuning &tn, hipStream_t s) {
@@ -3908,6 +4046,9 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
     });
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+    // (the plain sweep or, with cuberille_set_band, the band instantiations of the same kernels behind the same decisions)
+    auto sweep = [&](auto bandTag, const auto &iso, const auto &isoI) -> hipError_t {
+    constexpr bool BAND = decltype(bandTag)::value;
     Workspace w = wAll;
     const T *vox = (const T *)wAll.vox + (size_t)z0 * g.ny * g.nx;
     w.bits = wAll.bits + (size_t)z0 * g.ny * g.W;
@@ -3928,7 +4069,7 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
         // (eighth spans: 0.086 against 0.0825 ms at 512^3; 384 / 640 / 768 / 1024 workgroups of quarter spans: 0.097 / 0.095 / 0.087 / 0.088)
         const u64 nspans = nwordsAll / (SPAN_WORDS / 4);
         const unsigned blocks = (unsigned)(nspans < want0 ? nspans : want0);
-        hipLaunchKernelGGL((k_classify_span<T, SPAN_WORDS / 4>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, iso, isoI, w.sliceOcc, lg);
+        hipLaunchKernelGGL((k_classify_span<T, SPAN_WORDS / 4, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, iso, isoI, w.sliceOcc, lg);
         spanWords = nwordsAll;
       } else
       if (tn.classify_variant == 0 && nwordsAll * 64 * sizeof(T) >= (256ull << 20)) {
@@ -3939,7 +4080,7 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
         // thirds of a round the rest goes to the plain sweep behind this launch, which runs at four fifths of the rate
         if (nspans > want && (nspans % want) * 3 < want * 2 && !tn.classify_keep_tail) nspans -= nspans % want;
         const unsigned blocks = (unsigned)(nspans < want ? nspans : want);
-        hipLaunchKernelGGL((k_classify_span<T>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, iso, isoI, w.sliceOcc, lg);
+        hipLaunchKernelGGL((k_classify_span<T, SPAN_WORDS, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, iso, isoI, w.sliceOcc, lg);
         spanWords = nspans * SPAN_WORDS;
       }
       const u64 restWords = nwordsAll - spanWords;
@@ -3947,11 +4088,11 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       if (nchunks) {
         // 256 CUs x 8 blocks of 256 threads; grid-stride over the rest; 8 KiB per wave trip, nontemporal
         const unsigned blocks = grid_for((nchunks + 7) / 8 * 64, 256, tn.classify_grid > 0 ? tn.classify_grid : 2048);
-        hipLaunchKernelGGL((k_classify_flat<T, 8, true>), dim3(blocks), dim3(256), 0, s, vox + spanWords * 64, w.bits + spanWords,
+        hipLaunchKernelGGL((k_classify_flat<T, 8, true, BAND>), dim3(blocks), dim3(256), 0, s, vox + spanWords * 64, w.bits + spanWords,
                            nchunks, iso, isoI, w.sliceOcc, lg, spanWords);
       }
       if (spanWords + nchunks * VPL < nwordsAll)
-        hipLaunchKernelGGL((k_classify_rows<T>), dim3(1), dim3(256), 0, s, vox, w.bits, g.nx, g.W, spanWords + nchunks * VPL, nrows,
+        hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(1), dim3(256), 0, s, vox, w.bits, g.nx, g.W, spanWords + nchunks * VPL, nrows,
                            (u64)g.ny, iso, isoI, w.sliceOcc);
     } else if (ragged_span_path(wAll, g, sizeof(T), tn)) {
       const u64 nwordsAll = nrows * g.W;
@@ -3961,7 +4102,7 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       //  are 8 rounds of 489 rather than 7 of 512 and one of 323, whose time is a whole round's)
       const u64 rounds = (nspans + want - 1) / want;
       const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
-      hipLaunchKernelGGL((k_classify_span_rows<T>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, nwordsAll, g.nx, g.W, (u32)g.ny,
+      hipLaunchKernelGGL((k_classify_span_rows<T, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, nwordsAll, g.nx, g.W, (u32)g.ny,
                          iso, isoI, w.sliceOcc);
     } else if (ragged_stream_path(wAll, g, sizeof(T), tn)) {
       // ragged rows: flat stream of aligned 16-byte vectors (the first and last vector may reach up to 15 bytes
@@ -3978,18 +4119,26 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
         // (the 32-KiB-in-flight geometry of the span kernel does not carry over: this loop waits for all its loads before
         //  it computes, 0.74 ms at U4 x 1024 workgroups vs 0.745 at U8 x 2048 on 1000^3 f32)
         const unsigned blocks = grid_for((nchunks + 7) / 8 * 64, 256, 2048);
-        hipLaunchKernelGGL((k_classify_flat<T, 8, true>), dim3(blocks), dim3(256), 0, s, abase, flat, nchunks, iso, isoI,
+        hipLaunchKernelGGL((k_classify_flat<T, 8, true, BAND>), dim3(blocks), dim3(256), 0, s, abase, flat, nchunks, iso, isoI,
                            (u32 *)nullptr, -1, (u64)0);
       }
-      if (nvec % 64) hipLaunchKernelGGL((k_classify_tail<T>), dim3(1), dim3(64), 0, s, abase, flat, nchunks * 64, nvec, iso, isoI);
+      if (nvec % 64) hipLaunchKernelGGL((k_classify_tail<T, BAND>), dim3(1), dim3(64), 0, s, abase, flat, nchunks * 64, nvec, iso, isoI);
       hipLaunchKernelGGL(k_repack_rows, dim3(grid_for(nrows * g.W, 256, 0)), dim3(256), 0, s, flat, w.bits, g.nx, g.W, nrows, skew);
     } else {
       const u64 total = nrows * g.W;
       const unsigned blocks = grid_for(total * 64, 256, 8192);
-      hipLaunchKernelGGL((k_classify_rows<T>), dim3(blocks), dim3(256), 0, s, vox, w.bits, g.nx, g.W, (u64)0, nrows,
+      hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, g.nx, g.W, (u64)0, nrows,
                          (u64)g.ny, iso, isoI, w.sliceOcc);
     }
     return hipGetLastError();
+    };
+    if (wAll.band) {
+      BandBoundsD bd;
+      BandBoundsI bi;
+      band_sweep_args<T>(wAll, prm, bd, bi);
+      return sweep(std::true_type(), bd, bi);
+    }
+    return sweep(std::false_type(), iso, isoI);
   });
 }
 
@@ -4353,11 +4502,23 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     hipLaunchKernelGGL((k_project<T, MODE, GEOM, PAD, REGION>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
                        w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
                        w.escCap, dyn, w.padValue, w.padValueInt, w.rowPitch, w.slicePitch)
+#define CUBERILLE_LAUNCH_PROJECT_BAND(GEOM)                                                                                  \
+    hipLaunchKernelGGL((k_project<T, 0, GEOM, false, false, true>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
+                       w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
+                       w.escCap, dyn, bandTail[0], bandTail[1], bandTail[2], bandTail[3])
 #define CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, PAD) CUBERILLE_LAUNCH_PROJECT_FRAME(MODE, GEOM, PAD, false)
 #define CUBERILLE_LAUNCH_PROJECT(MODE, GEOM) CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, false)
 #define CUBERILLE_LAUNCH_PROJECT_GEOM(MODE)                                                                                  \
     do { if (geom == 2) CUBERILLE_LAUNCH_PROJECT(MODE, 2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT(MODE, 1);            \
          else CUBERILLE_LAUNCH_PROJECT(MODE, 0); } while (0)
+    if (w.band) {
+      // a whole volume, every slice in the buffer, no ring and no pitches: MODE 0, the only one offered with a band (count_prepare)
+      if (mode != 0 || w.pad || w.region) return hipErrorInvalidValue;
+      const T bandTail[4] = {value_as<T>(w.bandV[0], w.bandVi[0]), value_as<T>(w.bandV[1], w.bandVi[1]),
+                                       value_as<T>(w.bandV[2], w.bandVi[2]), value_as<T>(w.bandV[3], w.bandVi[3])};
+      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_BAND(2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_BAND(1);
+      else CUBERILLE_LAUNCH_PROJECT_BAND(0);
+    } else
     if (w.pad) {
       // a whole volume, every slice in the (implied) buffer: MODE 0, the only one offered with a border (count_prepare)
       if (mode != 0) return hipErrorInvalidValue;
@@ -4377,6 +4538,7 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
 #undef CUBERILLE_LAUNCH_PROJECT
 #undef CUBERILLE_LAUNCH_PROJECT_PAD
 #undef CUBERILLE_LAUNCH_PROJECT_FRAME
+#undef CUBERILLE_LAUNCH_PROJECT_BAND
     return hipGetLastError();
   });
 }

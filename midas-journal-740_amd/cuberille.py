@@ -130,6 +130,34 @@ def check_border(pixel_type, border):
         raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "the border value is not representable in the pixel type")
 
 
+def _band_arrays(band):
+    """(lower, upper, inside, outside) as the two arrays cuberille_set_band / cuberille_band_check take: doubles, and the
+    64 bits a 64-bit integer pixel type would hold (a uint64 past 2^63 wraps, like the iso value)."""
+    exact = [iso_int_of(x) for x in band]
+    v = (C.c_double * 4)(*[float(x) for x in band])
+    vi = (C.c_int64 * 4)(*[0 if e is None else ((e + (1 << 63)) % (1 << 64)) - (1 << 63) for e in exact])
+    return v, vi, exact
+
+
+def check_band(pixel_type, band):
+    """(lower, upper, inside, outside) of Extractor.set_band against a pixel type (cuberille_band_check, no GPU): raises what
+    the library would at the extraction -- ERR_ARGUMENT for a value the pixel type does not hold (outside its range, or a
+    fraction for an integer type), for lower > upper and for a NaN bound.  band None: nothing to check."""
+    if band is None:
+        return
+    v, vi, exact = _band_arrays(band)
+    if int(pixel_type) in (8, 9):
+        # (the library judges the range of the 64-bit integer types by the double; a Python integer says it exactly)
+        lo, hi = (-(1 << 63), 1 << 63) if int(pixel_type) == 8 else (0, 1 << 64)
+        for e in exact:
+            if e is None or not (lo <= e < hi):
+                raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "band (cuberille_set_band): a value is not representable in the pixel type")
+    rc = _abi.lib().cuberille_band_check(int(pixel_type), v, vi)
+    if rc:
+        text = _abi.lib().cuberille_last_error(None)      # (the library's own words, kept per thread)
+        raise _abi.CuberilleError(rc, text.decode() if text else "")
+
+
 def region_desc(desc, start_xyz, size_xyz):
     """The description of the box [start, start + size) of the buffer `desc` describes (cuberille_region_desc, no GPU): dims
     = size, index_start = the buffer's + start, the same origin, spacing and direction -- the image
@@ -408,6 +436,20 @@ class Extractor:
         _abi.check(self._ctx, self._lib.cuberille_set_border(self._ctx, int(width), float(value), as_int))
         self._border = (int(width), exact)
 
+    def set_band(self, lower, upper, inside=1, outside=0):
+        """Mesh a label or a value band in place (cuberille_set_band): every later whole-volume extraction gives the mesh of
+        B = (lower <= pixel <= upper) ? inside : outside -- what itk::BinaryThresholdImageFilter hands the reference, all four
+        values in the pixel type, a NaN pixel outside -- bit for bit, without B: the sweep evaluates the band, the walk maps
+        every pixel it loads.  The iso value and all other parameters stay the caller's and apply to B.  The values are checked
+        against the pixel type at the extraction (check_band).  Slabs, steps, groups, extract_stream, set_border, set_region,
+        the B-spline interpolator, a held or recursive-Gaussian gradient and the two projection variants are refused there."""
+        v, vi, _ = _band_arrays((lower, upper, inside, outside))
+        _abi.check(self._ctx, self._lib.cuberille_set_band(self._ctx, 1, v, vi))
+
+    def clear_band(self):
+        """Back to the default: the pixels are thresholded against the iso value themselves."""
+        _abi.check(self._ctx, self._lib.cuberille_set_band(self._ctx, 0, None, None))
+
     def set_region(self, start_xyz, size_xyz):
         """Extract a box of a larger volume in place (cuberille_set_region): every later whole-volume extraction still takes
         the description and the pointer of the WHOLE buffer and gives the mesh of the box [start, start + size) -- that of
@@ -598,6 +640,14 @@ class ExtractorGroup:
             ctx = self.context(i)
             _abi.check(ctx, self._lib.cuberille_set_border(ctx, int(width), float(value), 0))
 
+    def set_band(self, lower, upper, inside=1, outside=0):
+        """A band (Extractor.set_band) on every member: the group's extraction then raises the library's refusal -- the binary
+        image belongs to one context's whole volume."""
+        v, vi, _ = _band_arrays((lower, upper, inside, outside))
+        for i in range(len(self.devices)):
+            ctx = self.context(i)
+            _abi.check(ctx, self._lib.cuberille_set_band(ctx, 1, v, vi))
+
     def set_region(self, start_xyz, size_xyz):
         """A region (Extractor.set_region) on every member: the group's extraction then raises the library's refusal -- a
         box belongs to one context's whole volume."""
@@ -663,6 +713,13 @@ class CuberilleImageToMeshFilter:
     Input: mha.Volume (host memory, like the itk::Image the reference driver hands
     over).  Output: Mesh with the reference's vertex ids, cell order and coordinates.
     """
+
+    # The band's state alone is held at class level, not in __init__ with the rest: Update() reads it on every call, and
+    # tests/test_region.py::test_python_filter_index_arithmetic runs Update() on a filter made by __new__ with only the
+    # attributes set that Update() read before the band existed.  An instance's setters shadow these; none is mutable.
+    _band_on = False                              # InsideBandOn: off, like the reference
+    _band = (0, 0)                                # SetInsideBand: lower, upper
+    _band_values = (1, 0)                         # SetBandValues: NumericTraits<InputPixelType>::One / Zero
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -879,6 +936,24 @@ class CuberilleImageToMeshFilter:
         s = getattr(vol, "index_start", (0, 0, 0))
         return tuple(int(i) - int(b) for i, b in zip(self._region[0], s)), self._region[1]
 
+    def SetInsideBand(self, lower, upper):
+        """Not in the reference -- what a caller does there with itk::BinaryThresholdImageFilter first: with InsideBandOn(),
+        mesh the binary image (lower <= pixel <= upper) ? inside : outside as if that filter's output were the input; the iso
+        value applies to it.  No thresholded copy is made (cuberille_set_band)."""
+        self._band = (lower, upper)
+
+    def SetBandValues(self, inside, outside):
+        self._band_values = (inside, outside)
+
+    def InsideBandOn(self):
+        self._band_on = True
+
+    def InsideBandOff(self):
+        self._band_on = False
+
+    def GetInsideBand(self):
+        return self._band_on
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -894,6 +969,12 @@ class CuberilleImageToMeshFilter:
         if len(self._devices) > 1 and self._region is not None:
             raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "a region (SetExtractionRegion / cuberille_set_region) is not "
                                       "offered in a group: a box belongs to one context's whole volume")
+        if len(self._devices) > 1 and self._band_on:
+            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "a band (InsideBandOn / cuberille_set_band) is not offered in a "
+                                      "group: the binary image belongs to one context's whole volume")
+        if self._band_on:
+            # (before a device is touched: the four values against the input's pixel type)
+            check_band(int(self._group_desc(self._input).pixel_type), self._band + self._band_values)
         if self._region is not None:
             # (before a device is touched: the box against the input's buffered region)
             check_region(self._group_desc(self._input), self._buffer_region(self._input))
@@ -921,6 +1002,10 @@ class CuberilleImageToMeshFilter:
             self._extractor.set_region(*self._buffer_region(vol))
         else:
             self._extractor.clear_region()
+        if self._band_on:
+            self._extractor.set_band(*(self._band + self._band_values))
+        else:
+            self._extractor.clear_band()
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
         self.last_number_of_slabs = 1

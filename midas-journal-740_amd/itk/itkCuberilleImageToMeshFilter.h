@@ -244,6 +244,34 @@ public:
   const RegionType &GetExtractionRegion() const { return m_ExtractionRegion; }
   bool HasExtractionRegion() const { return m_HasExtractionRegion; }
 
+  /** Not in the reference -- what a caller does there with itk::BinaryThresholdImageFilter first (the reference's own driver
+   *  holds that filter ready, test:80,126-132).  SetInsideBand(lower, upper) + InsideBandOn(): Update() gives the mesh the
+   *  filter gives for the output of itk::BinaryThresholdImageFilter<TInputImage, TInputImage> with those thresholds and
+   *  the inside / outside values of SetBandValues (defaults NumericTraits<InputPixelType>::One / Zero, not the threshold
+   *  filter's max / zero: a label mask) -- (lower <= pixel && pixel <= upper) ? inside : outside, a NaN pixel outside -- the
+   *  same points, bit for bit, and cells as threshold-then-filter; the iso value applies to that binary image.  No
+   *  thresholded copy of the image is made, on the host or on the device (cuberille_set_band).  lower > upper makes Update()
+   *  throw, as the threshold filter does.  Offered where the device walks (or nothing is projected): with SetDevices of
+   *  more than one device, the B-spline interpolator, ReproduceStaleGradient, PadBorderOn(), SetExtractionRegion, the
+   *  compiled-out projection / gradient variants or an interpolator that takes the host walk (the user's object is bound
+   *  to the image, not to the binary one) Update() throws with the library's message.  Default off: the reference's
+   *  behaviour. */
+  void SetInsideBand(InputPixelType lower, InputPixelType upper)
+    {
+    if (m_BandLower != lower || m_BandUpper != upper) { m_BandLower = lower; m_BandUpper = upper; this->Modified(); }
+    }
+  void SetBandValues(InputPixelType inside, InputPixelType outside)
+    {
+    if (m_BandInside != inside || m_BandOutside != outside) { m_BandInside = inside; m_BandOutside = outside; this->Modified(); }
+    }
+  itkGetMacro(InsideBand, bool);
+  itkSetMacro(InsideBand, bool);
+  itkBooleanMacro(InsideBand);
+  InputPixelType GetBandLower() const { return m_BandLower; }
+  InputPixelType GetBandUpper() const { return m_BandUpper; }
+  InputPixelType GetBandInsideValue() const { return m_BandInside; }
+  InputPixelType GetBandOutsideValue() const { return m_BandOutside; }
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -286,6 +314,10 @@ private:
   InputPixelType m_BorderPadValue;
   RegionType m_ExtractionRegion;
   bool m_HasExtractionRegion;
+  bool m_InsideBand;
+  InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
+  void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them
+  void ApplyBand(::cuberille_ctx *ctx) const;   // cuberille_set_band on ctx from the four members (or off); throws on a refusal
   double m_LastDeviceSeconds;
   double m_LastMeshFillSeconds;
   double m_LastExtractSeconds;

@@ -500,6 +500,10 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_PadBorder = false;
   m_HasExtractionRegion = false;
   m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
+  m_InsideBand = false;
+  m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
+  m_BandInside = NumericTraits<InputPixelType>::One;
+  m_BandOutside = NumericTraits<InputPixelType>::Zero;
   m_LastDeviceSeconds = 0.0;
   m_LastMeshFillSeconds = 0.0;
   m_LastExtractSeconds = 0.0;
@@ -590,6 +594,28 @@ bool CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Acquir
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
+void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::BandArguments(double v[4], int64_t vi[4]) const
+{
+  const InputPixelType t[4] = {m_BandLower, m_BandUpper, m_BandInside, m_BandOutside};
+  for (int k = 0; k < 4; k++)
+    {
+    v[k] = static_cast<double>(t[k]);
+    vi[k] = cuberille_detail::IsoInt<InputPixelType>::Get(t[k]);
+    }
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::ApplyBand(::cuberille_ctx *ctx) const
+{
+  double v[4];
+  int64_t vi[4];
+  this->BandArguments(v, vi);
+  // (a refusal would leave the context's previous band in force: reported, like the border's and the region's)
+  if (cuberille_set_band(ctx, m_InsideBand ? 1 : 0, m_InsideBand ? v : 0, m_InsideBand ? vi : 0) != CUBERILLE_OK)
+    itkExceptionMacro(<< "cuberille_set_band: " << cuberille_last_error(ctx));
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
 void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetInput(const InputImageType *image)
 {
   this->ProcessObject::SetNthInput(0, const_cast<InputImageType *>(image));
@@ -675,6 +701,20 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "an implied border (PadBorderOn / cuberille_set_border) is not offered with an interpolator that takes "
                          "the host walk: the caller's interpolator object is bound to the unpadded image");
 
+  // InsideBandOn(): the four values against the pixel type by the library's validator (lower > upper: the threshold filter
+  // throws there too), and on the device's walk
+  if (m_InsideBand)
+    {
+    double v[4];
+    int64_t vi[4];
+    this->BandArguments(v, vi);
+    if (cuberille_band_check(desc.pixel_type, v, vi) != CUBERILLE_OK)
+      itkExceptionMacro(<< "InsideBandOn: " << cuberille_last_error(0));
+    if (hostWalk)
+      itkExceptionMacro(<< "a band (InsideBandOn / cuberille_set_band) is not offered with an interpolator that takes the host "
+                           "walk: the caller's interpolator object is bound to the image, not to the binary one");
+    }
+
   // SetExtractionRegion: ITK index space -> a position in the buffer; inside the buffered region, and on the device's walk
   int64_t boxStart[3] = {0, 0, 0}, boxSize[3] = {0, 0, 0};
   if (m_HasExtractionRegion)
@@ -712,6 +752,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     for (int i = 0; i < static_cast<int>(m_Devices.size()); i++)
       (void)cuberille_set_border(cuberille_group_context(m_Group, i), m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
                                  cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
+    // (... and a band: the same)
+    for (int i = 0; i < static_cast<int>(m_Devices.size()); i++) this->ApplyBand(cuberille_group_context(m_Group, i));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_group_extract_host: " << cuberille_group_last_error(m_Group));
@@ -733,6 +775,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< "cuberille_set_border: " << cuberille_last_error(m_Context));
     if (cuberille_set_region(m_Context, boxStart, boxSize) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_region: " << cuberille_last_error(m_Context));
+    this->ApplyBand(m_Context);
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
