@@ -112,6 +112,7 @@ struct cuberille_ctx {
   int interp = CUBERILLE_INTERP_LINEAR;  // cuberille_set_interpolator: the value interpolator of later walks ...
   int bsBits = 0;                        // ... and, for the B-spline, its coordinate / coefficient width (32 or 64)
   DevBuf bsCoef, bsScratch;              // the B-spline coefficient image, and the double scratch of its passes (32-bit only)
+  // the three source-view settings, each as its setter left it; resolve_view makes one View of them per extraction
   int padWidth = 0;                      // cuberille_set_border: voxels of constant border implied around every later whole volume
   double padValue = 0.0;                 // ... and their value, which travels like the iso value
   long long padValueInt = 0;
@@ -121,8 +122,6 @@ struct cuberille_ctx {
   bool regionOn = false;                 // cuberille_set_region: every later whole-volume extraction meshes this box of its buffer ...
   int64_t regionStart[3] = {0, 0, 0};    // ... its first voxel, as a position in the buffer (x, y, z) ...
   int64_t regionSize[3] = {0, 0, 0};     // ... and its size
-  bool regionApplied = false;            // inside cuberille_extract_host: the box has been uploaded on its own, the description
-                                         // handed on is the box's already
   int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
@@ -236,7 +235,7 @@ void invert3(const double m[9], double inv[9]) {
 // cuberille_region_desc: the description of the box [start, start + size) of the buffer `img` describes -- what the reference
 // is given after itk::ExtractImageFilter / RegionOfInterestImageFilter with the index kept: the box's size, its start index the
 // buffer's plus the box's place in it, the same origin, spacing and direction.  The single validator of a box: the public symbol,
-// validate(), count_prepare and cuberille_warm_up all come here.  *why: the text of a refusal.
+// resolve_view and cuberille_set_region come here.  *why: the text of a refusal.
 int region_check(const cuberille_image_desc *img, const int64_t start[3], const int64_t size[3], cuberille_image_desc *out,
                  const char **why) {
   const char *dummy;
@@ -323,6 +322,22 @@ int band_check(int pixel_type, const double v[4], const int64_t vi[4], const cha
   return CUBERILLE_OK;
 }
 
+// Does a value that travels as a double (the iso value, the ring's) convert to the pixel type without leaving its range?  (The
+// 8- to 32-bit integer types; a fraction is cut off like a C cast does.  The other types take any double.)
+bool converts(int pixel_type, double v) {
+  double lo = 0.0, hi = 0.0;
+  switch (pixel_type) {
+    case CUBERILLE_PIX_U8: hi = 255.0; break;
+    case CUBERILLE_PIX_I8: lo = -128.0; hi = 127.0; break;
+    case CUBERILLE_PIX_U16: hi = 65535.0; break;
+    case CUBERILLE_PIX_I16: lo = -32768.0; hi = 32767.0; break;
+    case CUBERILLE_PIX_U32: hi = 4294967295.0; break;
+    case CUBERILLE_PIX_I32: lo = -2147483648.0; hi = 2147483647.0; break;
+    default: break;
+  }
+  return hi == lo || (v > lo - 1.0 && v < hi + 1.0);
+}
+
 int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!img || !vox || !prm) return fail(c, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
@@ -352,112 +367,10 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
     if (c->holdGradient)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is not offered on a context holding a gradient (cuberille_hold_gradient)");
   }
-  // the iso value is an InputPixelType in the reference (h:180-181): for the integer pixel types it must convert
-  // without leaving the type's range (a fraction is cut off like a C cast does)
-  double lo = 0.0, hi = 0.0;
-  switch (img->pixel_type) {
-    case CUBERILLE_PIX_U8: hi = 255.0; break;
-    case CUBERILLE_PIX_I8: lo = -128.0; hi = 127.0; break;
-    case CUBERILLE_PIX_U16: hi = 65535.0; break;
-    case CUBERILLE_PIX_I16: lo = -32768.0; hi = 32767.0; break;
-    case CUBERILLE_PIX_U32: hi = 4294967295.0; break;
-    case CUBERILLE_PIX_I32: lo = -2147483648.0; hi = 2147483647.0; break;
-    default: lo = hi = 0.0; break;
-  }
-  if (hi != lo && !(prm->iso_value > lo - 1.0 && prm->iso_value < hi + 1.0))
+  // the iso value is an InputPixelType in the reference (h:180-181)
+  if (!converts(img->pixel_type, prm->iso_value))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
-  if (c->regionOn && !c->regionApplied) {
-    // cuberille_set_region: the box against this buffer, and what would need a second image of the box's shape (coefficients, a
-    // gradient image) or is simply not part of the setting
-    if (c->padWidth)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) together with an implied border (cuberille_set_border) is not offered: the box's faces inside the buffer would need a ring of their own");
-    cuberille_image_desc box;
-    const char *why = "";
-    const int rrc = region_check(img, c->regionStart, c->regionSize, &box, &why);
-    if (rrc) return fail(c, rrc, why);
-    if (prm->project_vertices) {
-      if (c->interp == CUBERILLE_INTERP_BSPLINE)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered with the B-spline interpolator: its coefficient image would be the box's");
-      if (c->holdGradient)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
-      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would be the box's");
-      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is offered with the default projection branch only (txx:439-474)");
-    }
-  }
-  if (c->bandOn) {
-    // cuberille_set_band: the four values against THIS image's pixel type, and what would need the binary image B in a second
-    // image (coefficients, a gradient image) or is simply not part of the setting -- the border's list, for the border's reasons
-    const char *why = "";
-    const int brc = band_check(img->pixel_type, c->bandV, (const int64_t *)c->bandVi, &why);
-    if (brc) return fail(c, brc, why);
-    if (c->padWidth)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) together with an implied border (cuberille_set_border) is not offered: the ring's value would have to be one of the band's two");
-    if (c->regionOn)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) together with a region (cuberille_set_region) is not offered: the pitched sweep and walk have no band form");
-    if (prm->project_vertices) {
-      if (c->interp == CUBERILLE_INTERP_BSPLINE)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered with the B-spline interpolator: its coefficient image would be the binary image's");
-      if (c->holdGradient)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
-      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would be the binary image's");
-      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is offered with the default projection branch only (txx:439-474)");
-    }
-  }
-  if (c->padWidth) {
-    // cuberille_set_border: the limits above hold for the image with its ring, the ring's value converts like the iso value, and
-    // what would need the ring in a second image (coefficients, a gradient image) is not offered
-    for (int i = 0; i < 3; i++) {
-      if (img->dims[i] + 2 * c->padWidth > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_LIMIT, "image dimension with its border exceeds 2^31-1");
-      if (img->index_start[i] - c->padWidth < -(1LL << 30))
-        return fail(c, CUBERILLE_ERR_LIMIT, "the bordered region's start index must lie within +-2^30");
-    }
-    if (hi != lo && !(c->padValue > lo - 1.0 && c->padValue < hi + 1.0))
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "the border value (cuberille_set_border) is not representable in the pixel type");
-    if (prm->project_vertices) {
-      if (c->interp == CUBERILLE_INTERP_BSPLINE)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is not offered with the B-spline interpolator: its coefficient image would need the ring");
-      if (c->holdGradient)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is not offered on a context holding a gradient image (cuberille_hold_gradient)");
-      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is offered with the central-difference gradient only: the recursive-Gaussian gradient image would need the ring");
-      if (prm->projection_variant != CUBERILLE_PROJECT_DEFAULT)
-        return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) is offered with the default projection branch only (txx:439-474)");
-    }
-  }
   return CUBERILLE_OK;
-}
-
-// cuberille_set_border: the description of the image with its ring of c->padWidth constant voxels -- what the reference is
-// given after itk::ConstantPadImageFilter: the region grown by the pad on every side, its start index moved down by it, the
-// same origin, spacing and direction -- or the caller's own with the setting off.  The one place the two frames meet: the
-// layout, the geometry and every workspace size follow from this description, the sweep and the walk alone read the
-// caller's buffer (Workspace::pad).
-cuberille_image_desc bordered(const cuberille_ctx *c, const cuberille_image_desc *img) {
-  cuberille_image_desc d = *img;
-  for (int i = 0; i < 3; i++) {
-    d.dims[i] += 2 * c->padWidth;
-    d.index_start[i] -= c->padWidth;
-  }
-  return d;
-}
-
-// Is a box in force for the description an entry point was handed?  (Not inside cuberille_extract_host behind its upload of the
-// box: what travels on from there IS the box.)
-bool boxed(const cuberille_ctx *c) { return c->regionOn && !c->regionApplied; }
-
-// The frame the layout, the geometry and every workspace size follow from: the caller's image, with its implied ring
-// (cuberille_set_border) or cut to its box (cuberille_set_region; validate() has passed the box, and refuses the two together).
-cuberille_image_desc framed_desc(const cuberille_ctx *c, const cuberille_image_desc *img) {
-  if (boxed(c)) {
-    cuberille_image_desc d;
-    if (region_check(img, c->regionStart, c->regionSize, &d, nullptr) == CUBERILLE_OK) return d;
-    return *img;
-  }
-  return bordered(c, img);
 }
 
 }  // namespace
@@ -599,6 +512,152 @@ void resolve(const cuberille_image_desc *img, const cuberille_params *prm, Geo &
   p.gradVariant = prm->gradient_variant;
 }
 
+// ---- source views: cuberille_set_border, cuberille_set_region and cuberille_set_band as one kind of setting -----------------
+// The entry points that differ in what they offer of a view.  ROUTE_HOST: cuberille_extract_host, which uploads a box alone.
+// ROUTE_WARM_UP only reserves: it looks at what changes a size (the border, the region), not at the band nor at the parameters.
+enum Route { ROUTE_DEVICE, ROUTE_HOST, ROUTE_SLAB, ROUTE_STEP, ROUTE_STREAM, ROUTE_GROUP, ROUTE_WARM_UP, N_ROUTES };
+
+// The one table of what is not offered: per kind its name in words and as the C function, the reason per route (null: offered)
+// and what a second image of the view's shape -- B-spline coefficients, a gradient image -- would have to be.
+struct ViewWords {
+  const char *noun, *fn;
+  const char *route[N_ROUTES];
+  const char *second;
+};
+const ViewWords kViewWords[4] = {
+    {"", "", {}, ""},
+    {"an implied border", "cuberille_set_border",
+     {nullptr, nullptr, " belongs to a whole volume: not offered on slabs",
+      " would have to reach across ranks: not offered with the cuberille_step_* calls", nullptr,
+      "the ring would have to reach across slabs, not offered in a group", nullptr},
+     "need the ring"},
+    {"a region", "cuberille_set_region",
+     {nullptr, nullptr, " is a box of a whole volume: not offered on slabs",
+      " is a box of one context's whole volume: not offered with the cuberille_step_* calls",
+      " is not offered with cuberille_extract_stream: the source produces whole slices",
+      "a box of one context's whole volume, not offered in a group", nullptr},
+     "be the box's"},
+    {"a band", "cuberille_set_band",
+     {nullptr, nullptr, " belongs to a whole volume: not offered on slabs",
+      " belongs to one context's whole volume: not offered with the cuberille_step_* calls",
+      " is not offered with cuberille_extract_stream", "it belongs to one context's whole volume, not offered in a group", nullptr},
+     "be the binary image's"},
+};
+// ... and why two of them do not go together, [the later kind][the earlier one]
+const char *const kViewPairs[4][4] = {
+    {}, {},
+    {nullptr, "the box's faces inside the buffer would need a ring of their own"},
+    {nullptr, "the ring's value would have to be one of the band's two", "the pitched sweep and walk have no band form"},
+};
+
+// cuberille_set_border against an image: the limits of validate() hold for the image with its ring, and the ring's value converts
+// like the iso value (a fraction is cut off like a C cast does, the range is the pixel type's)
+int border_check(const cuberille_image_desc *img, int padWidth, double padValue, bool value, const char **why) {
+  for (int i = 0; i < 3; i++) {
+    if (img->dims[i] + 2 * padWidth > 0x7fffffffLL) { *why = "image dimension with its border exceeds 2^31-1"; return CUBERILLE_ERR_LIMIT; }
+    if (img->index_start[i] - padWidth < -(1LL << 30)) { *why = "the bordered region's start index must lie within +-2^30"; return CUBERILLE_ERR_LIMIT; }
+  }
+  if (value && !converts(img->pixel_type, padValue)) {
+    *why = "the border value (cuberille_set_border) is not representable in the pixel type";
+    return CUBERILLE_ERR_ARGUMENT;
+  }
+  return CUBERILLE_OK;
+}
+
+// The frame the layout, the geometry and every workspace size follow from -- what the reference would be handed: the caller's
+// image; with its ring (after itk::ConstantPadImageFilter: the region grown by one on every side, its start index moved down by
+// one); or cut to its box (cuberille_region_desc); origin, spacing and direction the same.  The sweep and the walk alone read
+// the caller's buffer.
+cuberille_image_desc framed_desc(const View &v, const cuberille_image_desc *img) {
+  cuberille_image_desc d = *img;
+  if (v.kind == VIEW_BORDER)
+    for (int i = 0; i < 3; i++) { d.dims[i] += 2; d.index_start[i] -= 1; }
+  if (v.kind == VIEW_REGION) {
+    const int64_t start[3] = {v.start[0], v.start[1], v.start[2]}, size[3] = {v.size[0], v.size[1], v.size[2]};
+    if (region_check(img, start, size, &d, nullptr) != CUBERILLE_OK) return *img;     // (resolve_view has passed the box)
+  }
+  return d;
+}
+
+// A region whose box has been uploaded on its own (cuberille_extract_host): `box` describes the device copy, contiguous, the
+// pitches are the box's -- what is left of the view is the walk's runtime start index
+View applied_region(const cuberille_image_desc &box) {
+  View v{};
+  v.kind = VIEW_REGION;
+  for (int i = 0; i < 3; i++) v.size[i] = box.dims[i];
+  v.rowPitch = box.dims[0]; v.slicePitch = box.dims[0] * box.dims[1];
+  return v;
+}
+
+// What of the parameters a view's refusals depend on (resolve() fills the rest, from the frame)
+Params projection_features(const cuberille_params *prm) {
+  Params p{};
+  p.project = prm->project_vertices != 0;
+  p.variant = prm->projection_variant;
+  p.gradVariant = prm->gradient_variant;
+  return p;
+}
+
+// The settings of a context against an image on a route: one View, or a refusal with its text in *why.  Every "not offered"
+// comes from here: the route's (kViewWords), two settings at once (kViewPairs), each setting's validator, what the projection
+// would need a second image for.  No device is touched.
+int resolve_view(const cuberille_ctx *c, const cuberille_image_desc *img, const Params &p, Route route, View *out, const char **why) {
+  static thread_local std::string text;
+  auto no = [&](const std::string &m) { text = m; *why = text.c_str(); return CUBERILLE_ERR_ARGUMENT; };
+  auto name = [](int k) { return std::string(kViewWords[k].noun) + " (" + kViewWords[k].fn + ")"; };
+  const bool on[4] = {false, c->padWidth != 0, c->regionOn, c->bandOn && route != ROUTE_WARM_UP};
+  View v{};
+  *why = "";
+  for (int k = VIEW_BORDER; k <= VIEW_BAND; k++) {
+    if (!on[k]) continue;
+    if (const char *r = kViewWords[k].route[route])
+      return route == ROUTE_GROUP ? no(std::string("has ") + kViewWords[k].noun + " set (" + kViewWords[k].fn + "): " + r) : no(name(k) + r);
+    for (int j = VIEW_BORDER; j < k; j++)
+      if (on[j]) return no(name(k) + " together with " + name(j) + " is not offered: " + kViewPairs[k][j]);
+    v.kind = k;
+  }
+  int rc = CUBERILLE_OK;
+  cuberille_image_desc framed = *img;
+  if (v.kind == VIEW_BORDER) {
+    v.padValue = c->padValue; v.padValueInt = c->padValueInt;
+    rc = border_check(img, c->padWidth, c->padValue, route != ROUTE_WARM_UP, why);
+  } else if (v.kind == VIEW_REGION) {
+    for (int i = 0; i < 3; i++) { v.start[i] = c->regionStart[i]; v.size[i] = c->regionSize[i]; }
+    rc = region_check(img, c->regionStart, c->regionSize, &framed, why);
+    v.pitched = framed.dims[0] != img->dims[0] || framed.dims[1] != img->dims[1];
+  } else if (v.kind == VIEW_BAND) {
+    for (int k = 0; k < 4; k++) { v.bandV[k] = c->bandV[k]; v.bandVi[k] = c->bandVi[k]; }
+    rc = band_check(img->pixel_type, c->bandV, (const int64_t *)c->bandVi, why);
+  }
+  if (rc) return rc;
+  // (the box's rows and slices lie the BUFFER's pitches apart; every other view's the frame's own)
+  if (v.kind == VIEW_BORDER) framed = framed_desc(v, img);
+  const cuberille_image_desc *mem = v.kind == VIEW_REGION ? img : &framed;
+  v.rowPitch = mem->dims[0]; v.slicePitch = mem->dims[0] * mem->dims[1];
+  if (v.kind != VIEW_WHOLE && p.project && route != ROUTE_WARM_UP) {
+    if (c->interp == CUBERILLE_INTERP_BSPLINE)
+      return no(name(v.kind) + " is not offered with the B-spline interpolator: its coefficient image would " + kViewWords[v.kind].second);
+    if (c->holdGradient) return no(name(v.kind) + " is not offered on a context holding a gradient image (cuberille_hold_gradient)");
+    if (p.gradVariant != CUBERILLE_GRADIENT_CENTRAL)
+      return no(name(v.kind) + " is offered with the central-difference gradient only: the recursive-Gaussian gradient image would " + kViewWords[v.kind].second);
+    if (p.variant != CUBERILLE_PROJECT_DEFAULT) return no(name(v.kind) + " is offered with the default projection branch only (txx:439-474)");
+  }
+  *out = v;
+  return CUBERILLE_OK;
+}
+
+// resolve_view for an entry point: the refusal becomes the context's error
+int view_of(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm, Route route, View *v) {
+  const char *why = "";
+  const int rc = resolve_view(c, img, projection_features(prm), route, v, &why);
+  return rc ? fail(c, rc, why) : CUBERILLE_OK;
+}
+
+// (an all-zero slab stands for the whole volume)
+bool whole_volume(const cuberille_slab *slab) {
+  return !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);
+}
+
 // RecursiveGaussianImageFilter::SetUp of ITK 3.x (Deriche's fourth-order recursive Gaussian): the 20 coefficients of one
 // separable pass -- order 0 smoothing, order 1 first derivative with NormalizeAcrossScale (txx:490) -- for `sigma` in
 // physical units on an axis of the given spacing.  Evaluated on the host in double, once per extraction; the kernels
@@ -689,8 +748,9 @@ struct CountSizes {
   size_t flatBits, vqueue;                                 // optional
 };
 
-// bordered (cuberille_set_border): neither padded sweep goes through the flat scratch stream
-CountSizes count_sizes(const Grid &g, const Tuning &t, bool bordered) {
+// (neither the padded nor the pitched sweep goes through the flat scratch stream)
+CountSizes count_sizes(const Grid &g, const Tuning &t, const View &v) {
+  const bool bordered = v.kind == VIEW_BORDER || (v.kind == VIEW_REGION && v.pitched);
   const size_t slice = (size_t)g.ny * g.W, nwords = (size_t)(g.oz1 - g.cz0) * slice, nblk = (nwords + COUNT_WB - 1) / COUNT_WB;
   CountSizes s;
   s.nwords = nwords; s.nseg = (nwords + 63) / 64;
@@ -747,8 +807,9 @@ void *optional(DevBuf &b, size_t bytes, size_t cover = 0) {
 
 // First half of a count: layout, parameters, workspace, zeroed state.  The caller then thresholds the slices
 // (all at once, or z-range by z-range as they arrive) and calls count_finish.
+// view: what resolve_view made of the context's settings for this image and route.
 int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
-                  const cuberille_slab *slab) {
+                  const cuberille_slab *slab, const View &view) {
   c->counted = false;
   c->pointsEmitted = false;
   c->haveMesh = false;
@@ -761,13 +822,11 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
-  const cuberille_image_desc framed = framed_desc(c, img);
+  const cuberille_image_desc framed = framed_desc(view, img);
   Grid g = whole_grid(&framed, c->tune);
   Geo geo{};
   Params p{};
   resolve(&framed, prm, geo, p);
-  // cuberille_set_region: are the box's rows apart in memory (else the box is a pointer offset into the buffer)?
-  const bool pitched = boxed(c) && (framed.dims[0] != img->dims[0] || framed.dims[1] != img->dims[1]);
   if (c->holdGradient && prm->step_length < 0.0) {
     // cuberille_hold_gradient stands for one filter OBJECT: m_ProjectVertexStepLength is replaced by its default once, at the
     // first Update(), from THAT input's spacing, and stays (txx:82-85) -- like the gradient image, the default step of every
@@ -775,13 +834,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     if (c->heldStep < 0.0) c->heldStep = p.step;
     p.step = c->heldStep;
   }
-  const bool whole = !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);   // (all-zero slab = whole volume)
-  if (!whole && c->padWidth)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
-  if (!whole && c->regionOn)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is a box of a whole volume: not offered on slabs");
-  if (!whole && c->bandOn)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) belongs to a whole volume: not offered on slabs");
+  const bool whole = whole_volume(slab);
   if (!whole) {
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
@@ -815,7 +868,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     g.oz1 = (int)(slab->own_z1 - slab->z_begin);
   }
   g.cz0 = g.oz0 > 0 ? g.oz0 - 1 : 0;
-  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0 || pitched);
+  const CountSizes sz = count_sizes(g, c->tune, view);
   if (sz.nseg > 0x7fffffffULL) return fail(c, CUBERILLE_ERR_LIMIT, "volume too large for one device scan");
 
   // ---- workspace ----------------------------------------------------------------------------------
@@ -836,20 +889,9 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   w.flatBits = (u64 *)optional(c->flatBits, sz.flatBits);
   w.vqueue = (u32 *)optional(c->vqueue, sz.vqueue);
   w.vox = dev_voxels;
-  w.pad = c->padWidth; w.padValue = c->padValue; w.padValueInt = c->padValueInt;
-  w.rowPitch = g.nx; w.slicePitch = (long long)g.nx * g.ny;
-  w.band = c->bandOn ? 1 : 0;
-  for (int k = 0; k < 4; k++) { w.bandV[k] = c->bandV[k]; w.bandVi[k] = c->bandVi[k]; }
-  if (boxed(c)) {
-    // the sweep and the walk start at the box's first voxel and step by the BUFFER's pitches; nothing else reads voxels
-    const long long Nx = (long long)img->dims[0], NxNy = Nx * (long long)img->dims[1];
-    w.vox = (const char *)dev_voxels + (size_t)(c->regionStart[0] + c->regionStart[1] * Nx + c->regionStart[2] * NxNy) * pixel_size(img->pixel_type);
-    w.rowPitch = Nx; w.slicePitch = NxNy;
-    w.regionSweep = pitched ? 1 : 0;
-  }
-  // (the walk with a runtime start index in its axis-aligned forms too: where the rows are pitched, and wherever a box left its
-  //  start index away from 0 -- the uploaded box of cuberille_extract_host included)
-  w.region = c->regionOn && whole && (pitched || geo.istart[0] != 0 || geo.istart[1] != 0 || geo.istart[2] != 0) ? 1 : 0;
+  w.view = view;
+  if (view.kind == VIEW_REGION)   // the sweep and the walk start at the box's first voxel and step by the view's pitches; nothing else reads voxels
+    w.vox = (const char *)dev_voxels + (size_t)(view.start[0] + view.start[1] * view.rowPitch + view.start[2] * view.slicePitch) * pixel_size(img->pixel_type);
   w.bits = (u64 *)c->bits.p; w.sliceOcc = (u32 *)((char *)c->occ.p + sizeof(Totals));
   w.prefix = (u32 *)c->prefix.p;
   w.segPre = (u64 *)c->segPre.p; w.blockTot = (u64 *)c->blockTot.p; w.blockBase = (u64 *)c->blockBase.p;
@@ -993,7 +1035,10 @@ int cuberille_count(cuberille_ctx *c, const cuberille_image_desc *img, const voi
                     const cuberille_params *prm, const cuberille_slab *slab, uint64_t *n_points, uint64_t *n_cells) {
   int rc = validate(c, img, dev_voxels, prm);
   if (rc) return rc;
-  rc = count_prepare(c, img, dev_voxels, prm, slab);
+  View view;
+  rc = view_of(c, img, prm, whole_volume(slab) ? ROUTE_DEVICE : ROUTE_SLAB, &view);
+  if (rc) return rc;
+  rc = count_prepare(c, img, dev_voxels, prm, slab, view);
   if (rc) return rc;
   rc = classify_slab(c, img, slab);
   if (rc) return rc;
@@ -1018,7 +1063,7 @@ int classify_slab(cuberille_ctx *c, const cuberille_image_desc *img, const cuber
     HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, g.oz1, g.nzb, c->tune, s));
   } else {
     // (with a border the grid is two slices taller than the buffer the sweep reads)
-    HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, 0, g.nzb - 2 * c->w.pad, c->tune, s));
+    HIP_TRY(c, launch_classify(img->pixel_type, c->w, g, c->prm, 0, g.nzb - (c->w.view.kind == VIEW_BORDER ? 2 : 0), c->tune, s));
   }
   return CUBERILLE_OK;
 }
@@ -1314,8 +1359,9 @@ int cuberille_reproject_escaped(cuberille_ctx *c, const void *dev_voxels, int64_
   if (!c || !dev_voxels) return CUBERILLE_ERR_ARGUMENT;
   if (!c->counted || !c->pointsEmitted || !c->thinHalo)
     return fail(c, CUBERILLE_ERR_STATE, "cuberille_reproject_escaped follows cuberille_emit_points on a THIN_HALO slab");
-  if (c->w.pad)   // (cannot happen: a slab count refuses the border -- said here so that it never becomes a bare launch error)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "an implied border (cuberille_set_border) belongs to a whole volume: not offered on slabs");
+  if (c->w.view.kind == VIEW_BORDER)   // (cannot happen: a slab count refuses the border -- said here so that it never becomes a bare launch error)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, std::string(kViewWords[VIEW_BORDER].noun) + " (" + kViewWords[VIEW_BORDER].fn + ")" +
+                                               kViewWords[VIEW_BORDER].route[ROUTE_SLAB]);
   if (c->tot.err & ERRF_ESCAPE_OVERFLOW)
     return fail(c, CUBERILLE_ERR_LIMIT, "more walks left the thin halo than the escape list holds: count the slab again with "
                                         "the full halo (cuberille_required_halo)");
@@ -1441,15 +1487,11 @@ int step_launch(cuberille_ctx *c, const void **dev_row, size_t *row_bytes) {
 
 // cuberille_step_begin, and the first half of cuberille_extract_device (the one-wait step with the context as its only rank:
 // a whole volume, so an implied border is at home there while the steps of a driver's ranks refuse it)
-const char *const kNoBorderInSteps = "an implied border (cuberille_set_border) would have to reach across ranks: not offered with the cuberille_step_* calls";
-const char *const kNoBandInSteps = "a band (cuberille_set_band) belongs to one context's whole volume: not offered with the cuberille_step_* calls";
-const char *const kNoRegionInSteps = "a region (cuberille_set_region) is a box of one context's whole volume: not offered with the cuberille_step_* calls";
 int step_begin_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
-                    const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
-  int rc = validate(c, img, dev_voxels, prm);
-  if (rc) return rc;
+                    const cuberille_slab *slab, const View &view, const void **dev_row, size_t *row_bytes) {
+  // (the caller has passed validate() and resolved the view)
   if (!dev_row || !row_bytes) return fail(c, CUBERILLE_ERR_ARGUMENT, "null row pointer");
-  rc = count_prepare(c, img, dev_voxels, prm, slab);
+  int rc = count_prepare(c, img, dev_voxels, prm, slab, view);
   if (rc) return rc;
   rc = classify_slab(c, img, slab);
   if (rc) return rc;
@@ -1463,21 +1505,20 @@ extern "C" {
 // ---- one step without a host round trip between count and emit (the multi-GPU steady state) -------------------------
 int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                          const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
-  if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
-  if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
-  if (c && c->bandOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBandInSteps);
-  return step_begin_impl(c, img, dev_voxels, prm, slab, dev_row, row_bytes);
+  View view;
+  int rc = validate(c, img, dev_voxels, prm);
+  if (!rc) rc = view_of(c, img, prm, ROUTE_STEP, &view);
+  return rc ? rc : step_begin_impl(c, img, dev_voxels, prm, slab, view, dev_row, row_bytes);
 }
 
 int cuberille_step_classify(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                             const cuberille_slab *slab, uint64_t **dev_bits, size_t *words_per_slice) {
-  if (c && c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBorderInSteps);
-  if (c && c->regionOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoRegionInSteps);
-  if (c && c->bandOn) return fail(c, CUBERILLE_ERR_ARGUMENT, kNoBandInSteps);
+  View view;
   int rc = validate(c, img, dev_voxels, prm);
+  if (!rc) rc = view_of(c, img, prm, ROUTE_STEP, &view);
   if (rc) return rc;
   if (!dev_bits || !words_per_slice) return fail(c, CUBERILLE_ERR_ARGUMENT, "null bit-plane pointer");
-  rc = count_prepare(c, img, dev_voxels, prm, slab);
+  rc = count_prepare(c, img, dev_voxels, prm, slab, view);
   if (rc) return rc;
   if (slab && slab->voxels_ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, (hipEvent_t)slab->voxels_ready_event, 0));
   HIP_TRY(c, launch_classify(img->pixel_type, c->w, c->g, c->prm, c->g.oz0, c->g.oz1, c->tune, c->stream));
@@ -1585,25 +1626,40 @@ int cuberille_failed_row(void *host_row, size_t capacity, size_t *row_bytes) {
   return CUBERILLE_OK;
 }
 
-int cuberille_extract_device(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels,
-                             const cuberille_params *prm, const cuberille_slab *slab, cuberille_result *res) {
+}  // extern "C"
+
+namespace {
+
+int extract_device_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
+                        const cuberille_slab *slab, const View &view, cuberille_result *res) {
   // the one-wait step with this context as the only rank: the first extraction on a context reads its counts back
   // before it sizes the emit, the following ones launch everything blindly from the sizes of the one before and wait
   // once (every volume the reference ships is in the regime where the waits ARE the extraction time)
   const void *row = nullptr;
   size_t rowBytes = 0;
-  if (!c) return CUBERILLE_ERR_ARGUMENT;
   struct OneCall {
     cuberille_ctx *c;
     explicit OneCall(cuberille_ctx *ctx) : c(ctx) { c->oneCall = true; }
     ~OneCall() { c->oneCall = false; }
   } guard(c);
-  int rc = step_begin_impl(c, img, dev_voxels, prm, slab, &row, &rowBytes);
+  int rc = step_begin_impl(c, img, dev_voxels, prm, slab, view, &row, &rowBytes);
   if (rc) return rc;
   rc = step_end_impl(c, row, 1, 0, slab ? slab->point_id_offset : 0, res);
   if (rc != CUBERILLE_RETRY) return rc;
   // counts beyond the guess, or a slab that needs its neighbours (quirk Q1, an escaped walk): the count stands
   return cuberille_emit(c, slab ? slab->point_id_offset : 0, res);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cuberille_extract_device(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels,
+                             const cuberille_params *prm, const cuberille_slab *slab, cuberille_result *res) {
+  View view;
+  int rc = validate(c, img, dev_voxels, prm);
+  if (!rc) rc = view_of(c, img, prm, whole_volume(slab) ? ROUTE_DEVICE : ROUTE_SLAB, &view);
+  return rc ? rc : extract_device_impl(c, img, dev_voxels, prm, slab, view, res);
 }
 
 }  // extern "C"
@@ -1686,10 +1742,10 @@ struct StagePool {
 // the buffer is thresholded, as classify_slab does.  The caller emits.
 template <class Fill>
 int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_params *prm, const cuberille_slab *slab,
-                    size_t stageBytes, size_t slicesPerChunk, const char *what, Fill fill) {
+                    const View &view, size_t stageBytes, size_t slicesPerChunk, const char *what, Fill fill) {
   int rc = ensure_staging(c, stageBytes);
   if (rc) return rc;
-  rc = count_prepare(c, img, c->voxOwn.p, prm, slab);
+  rc = count_prepare(c, img, c->voxOwn.p, prm, slab, view);
   if (rc) return rc;
   const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type), nz = (size_t)img->dims[2];
   hipError_t e = hipSuccess;
@@ -1722,8 +1778,8 @@ int extract_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const cub
 // chunkBytes: 0 = kUploadChunk (Tuning::upload_chunk_kib: smaller chunks, for tests of the pipeline on small volumes).
 constexpr size_t kUploadChunk = 32u << 20;
 int count_host_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels, size_t base,
-                       const cuberille_params *prm, const cuberille_slab *slab, size_t srcRowBytes = 0, size_t srcSliceBytes = 0,
-                       size_t chunkBytes = 0) {
+                       const cuberille_params *prm, const cuberille_slab *slab, const View &view, size_t srcRowBytes = 0,
+                       size_t srcSliceBytes = 0, size_t chunkBytes = 0) {
   const size_t rowBytes = (size_t)img->dims[0] * pixel_size(img->pixel_type), ny = (size_t)img->dims[1];
   const size_t sliceBytes = rowBytes * ny;
   const size_t bytes = sliceBytes * (size_t)img->dims[2];
@@ -1746,7 +1802,7 @@ int count_host_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const 
       off += n;
     }
   }, c->poolThreads);
-  return extract_chunked(c, img, prm, slab, kUploadChunk, slices, "overlapped upload: ",
+  return extract_chunked(c, img, prm, slab, view, kUploadChunk, slices, "overlapped upload: ",
                          [&](size_t i, void *, size_t, size_t) {
                            pool.release(i);
                            pool.wait(i);
@@ -1758,30 +1814,20 @@ int count_host_chunked(cuberille_ctx *c, const cuberille_image_desc *img, const 
 // that fit a chunk) or one plain copy.
 bool upload_in_chunks(size_t sliceBytes, size_t bytes) { return bytes >= (1ull << 30) && sliceBytes <= kUploadChunk; }
 
-}  // namespace
-
-extern "C" {
-
-int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels,
-                           const cuberille_params *prm, cuberille_result *res) {
-  int rc = validate(c, img, host_voxels, prm);
-  if (rc) return rc;
+int extract_host_impl(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels, const cuberille_params *prm,
+                      View view, cuberille_result *res) {
   HIP_TRY(c, hipSetDevice(c->device));
-  // cuberille_set_region: only the box crosses the link, straight from the caller's image -- the device copy is the box,
-  // contiguous, and from here on the image IS the box (its description cuberille_region_desc's; validate() has passed it)
-  const bool box = boxed(c);
-  const cuberille_image_desc whole = *img, cut = framed_desc(c, img);
-  if (box) img = &cut;
-  struct Applied {
-    cuberille_ctx *c; bool on;
-    Applied(cuberille_ctx *ctx, bool b) : c(ctx), on(b) { if (on) c->regionApplied = true; }
-    ~Applied() { if (on) c->regionApplied = false; }
-  } applied(c, box);
+  // VIEW_REGION: only the box crosses the link, straight from the caller's image -- the device copy is the box, contiguous,
+  // and from here on the image IS the box (its description cuberille_region_desc's) under the view that says so
+  const bool box = view.kind == VIEW_REGION;
+  const cuberille_image_desc whole = *img, cut = framed_desc(view, img);
+  const size_t at[3] = {(size_t)view.start[0], (size_t)view.start[1], (size_t)view.start[2]};
+  if (box) { img = &cut; view = applied_region(cut); }
   const size_t pix = pixel_size(img->pixel_type);
   const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pix;
   const size_t bytes = sliceBytes * (size_t)img->dims[2];
   const size_t srcRow = (size_t)whole.dims[0] * pix, srcSlice = srcRow * (size_t)whole.dims[1];
-  const size_t base = box ? (size_t)c->regionStart[0] * pix + (size_t)c->regionStart[1] * srcRow + (size_t)c->regionStart[2] * srcSlice : 0;
+  const size_t base = box ? at[0] * pix + at[1] * srcRow + at[2] * srcSlice : 0;
   const bool rowsApart = box && (img->dims[0] != whole.dims[0] || img->dims[1] != whole.dims[1]);
   HIP_TRY(c, c->voxOwn.reserve(bytes));
   // below a GiB: one plain copy (the runtime stages pageable memory itself, at link rate once the copy is large; the
@@ -1800,28 +1846,38 @@ int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, co
     } else {
       HIP_TRY(c, hipMemcpyAsync(c->voxOwn.p, (const char *)host_voxels + base, bytes, hipMemcpyHostToDevice, c->stream));
     }
-    return cuberille_extract_device(c, img, c->voxOwn.p, prm, nullptr, res);
+    return extract_device_impl(c, img, c->voxOwn.p, prm, nullptr, view, res);
   }
-  rc = count_host_chunked(c, img, host_voxels, base, prm, nullptr, rowsApart ? srcRow : 0, rowsApart ? srcSlice : 0,
+  const int rc = count_host_chunked(c, img, host_voxels, base, prm, nullptr, view, rowsApart ? srcRow : 0, rowsApart ? srcSlice : 0,
                           (size_t)(c->tune.upload_chunk_kib > 0 ? c->tune.upload_chunk_kib : 0) << 10);
   return rc ? rc : cuberille_emit(c, 0, res);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cuberille_extract_host(cuberille_ctx *c, const cuberille_image_desc *img, const void *host_voxels,
+                           const cuberille_params *prm, cuberille_result *res) {
+  View view;
+  int rc = validate(c, img, host_voxels, prm);
+  if (!rc) rc = view_of(c, img, prm, ROUTE_HOST, &view);
+  return rc ? rc : extract_host_impl(c, img, host_voxels, prm, view, res);
 }
 
 int cuberille_extract_stream(cuberille_ctx *c, const cuberille_image_desc *img, cuberille_chunk_source source, void *user,
                              const cuberille_params *prm, cuberille_result *res) {
   if (c && !source) return fail(c, CUBERILLE_ERR_ARGUMENT, "null chunk source");
-  if (c && c->regionOn)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) is not offered with cuberille_extract_stream: the source produces whole slices");
-  if (c && c->bandOn)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "a band (cuberille_set_band) is not offered with cuberille_extract_stream");
+  View view;
   int rc = validate(c, img, (const void *)source, prm);
+  if (!rc) rc = view_of(c, img, prm, ROUTE_STREAM, &view);
   if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t sliceBytes = (size_t)img->dims[0] * img->dims[1] * pixel_size(img->pixel_type);
   HIP_TRY(c, c->voxOwn.reserve(sliceBytes * (size_t)img->dims[2]));
   // chunks of about 32 MiB, whole slices, at least one; the caller's source fills each slot on this thread, in order
   const size_t slicesPerChunk = sliceBytes >= (32u << 20) ? 1 : (32u << 20) / sliceBytes;
-  rc = extract_chunked(c, img, prm, nullptr, slicesPerChunk * sliceBytes, slicesPerChunk, "streamed upload: ",
+  rc = extract_chunked(c, img, prm, nullptr, view, slicesPerChunk * sliceBytes, slicesPerChunk, "streamed upload: ",
                        [&](size_t, void *slot, size_t z0, size_t z1) { return source(user, slot, (int64_t)z0, (int64_t)z1); });
   return rc ? rc : cuberille_emit(c, 0, res);
 }
@@ -1852,15 +1908,11 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     cuberille_params p = dflt;
     p.iso_value = 100.0;
     cuberille_result r{};
-    const bool applied = c->regionApplied, banded = c->bandOn;
-    c->regionApplied = true;                 // (cuberille_set_region speaks of the caller's volumes, not of this one)
-    c->bandOn = false;                       // (... and so does cuberille_set_band, whose values are those of the caller's pixel type)
     for (int i = 0; i < 2; i++) {            // twice: the second one takes the blind launches of the one-wait step
-      const int rc = cuberille_extract_host(c, &d, tiny, &p, &r);
-      if (rc) { c->regionApplied = applied; c->bandOn = banded; return rc; }
+      // (the whole toy volume: the context's view settings speak of the caller's volumes, not of this one)
+      const int rc = extract_host_impl(c, &d, tiny, &p, View{}, &r);
+      if (rc) return rc;
     }
-    c->regionApplied = applied;
-    c->bandOn = banded;
     // the runtime sets up its staging for copies from and to PAGEABLE memory at the first copy that needs it (measured
     // through the reference's driver: 7.2 ms inside the first hipMemcpyAsync of nucleon.mha's 69 KB, profiles/
     // r4_cold_update.log): one round trip of a size that takes its staging buffers, one of a size it pins in place
@@ -1887,25 +1939,15 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
   if (live) return CUBERILLE_OK;
   // the buffers whose size follows from the description (count_prepare, emit_points_phase, cuberille_extract_host); a
   // reservation that fails here is asked for again, and reported, by the extraction
-  // (cuberille_set_border: the workspace of the image with its ring, the voxel buffer of the image as it is)
-  // (cuberille_set_region: the workspace AND the voxel buffer of the box -- cuberille_extract_host uploads nothing else)
-  if (boxed(c)) {
-    if (c->padWidth) return fail(c, CUBERILLE_ERR_ARGUMENT, "a region (cuberille_set_region) together with an implied border (cuberille_set_border) is not offered");
-    cuberille_image_desc box;
-    const char *why = "";
-    const int rrc = region_check(img, c->regionStart, c->regionSize, &box, &why);
-    if (rrc) return fail(c, rrc, why);
-  }
-  const cuberille_image_desc framed = framed_desc(c, img);
-  for (int i = 0; i < 3; i++) {     // (the limits of validate() for the image with its ring)
-    if (framed.dims[i] > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_LIMIT, "image dimension with its border exceeds 2^31-1");
-    if (c->padWidth && framed.index_start[i] < -(1LL << 30))
-      return fail(c, CUBERILLE_ERR_LIMIT, "the bordered region's start index must lie within +-2^30");
-  }
+  // (VIEW_BORDER: the workspace of the image with its ring, the voxel buffer of the image as it is)
+  // (VIEW_REGION: the workspace AND the voxel buffer of the box -- cuberille_extract_host uploads nothing else)
+  View view;
+  const int vrc = view_of(c, img, &dflt, ROUTE_WARM_UP, &view);
+  if (vrc) return vrc;
+  const cuberille_image_desc framed = framed_desc(view, img);
   const Grid g = whole_grid(&framed, c->tune);
-  const bool pitched = boxed(c) && (framed.dims[0] != img->dims[0] || framed.dims[1] != img->dims[1]);
-  const CountSizes sz = count_sizes(g, c->tune, c->padWidth != 0 || pitched);
-  const cuberille_image_desc *held = boxed(c) ? &framed : img;     // the image a host-resident extraction keeps on the device
+  const CountSizes sz = count_sizes(g, c->tune, view);
+  const cuberille_image_desc *held = view.kind == VIEW_REGION ? &framed : img;     // the image a host-resident extraction keeps on the device
   const size_t bytes = (size_t)held->dims[0] * (size_t)held->dims[1] * (size_t)held->dims[2] * pixel_size(img->pixel_type);
   const std::pair<DevBuf *, size_t> want[] = {{&c->voxOwn, bytes}, {&c->bits, sz.bits}, {&c->occ, sz.occ}, {&c->prefix, sz.prefix},
                                               {&c->segPre, sz.segPre}, {&c->blockTot, sz.blockTot}, {&c->blockBase, sz.blockBase},
@@ -2446,15 +2488,10 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
   if (group_plan_impl(img, prm, n, b.data(), &used, &why) != CUBERILLE_OK) return gfail(g, CUBERILLE_ERR_ARGUMENT, why);
   for (int i = 0; i < n; i++) {
     const cuberille_ctx *c = g->ctx[(size_t)i];
-    if (c->regionOn)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has a region set (cuberille_set_region): "
-                                              "a box of one context's whole volume, not offered in a group");
-    if (c->bandOn)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has a band set (cuberille_set_band): "
-                                              "it belongs to one context's whole volume, not offered in a group");
-    if (c->padWidth)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has an implied border set (cuberille_set_border): "
-                                              "the ring would have to reach across slabs, not offered in a group");
+    View view;
+    const char *why = "";
+    const int vrc = resolve_view(c, img, projection_features(prm), ROUTE_GROUP, &view, &why);
+    if (vrc) return gfail(g, vrc, "member " + std::to_string(i) + " " + why);
     if (c->interp == CUBERILLE_INTERP_BSPLINE)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has the B-spline interpolator set: its "
                                               "prefilter needs whole lines of the volume, not offered in a group");
@@ -2492,7 +2529,7 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
       s.set(rc, "upload", c);
     } else if (upload_in_chunks(sliceBytes, bytes)) {
       rc = validate(c, &d, host_voxels, prm);
-      if (!rc) rc = count_host_chunked(c, &d, host_voxels, base, prm, &slab);
+      if (!rc) rc = count_host_chunked(c, &d, host_voxels, base, prm, &slab, View{});
       if (!rc) { np[(size_t)i] = c->res.n_points; nc[(size_t)i] = c->res.n_cells; }
       if (rc) s.set(rc, "chunked upload and count", c);
     } else {

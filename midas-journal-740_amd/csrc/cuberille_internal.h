@@ -116,6 +116,30 @@ struct HeldGradient {
   int n[3];
 };
 
+// What an extraction meshes of the caller's buffer without a copy of it: one kind per extraction, read by the sweep and the
+// walk only.  The Grid and the Geo always describe the FRAME (framed_desc: the image the reference would be handed), `vox` what
+// is in memory.
+//   VIEW_BORDER (cuberille_set_border): the frame is the image with a ring of one constant voxel around it, `vox` the caller's
+//     buffer, two voxels smaller along every axis; the ring's value travels like the iso value (a double, and an integer for
+//     the 64-bit integer types).
+//   VIEW_REGION (cuberille_set_region): the frame is a BOX of the caller's buffer and `vox` points at the box's first voxel;
+//     its rows and slices lie rowPitch / slicePitch voxels apart (the buffer's Nx and Nx * Ny; the box's own where the box is
+//     contiguous in memory or was uploaded on its own).  pitched: the rows are not contiguous, the pitched sweep reads them.
+//   VIEW_BAND (cuberille_set_band): the sweep and the walk see B = (lower <= pixel && pixel <= upper) ? inside : outside in
+//     place of the pixel -- itk::BinaryThresholdImageFilter's output, never stored.  bandV / bandVi: lower, upper, inside,
+//     outside, each the pair the iso value travels as.
+enum ViewKind { VIEW_WHOLE, VIEW_BORDER, VIEW_REGION, VIEW_BAND };
+struct View {
+  int kind;
+  double padValue;
+  long long padValueInt;
+  long long start[3], size[3];     // the box in the caller's buffer (positions x, y, z)
+  long long rowPitch, slicePitch;
+  int pitched;
+  double bandV[4];
+  long long bandVi[4];
+};
+
 struct Workspace {     // device pointers valid for one count/emit pair
   const void *vox;
   u64 *bits;
@@ -137,25 +161,7 @@ struct Workspace {     // device pointers valid for one count/emit pair
   u32 *escList;        // THIN_HALO: indices (in this rank's point buffer) of the vertices whose walk left the buffer
   u32 escCap;
   const HeldGradient *held;   // (host pointer) the held gradient image the walk follows instead of the volume's own, or null
-  // cuberille_set_border: 1 = the Grid (and the Geo) describe the image with a ring of one constant voxel around it while `vox`
-  // is the caller's buffer, two voxels smaller along every axis -- read by the sweep and the walk only, every other kernel works
-  // on the bit volume; the ring's value travels like the iso value (a double, and an integer for the 64-bit integer types)
-  int pad;
-  double padValue;
-  long long padValueInt;
-  // cuberille_set_region: the Grid (and the Geo) describe a BOX of the caller's buffer and `vox` points at the box's first
-  // voxel; its rows and slices lie rowPitch / slicePitch voxels apart (the buffer's Nx and Nx * Ny; the box's own nx and
-  // nx * ny where the box is contiguous in memory or was uploaded on its own).  region: the walk takes the pitches and a
-  // runtime start index in all three geometry forms; regionSweep: the rows are not contiguous, the pitched sweep reads
-  // them.  Read by the sweep and the walk only, every other kernel works on the bit volume.
-  int region, regionSweep;
-  long long rowPitch, slicePitch;
-  // cuberille_set_band: the sweep and the walk see B = (lower <= pixel && pixel <= upper) ? inside : outside in place of the
-  // pixel -- itk::BinaryThresholdImageFilter's output, never stored.  bandV / bandVi: lower, upper, inside, outside, each the
-  // pair the iso value travels as.  Read by the unpadded, unpitched sweep and the default walk only.
-  int band;
-  double bandV[4];
-  long long bandVi[4];
+  View view;           // what of `vox` the sweep and the walk read; every other kernel works on the bit volume
 };
 
 // Development switches, set per context through cuberille_debug_set_option (never read from the environment).
@@ -221,7 +227,7 @@ struct Gate {
 
 // launchers (cuberille_kernels.hip); all asynchronous on `s`.  dyn: the launch is sized for an estimate, the kernel
 // reads the real sizes from the device totals and runs only when Totals::go says so.
-// (z0, z1: slices of `vox` -- with Workspace::pad the caller's, the range that holds its first / last slice writes the ring's too)
+// (z0, z1: slices of `vox` -- with VIEW_BORDER the caller's, the range that holds its first / last slice writes the ring's too)
 hipError_t launch_classify(int pixel_type, const Workspace &w, const Grid &g, const Params &p, int z0, int z1, const Tuning &t,
                            hipStream_t s);
 hipError_t launch_occupancy(int pixel_type, const Workspace &w, const Grid &g, const Tuning &t, hipStream_t s);

@@ -2701,12 +2701,12 @@ __global__ __launch_bounds__(256) void k_emit_cells(EmitArgs a, Grid g, size_t n
 // Every arithmetic step mirrors the ITK 3.x contract I3..I9 in the same
 // operation order as the oracle, so the float coordinates come out bit-identical.
 // ---------------------------------------------------------------------------------------------
-template <class T, bool PAD = false, bool REGION = false, bool BAND = false>
+template <class T, int VIEW = VIEW_WHOLE>
 struct Sampler {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
-  __device__ __forceinline__ T map(T v) const { return v; }       // (what a loaded pixel stands for: itself; see the BAND form)
+  __device__ __forceinline__ T map(T v) const { return v; }       // (what a loaded pixel stands for: itself; see the VIEW_BAND form)
   __device__ __forceinline__ int zlocal(int zg) const {          // global z -> buffer slice
     const int z = zg - zglob0;
     return z < 0 ? 0 : (z > nzb - 1 ? nzb - 1 : z);
@@ -2727,7 +2727,7 @@ struct Sampler {
 // the padded frame; vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels.  Voxel p is vox[p - 1] where
 // 1 <= p <= n - 2 on every axis and `ring` elsewhere.
 template <class T>
-struct Sampler<T, true, false, false> {
+struct Sampler<T, VIEW_BORDER> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
@@ -2759,7 +2759,7 @@ struct Sampler<T, true, false, false> {
 // cropped copy; vox points at the box's first voxel and rows / slices lie rowS / sliceS voxels apart -- the buffer's Nx and
 // Nx * Ny.  Nothing outside the box is ever addressed.
 template <class T>
-struct Sampler<T, false, true, false> {
+struct Sampler<T, VIEW_REGION> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
@@ -2780,7 +2780,7 @@ struct Sampler<T, false, true, false> {
 // of an interior cell like the clamped taps -- becomes one of the two values, in T, before any conversion or arithmetic.  A NaN
 // pixel fails both comparisons and is `outside`.  A whole volume (zglob0 = 0, gnz = nzb), no ring, no pitches.
 template <class T>
-struct Sampler<T, false, false, true> {
+struct Sampler<T, VIEW_BAND> {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
@@ -2887,8 +2887,8 @@ __device__ __forceinline__ void gradient_from_taps(const Geo &geo, bool dirIdent
   }
 }
 
-template <class T, bool PAD = false, bool REGION = false, bool BAND = false>
-__device__ __forceinline__ void gradient_at(const Sampler<T, PAD, REGION, BAND> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
+template <class T, int VIEW = VIEW_WHOLE>
+__device__ __forceinline__ void gradient_at(const Sampler<T, VIEW> &s, const Geo &geo, bool dirIdentity, int x, int y, int z,
                                             float f0, float out[3]) {
   float fm[3], fp[3];
 #pragma unroll
@@ -2949,17 +2949,17 @@ __device__ __forceinline__ void cell_gradients(const Geo &geo, bool dirIdentity,
 // up to the SIGN OF A ZERO result, and a zero gradient component only ever enters the walk as a term added to a
 // sum that starts at +0 -- so the walk cannot tell.  Non-finite taps always give a non-finite component here too;
 // the caller tests for that and gathers again with LITERAL = true.
-// PAD (cuberille_set_border): positions are those of the padded frame; "interior" then means that the cell and its ring lie
+// VIEW_BORDER: positions are those of the padded frame; "interior" then means that the cell and its ring lie
 // inside the caller's buffer -- one voxel further in on every side -- and the 12 row segments are read through a base pointer
 // moved back by one voxel per axis, with the buffer's own row and slice pitch.  Only cells that touch the implied ring
 // take the clamped forms, whose taps go through Sampler::at_buffer.
-// REGION (cuberille_set_region): positions are those of the box, whose rows and slices lie the BUFFER's pitch apart in memory.
-template <class T, bool LITERAL, bool PAD = false, bool REGION = false, bool BAND = false>
-__device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
+// VIEW_REGION: positions are those of the box, whose rows and slices lie the BUFFER's pitch apart in memory.
+template <class T, bool LITERAL, int VIEW = VIEW_WHOLE>
+__device__ __forceinline__ void gather_cell(const Sampler<T, VIEW> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
                                             float G[8][3], typename SiteValue<T>::type Vd[8]) {
   const bool unit = c.lo[0] + 1 == c.hi[0] && c.lo[1] + 1 == c.hi[1] && c.lo[2] + 1 == c.hi[2];
   const int zl = c.lo[2] - s.zglob0;              // buffer slice of the cell's lower z
-  constexpr int IN = PAD ? 1 : 0;                 // voxels of the frame's rim that are not in memory
+  constexpr int IN = VIEW == VIEW_BORDER ? 1 : 0;                 // voxels of the frame's rim that are not in memory
   const bool interior = unit && c.lo[0] >= 1 + IN && c.lo[0] + 2 + IN < s.nx && c.lo[1] >= 1 + IN && c.lo[1] + 2 + IN < s.ny &&
                         zl >= 1 + IN && zl + 2 + IN < s.nzb;
   // one address form per gather pass: the immediate-offset form only when EVERY lane gathering now sits in the
@@ -2972,7 +2972,7 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> 
     const int pnx = s.nx - 2 * IN, pny = s.ny - 2 * IN;      // row and slice pitch of the buffer in memory
     const T *base;
     ptrdiff_t rowS, sliceS;
-    if constexpr (REGION) {
+    if constexpr (VIEW == VIEW_REGION) {
       rowS = (ptrdiff_t)s.rowS; sliceS = (ptrdiff_t)s.sliceS;
       base = s.vox + zl * sliceS + c.lo[1] * rowS + c.lo[0];
     } else {
@@ -3009,7 +3009,7 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> 
       for (int yi = 0; yi < 4; yi++) {
         const bool zin = (zi == 1 || zi == 2), yin = (yi == 1 || yi == 2);
         if (!zin && !yin) continue;
-        if constexpr (PAD) {
+        if constexpr (VIEW == VIEW_BORDER) {
           // every tap is loaded from the buffer at its position clamped into it -- the same unconditional loads as the
           // unpadded form -- and replaced by the ring's value where an axis says "ring": per axis four flags, per tap a select
           const bool oyz = s.on_ring(ys[yi], s.ny) || s.on_ring(zs[zi], s.nzb);
@@ -3029,7 +3029,7 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> 
           }
         } else {
         const T *row;
-        if constexpr (REGION) row = s.vox + zs[zi] * s.sliceS + ys[yi] * s.rowS;
+        if constexpr (VIEW == VIEW_REGION) row = s.vox + zs[zi] * s.sliceS + ys[yi] * s.rowS;
         else row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
         if (zin && yin) {
 #pragma unroll
@@ -3074,29 +3074,29 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, PAD, REGION, BAND> 
 // block in SGPRs and spills what does not fit (62 of them before) into the lanes of a vector register its loop reads back.
 // GEOM 2 = that; 1: identity direction, region at 0, ANY spacing (a diagonal matrix: three scalars instead of eighteen -- the
 // anisotropic volumes of CT and MR); 0: anything (a rotation, a region that starts elsewhere).
-// PAD (cuberille_set_border, MODE 0, a whole volume): `g` and `geo` describe the padded image, `vox` is the caller's buffer and
+// VIEW (one ViewKind; all but VIEW_WHOLE: MODE 0, a whole volume).  VIEW_BORDER: `g` and `geo` describe the padded image, `vox` is the caller's buffer and
 // the ring's value arrives as padD / padI (the pair the iso value travels as); GEOM 1 and 2 then stand for a caller's image
 // whose region starts at index 0, i.e. a padded one that starts at -1.  The other instantiations never read the two arguments.
-// REGION (cuberille_set_region, MODE 0, a whole volume): `g` and `geo` describe the box, `vox` points at the box's first voxel
+// VIEW_REGION: `g` and `geo` describe the box, `vox` points at the box's first voxel
 // and its rows and slices lie rowPitch / slicePitch voxels apart (the buffer's Nx and Nx * Ny).  GEOM 1 and 2 then speak of the
 // MATRICES alone: the start index of the box -- the input's plus the box's place in the buffer, rarely 0 -- stays the three runtime
 // scalars geo.istart in every form (it enters only through integer clamps in make_cell), so that a box of an axis-aligned image keeps
 // the axis-aligned walk.  The other instantiations never read the two pitches.
-// BAND (cuberille_set_band, MODE 0, a whole volume, PAD and REGION off): every pixel the walk loads is mapped to the band's
-// `inside` or `outside` first (Sampler's BAND form); the two bounds and the two values arrive as four scalars of T in the place
+// VIEW_BAND: every pixel the walk loads is mapped to the band's
+// `inside` or `outside` first (Sampler's VIEW_BAND form); the two bounds and the two values arrive as four scalars of T in the place
 // of the four arguments above, which that form has no use for -- the other instantiations keep their argument block to the letter.
-template <class T, bool BAND, class A> struct WalkArg { typedef A type; };
-template <class T, class A> struct WalkArg<T, true, A> { typedef T type; };
+template <class T, int VIEW, class A> struct WalkArg { typedef A type; };
+template <class T, class A> struct WalkArg<T, VIEW_BAND, A> { typedef T type; };
 
-template <class T, int MODE, int GEOM, bool PAD = false, bool REGION = false, bool BAND = false>
+template <class T, int MODE, int GEOM, int VIEW = VIEW_WHOLE>
 __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentityArg,
                                                  float *__restrict__ points, u64 nPoints, u64 nGhost, u64 chunk,
                                                  int REFILL, int xcdRemap, int forceLiteral, Totals *__restrict__ tot,
                                                  u32 *__restrict__ escList, u32 escCap, int dyn,
-                                                 typename WalkArg<T, BAND, double>::type padD, typename WalkArg<T, BAND, long long>::type padI,
-                                                 typename WalkArg<T, BAND, long long>::type rowPitch,
-                                                 typename WalkArg<T, BAND, long long>::type slicePitch) {
-  // (BAND: the four are lower, upper, inside, outside)
+                                                 typename WalkArg<T, VIEW, double>::type padD, typename WalkArg<T, VIEW, long long>::type padI,
+                                                 typename WalkArg<T, VIEW, long long>::type rowPitch,
+                                                 typename WalkArg<T, VIEW, long long>::type slicePitch) {
+  // (VIEW_BAND: the four are lower, upper, inside, outside)
   const int lane = threadIdx.x & 63;
   if (dyn) {
     if (!tot->go) return;
@@ -3131,10 +3131,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   if (wave >= nBatches) return;
   u64 next = 0;                                   // wave-uniform cursor
   const u64 end = ((nBatches - wave + NW - 1) / NW) << lgChunk;
-  Sampler<T, PAD, REGION, BAND> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-  if constexpr (PAD) s.ring = iso_as<T>(padD, padI);
-  if constexpr (REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
-  if constexpr (BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
+  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
+  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
+  if constexpr (VIEW == VIEW_BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
   const double iso = (double)iso_as<T>(prm.iso, prm.isoInt);
   unsigned myIters = 0;
@@ -3164,7 +3164,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       geo.dir[i] = (i % 4 == 0) ? 1.0 : 0.0;
       if (IDENT || i % 4 != 0) geo.p2i[i] = (i % 4 == 0) ? 1.0 : 0.0;
     }
-    if constexpr (!REGION) geo.istart[0] = geo.istart[1] = geo.istart[2] = PAD ? -1 : 0;
+    if constexpr (VIEW != VIEW_REGION) geo.istart[0] = geo.istart[1] = geo.istart[2] = VIEW == VIEW_BORDER ? -1 : 0;
     unitP2I = IDENT;
   }
   const int dirIdentity = GEOM ? 1 : dirIdentityArg;
@@ -3210,7 +3210,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
       }
       if (!escaped) {
       if (c.bc[0] != kc[0] || c.bc[1] != kc[1] || c.bc[2] != kc[2]) {
-        gather_cell<T, false, PAD, REGION, BAND>(s, geo, dirIdentity != 0, c, G, Vd);
+        gather_cell<T, false, VIEW>(s, geo, dirIdentity != 0, c, G, Vd);
 #pragma unroll
         for (int k = 0; k < 3; k++) kc[k] = c.bc[k];
         // all 32 cached numbers finite?  x*0 accumulates to 0 for finite x, to NaN for an infinity or a NaN
@@ -3223,7 +3223,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
           for (int k = 0; k < 3; k++) tf = __builtin_fmaf(G[counter][k], 0.0f, tf);
         }
         cellFinite = (tf == 0.0f) && (td == 0.0);
-        if (!cellFinite) gather_cell<T, true, PAD, REGION, BAND>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
+        if (!cellFinite) gather_cell<T, true, VIEW>(s, geo, dirIdentity != 0, c, G, Vd);   // rare: the reference's formula to the letter
 #pragma unroll
         for (int counter = 0; counter < 8; counter++)
 #pragma unroll
@@ -3957,13 +3957,33 @@ static bool ragged_stream_path(const Workspace &w, const Grid &g, size_t elem, c
   return g.nx % 64 != 0 && w.flatBits && ((uintptr_t)w.vox % elem) == 0 && !tn.no_stream_classify && !small_volume(g);
 }
 
-// ... or, for buffers of 256 MiB and more, through the span sweep for rows that are not whole words (k_classify_span_rows:
-// occupancy on the fly, no scratch stream)?  Also taken by whole-word rows behind a pointer that is not 16-byte aligned.
-// A property of the BUFFER, so that every z-range of it takes the same route and launch_occupancy knows which.
+// The staged span sweeps (k_classify_*span_rows: occupancy on the fly, no scratch stream) are for buffers of `bytes` = 256 MiB
+// and more whose pointer holds whole elements, with fewer than 2^32 words in the bit volume.  What differs between the callers
+// stays an argument: classify_variant 1 (always the plain sweep) keeps every caller off them; anyVariant: every other value
+// of it may take them, forceSmall: and classify_variant 2 takes them below 256 MiB too (tests) -- else only the default, 0.
+static bool staged_spans(const void *vox, size_t elem, u64 bytes, const Grid &g, const Tuning &tn, bool anyVariant, bool forceSmall) {
+  const bool variant = anyVariant ? tn.classify_variant != 1 : tn.classify_variant == 0;
+  return variant && !tn.no_stream_classify && ((uintptr_t)vox % elem) == 0 &&
+         (bytes >= (256ull << 20) || (forceSmall && tn.classify_variant == 2)) && (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
+}
+
+// Workgroups for nspans spans taken in rounds by `want` of them (two per CU, or Tuning::classify_grid): as many as fill every
+// round -- 3907 spans of a 1000^3 volume are 8 rounds of 489 rather than 7 of 512 and one of 323, whose time is a whole round's
+static unsigned whole_rounds(u64 nspans, const Tuning &tn) {
+  const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;
+  const u64 rounds = (nspans + want - 1) / want;
+  return (unsigned)((nspans + rounds - 1) / rounds);
+}
+
+// the grid of the one-wave-per-word sweeps (k_classify_rows, _pad_words, _region_words) over `words` words
+static unsigned word_sweep_grid(u64 words) { return grid_for(words * 64, 256, 8192); }
+
+// Ragged rows of a plain buffer through the span sweep (k_classify_span_rows); also taken by whole-word rows behind a pointer
+// that is not 16-byte aligned.  A property of the BUFFER, so that every z-range of it takes the same route and
+// launch_occupancy knows which.
 static bool ragged_span_path(const Workspace &w, const Grid &g, size_t elem, const Tuning &tn) {
   const bool wholeAligned = g.nx % 64 == 0 && ((uintptr_t)w.vox % 16) == 0;
-  return !wholeAligned && tn.classify_variant == 0 && !tn.no_stream_classify && ((uintptr_t)w.vox % elem) == 0 &&
-         (u64)g.nx * (u64)g.ny * (u64)g.nzb * (u64)elem >= (256ull << 20) && (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
+  return !wholeAligned && staged_spans(w.vox, elem, (u64)g.nx * (u64)g.ny * (u64)g.nzb * (u64)elem, g, tn, false, false);
 }
 
 // a (double, integer) pair in the pixel type, as iso_as does on the device
@@ -3979,8 +3999,9 @@ static T value_as(double d, long long i) {
 template <class T>
 static void band_sweep_args(const Workspace &w, const Params &prm, BandBoundsD &d, BandBoundsI &i) {
   const T iso = value_as<T>(prm.iso, prm.isoInt);
-  const bool bin = !(value_as<T>(w.bandV[2], w.bandVi[2]) < iso), bout = !(value_as<T>(w.bandV[3], w.bandVi[3]) < iso);
-  if (bin != bout) { d.lower = w.bandV[0]; d.upper = w.bandV[1]; i.lower = w.bandVi[0]; i.upper = w.bandVi[1]; }
+  const View &v = w.view;
+  const bool bin = !(value_as<T>(v.bandV[2], v.bandVi[2]) < iso), bout = !(value_as<T>(v.bandV[3], v.bandVi[3]) < iso);
+  if (bin != bout) { d.lower = v.bandV[0]; d.upper = v.bandV[1]; i.lower = v.bandVi[0]; i.upper = v.bandVi[1]; }
   else { d.lower = 1.0; d.upper = 0.0; i.lower = 1; i.upper = 0; }
   i.invert = bout ? 1 : 0;
 }
@@ -3991,7 +4012,7 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
   if (z1 <= z0) return hipSuccess;
   const double iso = prm.iso;
   const long long isoI = prm.isoInt;
-  if (wAll.pad)
+  if (wAll.view.kind == VIEW_BORDER)
     return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
       typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
       // cuberille_set_border: `g` is the padded layout, z0 / z1 are slices of the caller's buffer; the range that holds its
@@ -4000,47 +4021,31 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       const u64 pz0 = z0 == 0 ? 0 : (u64)z0 + 1, pz1 = z1 == nz ? (u64)nz + 2 : (u64)z1 + 1;
       const u64 wps = (u64)g.ny * g.W, t0 = pz0 * wps, t1 = pz1 * wps;
       const T *vox = (const T *)wAll.vox;
-      // the staged spans under the rule of the unpadded sweep: a buffer of 256 MiB and more, fewer than 2^32 words
-      const bool spans = tn.classify_variant != 1 && !tn.no_stream_classify && ((uintptr_t)vox % sizeof(T)) == 0 &&
-                         ((u64)nx * (u64)ny * (u64)nz * sizeof(T) >= (256ull << 20) || tn.classify_variant == 2) &&
-                         (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
-      if (spans) {
+      if (staged_spans(vox, sizeof(T), (u64)nx * (u64)ny * (u64)nz * sizeof(T), g, tn, true, true)) {
         const u64 nwordsAll = t1 - t0;
         const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-        const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;     // two workgroups per CU, whole rounds
-        const u64 rounds = (nspans + want - 1) / want;
-        const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
-        hipLaunchKernelGGL((k_classify_pad_span_rows<T>), dim3(blocks), dim3(256), 0, s, vox, wAll.bits + t0, nspans, nwordsAll,
-                           (u32)(pz0 * (u64)g.ny), nx, (u32)ny, (u32)nz, g.W, iso, isoI, wAll.padValue, wAll.padValueInt, wAll.sliceOcc);
+        hipLaunchKernelGGL((k_classify_pad_span_rows<T>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, vox, wAll.bits + t0, nspans, nwordsAll,
+                           (u32)(pz0 * (u64)g.ny), nx, (u32)ny, (u32)nz, g.W, iso, isoI, wAll.view.padValue, wAll.view.padValueInt, wAll.sliceOcc);
       } else {
-        const unsigned blocks = grid_for((t1 - t0) * 64, 256, 8192);
-        hipLaunchKernelGGL((k_classify_pad_words<T>), dim3(blocks), dim3(256), 0, s, vox, wAll.bits, t0, t1, nx, ny, nz, g.W, iso, isoI,
-                           wAll.padValue, wAll.padValueInt, wAll.sliceOcc);
+        hipLaunchKernelGGL((k_classify_pad_words<T>), dim3(word_sweep_grid(t1 - t0)), dim3(256), 0, s, vox, wAll.bits, t0, t1, nx, ny, nz, g.W, iso, isoI,
+                           wAll.view.padValue, wAll.view.padValueInt, wAll.sliceOcc);
       }
       return hipGetLastError();
     });
-  if (wAll.regionSweep)
+  if (wAll.view.kind == VIEW_REGION && wAll.view.pitched)
     return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
       typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
       // cuberille_set_region: `g` is the box's layout, wAll.vox its first voxel in the caller's buffer, z0 / z1 slices of the box
       const u64 wps = (u64)g.ny * g.W, t0 = (u64)z0 * wps, t1 = (u64)z1 * wps;
       const T *box = (const T *)wAll.vox;
-      // the staged spans under the rule of the unpadded sweep: a box of 256 MiB and more, fewer than 2^32 words
-      const bool spans = tn.classify_variant != 1 && !tn.no_stream_classify && ((uintptr_t)box % sizeof(T)) == 0 &&
-                         ((u64)g.nx * (u64)g.ny * (u64)g.nzb * sizeof(T) >= (256ull << 20) || tn.classify_variant == 2) &&
-                         (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
-      if (spans) {
+      if (staged_spans(box, sizeof(T), (u64)g.nx * (u64)g.ny * (u64)g.nzb * sizeof(T), g, tn, true, true)) {
         const u64 nwordsAll = t1 - t0;
         const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-        const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;     // two workgroups per CU, whole rounds
-        const u64 rounds = (nspans + want - 1) / want;
-        const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
-        hipLaunchKernelGGL((k_classify_region_span_rows<T>), dim3(blocks), dim3(256), 0, s, box, wAll.bits + t0, nspans, nwordsAll,
-                           (u32)((u64)z0 * (u64)g.ny), g.nx, g.W, (u32)g.ny, wAll.rowPitch, wAll.slicePitch, iso, isoI, wAll.sliceOcc);
+        hipLaunchKernelGGL((k_classify_region_span_rows<T>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, box, wAll.bits + t0, nspans, nwordsAll,
+                           (u32)((u64)z0 * (u64)g.ny), g.nx, g.W, (u32)g.ny, wAll.view.rowPitch, wAll.view.slicePitch, iso, isoI, wAll.sliceOcc);
       } else {
-        const unsigned blocks = grid_for((t1 - t0) * 64, 256, 8192);
-        hipLaunchKernelGGL((k_classify_region_words<T>), dim3(blocks), dim3(256), 0, s, box, wAll.bits, t0, t1, g.nx, g.ny, g.W,
-                           wAll.rowPitch, wAll.slicePitch, iso, isoI, wAll.sliceOcc);
+        hipLaunchKernelGGL((k_classify_region_words<T>), dim3(word_sweep_grid(t1 - t0)), dim3(256), 0, s, box, wAll.bits, t0, t1, g.nx, g.ny, g.W,
+                           wAll.view.rowPitch, wAll.view.slicePitch, iso, isoI, wAll.sliceOcc);
       }
       return hipGetLastError();
     });
@@ -4097,12 +4102,7 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
     } else if (ragged_span_path(wAll, g, sizeof(T), tn)) {
       const u64 nwordsAll = nrows * g.W;
       const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-      const u64 want = tn.classify_grid > 0 ? (u64)tn.classify_grid : 512;     // two workgroups per CU
-      // (the workgroups take the spans in rounds: as many workgroups as fill every round -- 3907 spans of a 1000^3 volume
-      //  are 8 rounds of 489 rather than 7 of 512 and one of 323, whose time is a whole round's)
-      const u64 rounds = (nspans + want - 1) / want;
-      const unsigned blocks = (unsigned)((nspans + rounds - 1) / rounds);
-      hipLaunchKernelGGL((k_classify_span_rows<T, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, nspans, nwordsAll, g.nx, g.W, (u32)g.ny,
+      hipLaunchKernelGGL((k_classify_span_rows<T, BAND>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, vox, w.bits, nspans, nwordsAll, g.nx, g.W, (u32)g.ny,
                          iso, isoI, w.sliceOcc);
     } else if (ragged_stream_path(wAll, g, sizeof(T), tn)) {
       // ragged rows: flat stream of aligned 16-byte vectors (the first and last vector may reach up to 15 bytes
@@ -4126,13 +4126,12 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       hipLaunchKernelGGL(k_repack_rows, dim3(grid_for(nrows * g.W, 256, 0)), dim3(256), 0, s, flat, w.bits, g.nx, g.W, nrows, skew);
     } else {
       const u64 total = nrows * g.W;
-      const unsigned blocks = grid_for(total * 64, 256, 8192);
-      hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(blocks), dim3(256), 0, s, vox, w.bits, g.nx, g.W, (u64)0, nrows,
+      hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(word_sweep_grid(total)), dim3(256), 0, s, vox, w.bits, g.nx, g.W, (u64)0, nrows,
                          (u64)g.ny, iso, isoI, w.sliceOcc);
     }
     return hipGetLastError();
     };
-    if (wAll.band) {
+    if (wAll.view.kind == VIEW_BAND) {
       BandBoundsD bd;
       BandBoundsI bi;
       band_sweep_args<T>(wAll, prm, bd, bi);
@@ -4149,7 +4148,7 @@ hipError_t launch_occupancy(int pixel_type, const Workspace &w, const Grid &g, c
   size_t elem = 1;
   (void)by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t { elem = sizeof(*tag); return hipSuccess; });
   const bool aligned = g.nx % 64 == 0 && ((uintptr_t)w.vox % 16) == 0;
-  if (w.pad || w.regionSweep) return hipSuccess;                     // (the padded and the pitched sweeps mark the occupancy themselves)
+  if (w.view.kind == VIEW_BORDER || (w.view.kind == VIEW_REGION && w.view.pitched)) return hipSuccess;                     // (the padded and the pitched sweeps mark the occupancy themselves)
   if (ragged_span_path(w, g, elem, tn)) return hipSuccess;           // (that sweep marks the occupancy itself)
   if ((aligned && occupancy_shift(g) < 0) || ragged_stream_path(w, g, elem, tn))
     hipLaunchKernelGGL(k_occupancy, dim3(g.nzb), dim3(256), 0, s, w.bits, (size_t)g.ny * g.W, w.sliceOcc);
@@ -4490,55 +4489,49 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     // inverse of a diagonal matrix by cofactors has exact zeros off its diagonal); 0 anything else
     // (cuberille_set_border: the padded region starts one index below the caller's; the padded kernels' forms 1 and 2 hold -1)
     // (cuberille_set_region: the region kernels take the start index at run time in every form: the matrices alone decide)
-    const int at0 = w.pad ? -1 : 0;
-    bool diag = dirIdentity != 0 && (w.region || (geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0)) && tn.proj_ident != 0;
+    // (VIEW_REGION: a box that is a pointer offset into its buffer with its start index at 0 is a plain image to the walk)
+    const View &v = w.view;
+    const int view = v.kind == VIEW_REGION && !v.pitched && geo.istart[0] == 0 && geo.istart[1] == 0 && geo.istart[2] == 0 ? (int)VIEW_WHOLE : v.kind;
+    const int at0 = view == VIEW_BORDER ? -1 : 0;
+    bool diag = dirIdentity != 0 && (view == VIEW_REGION || (geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0)) && tn.proj_ident != 0;
     bool unit = diag;
     for (int i = 0; i < 9; i++) {
       if (i % 4 != 0) diag = diag && geo.p2i[i] == 0.0;
       unit = unit && geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0);
     }
     const int geom = unit ? 2 : diag ? 1 : 0;
-#define CUBERILLE_LAUNCH_PROJECT_FRAME(MODE, GEOM, PAD, REGION)                                                              \
-    hipLaunchKernelGGL((k_project<T, MODE, GEOM, PAD, REGION>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
-                       w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
-                       w.escCap, dyn, w.padValue, w.padValueInt, w.rowPitch, w.slicePitch)
-#define CUBERILLE_LAUNCH_PROJECT_BAND(GEOM)                                                                                  \
-    hipLaunchKernelGGL((k_project<T, 0, GEOM, false, false, true>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,  \
-                       w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,  \
-                       w.escCap, dyn, bandTail[0], bandTail[1], bandTail[2], bandTail[3])
-#define CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, PAD) CUBERILLE_LAUNCH_PROJECT_FRAME(MODE, GEOM, PAD, false)
-#define CUBERILLE_LAUNCH_PROJECT(MODE, GEOM) CUBERILLE_LAUNCH_PROJECT_PAD(MODE, GEOM, false)
-#define CUBERILLE_LAUNCH_PROJECT_GEOM(MODE)                                                                                  \
-    do { if (geom == 2) CUBERILLE_LAUNCH_PROJECT(MODE, 2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT(MODE, 1);            \
-         else CUBERILLE_LAUNCH_PROJECT(MODE, 0); } while (0)
-    if (w.band) {
-      // a whole volume, every slice in the buffer, no ring and no pitches: MODE 0, the only one offered with a band (count_prepare)
-      if (mode != 0 || w.pad || w.region) return hipErrorInvalidValue;
-      const T bandTail[4] = {value_as<T>(w.bandV[0], w.bandVi[0]), value_as<T>(w.bandV[1], w.bandVi[1]),
-                                       value_as<T>(w.bandV[2], w.bandVi[2]), value_as<T>(w.bandV[3], w.bandVi[3])};
-      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_BAND(2); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_BAND(1);
-      else CUBERILLE_LAUNCH_PROJECT_BAND(0);
-    } else
-    if (w.pad) {
-      // a whole volume, every slice in the (implied) buffer: MODE 0, the only one offered with a border (count_prepare)
-      if (mode != 0) return hipErrorInvalidValue;
-      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_PAD(0, 2, true); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_PAD(0, 1, true);
-      else CUBERILLE_LAUNCH_PROJECT_PAD(0, 0, true);
-    } else
-    if (w.region) {
-      // a whole volume (the box), every slice in the buffer: MODE 0, the only one offered with a region (count_prepare)
-      if (mode != 0) return hipErrorInvalidValue;
-      if (geom == 2) CUBERILLE_LAUNCH_PROJECT_FRAME(0, 2, false, true); else if (geom == 1) CUBERILLE_LAUNCH_PROJECT_FRAME(0, 1, false, true);
-      else CUBERILLE_LAUNCH_PROJECT_FRAME(0, 0, false, true);
-    } else
-    if (mode == 1) CUBERILLE_LAUNCH_PROJECT_GEOM(1);
-    else if (mode == 2) CUBERILLE_LAUNCH_PROJECT_GEOM(2);
-    else CUBERILLE_LAUNCH_PROJECT_GEOM(0);
-#undef CUBERILLE_LAUNCH_PROJECT_GEOM
-#undef CUBERILLE_LAUNCH_PROJECT
-#undef CUBERILLE_LAUNCH_PROJECT_PAD
-#undef CUBERILLE_LAUNCH_PROJECT_FRAME
-#undef CUBERILLE_LAUNCH_PROJECT_BAND
+    // a border, a region and a band belong to a whole volume with every slice in the buffer: MODE 0, the only one offered
+    // with them (resolve_view)
+    if (view != VIEW_WHOLE && mode != 0) return hipErrorInvalidValue;
+    // one instantiation per (MODE, GEOM, VIEW); the four trailing arguments are the view's payload in the types of WalkArg
+    auto launch = [&](auto modeTag, auto geomTag, auto viewTag) {
+      constexpr int MODE = decltype(modeTag)::value, GEOM = decltype(geomTag)::value, VIEW = decltype(viewTag)::value;
+      if constexpr (MODE == 0 || VIEW == VIEW_WHOLE) {
+        auto go = [&](auto a0, auto a1, auto a2, auto a3) {
+          hipLaunchKernelGGL((k_project<T, MODE, GEOM, VIEW>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,
+                             w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,
+                             w.escCap, dyn, a0, a1, a2, a3);
+        };
+        if constexpr (VIEW == VIEW_BAND)
+          go(value_as<T>(v.bandV[0], v.bandVi[0]), value_as<T>(v.bandV[1], v.bandVi[1]), value_as<T>(v.bandV[2], v.bandVi[2]),
+             value_as<T>(v.bandV[3], v.bandVi[3]));
+        else go(v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
+      }
+    };
+    auto by_geom = [&](auto modeTag, auto viewTag) {
+      if (geom == 2) launch(modeTag, std::integral_constant<int, 2>(), viewTag);
+      else if (geom == 1) launch(modeTag, std::integral_constant<int, 1>(), viewTag);
+      else launch(modeTag, std::integral_constant<int, 0>(), viewTag);
+    };
+    auto by_mode = [&](auto viewTag) {
+      if (mode == 1) by_geom(std::integral_constant<int, 1>(), viewTag);
+      else if (mode == 2) by_geom(std::integral_constant<int, 2>(), viewTag);
+      else by_geom(std::integral_constant<int, 0>(), viewTag);
+    };
+    if (view == VIEW_BAND) by_mode(std::integral_constant<int, VIEW_BAND>());
+    else if (view == VIEW_BORDER) by_mode(std::integral_constant<int, VIEW_BORDER>());
+    else if (view == VIEW_REGION) by_mode(std::integral_constant<int, VIEW_REGION>());
+    else by_mode(std::integral_constant<int, VIEW_WHOLE>());
     return hipGetLastError();
   });
 }

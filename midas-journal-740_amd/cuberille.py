@@ -206,8 +206,9 @@ class Extractor:
             raise _abi.CuberilleError(rc, text.decode() if text else "")
         self.device = int(device)
         self.result = None
-        self._border = (0, 0)               # set_border: width, and the value as a 64-bit integer pixel type would hold it
-        self._region = None                 # set_region: (start_xyz, size_xyz) of the box, or None
+        # what the view setters left: border (width, the value as a 64-bit integer pixel type would hold it), region
+        # ((start_xyz, size_xyz) of the box, or None), band ((lower, upper, inside, outside), or None)
+        self._view = {"border": (0, 0), "region": None, "band": None}
 
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx:
@@ -219,6 +220,16 @@ class Extractor:
             self.close()
         except Exception:
             pass
+
+    def _check_view(self, desc, params, boxed=True):
+        """What can be said of the iso value and of the view settings (set_border, set_region) against the image an entry
+        point is about to be handed, before a device is touched; the library says the rest, the band's part included.
+        boxed: the entry point offers a region, so a box is held against desc; the others leave a set region to the
+        library's refusal."""
+        check_iso(int(desc.pixel_type), params)
+        check_border(int(desc.pixel_type), self._view["border"])
+        if boxed:
+            check_region(desc, self._view["region"])
 
     def warm_up(self, desc=None, params=None):
         """cuberille_warm_up: load the code objects and, with an image description, reserve the workspace for such a volume
@@ -245,9 +256,7 @@ class Extractor:
         """vol: mha.Volume in host memory.  Upload + extract (PCIe-inclusive)."""
         vox = np.ascontiguousarray(vol.voxels)
         desc = make_desc(vox.dtype, vol.dims, vol.spacing, vol.origin, vol.direction, getattr(vol, "index_start", (0, 0, 0)))
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
-        check_region(desc, self._region)
+        self._check_view(desc, params)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_host(
             self._ctx, C.byref(desc), C.c_void_p(vox.ctypes.data), C.byref(params), C.byref(res)))
@@ -261,8 +270,7 @@ class Extractor:
         by source ends the call (CuberilleError ERR_SOURCE, the exception chained as its cause)."""
         nx, ny, _ = (int(v) for v in desc.dims)
         dtype = np.dtype(PIXEL_DTYPES[int(desc.pixel_type)])
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
+        self._check_view(desc, params, boxed=False)
         raised = []
 
         def trampoline(_user, dst, z0, z1):
@@ -294,9 +302,7 @@ class Extractor:
             return self.extract_stream(desc, st, params), st
 
     def extract_device(self, dev_ptr, desc, params, slab=None):
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
-        check_region(desc, self._region)
+        self._check_view(desc, params)
         res = _abi.Result()
         _abi.check(self._ctx, self._lib.cuberille_extract_device(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -305,9 +311,7 @@ class Extractor:
         return res
 
     def count(self, dev_ptr, desc, params, slab=None):
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
-        check_region(desc, self._region)
+        self._check_view(desc, params)
         npnt, ncell = C.c_uint64(), C.c_uint64()
         _abi.check(self._ctx, self._lib.cuberille_count(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -327,8 +331,7 @@ class Extractor:
     def step_begin(self, dev_ptr, desc, params, slab=None):
         """Count and the offset-free part of the emit, launched back to back without waiting (cuberille_step_begin).
         Returns (device pointer, bytes) of this rank's row, to be all-gathered in rank order."""
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
+        self._check_view(desc, params, boxed=False)
         p, n = C.c_void_p(), C.c_size_t()
         _abi.check(self._ctx, self._lib.cuberille_step_begin(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -338,8 +341,7 @@ class Extractor:
     def step_classify(self, dev_ptr, desc, params, slab=None):
         """First half of step_begin for the bits-first halo (cuberille_step_classify): thresholds the owned slices and
         returns (device pointer of the buffer's bit volume, words per slice) without waiting."""
-        check_iso(int(desc.pixel_type), params)
-        check_border(int(desc.pixel_type), self._border)
+        self._check_view(desc, params, boxed=False)
         p, n = C.c_void_p(), C.c_size_t()
         _abi.check(self._ctx, self._lib.cuberille_step_classify(
             self._ctx, C.byref(desc), C.c_void_p(dev_ptr), C.byref(params),
@@ -434,7 +436,7 @@ class Extractor:
         exact = iso_int_of(value)
         as_int = 0 if exact is None else ((exact + (1 << 63)) % (1 << 64)) - (1 << 63)
         _abi.check(self._ctx, self._lib.cuberille_set_border(self._ctx, int(width), float(value), as_int))
-        self._border = (int(width), exact)
+        self._view["border"] = (int(width), exact)
 
     def set_band(self, lower, upper, inside=1, outside=0):
         """Mesh a label or a value band in place (cuberille_set_band): every later whole-volume extraction gives the mesh of
@@ -445,10 +447,12 @@ class Extractor:
         the B-spline interpolator, a held or recursive-Gaussian gradient and the two projection variants are refused there."""
         v, vi, _ = _band_arrays((lower, upper, inside, outside))
         _abi.check(self._ctx, self._lib.cuberille_set_band(self._ctx, 1, v, vi))
+        self._view["band"] = (lower, upper, inside, outside)
 
     def clear_band(self):
         """Back to the default: the pixels are thresholded against the iso value themselves."""
         _abi.check(self._ctx, self._lib.cuberille_set_band(self._ctx, 0, None, None))
+        self._view["band"] = None
 
     def set_region(self, start_xyz, size_xyz):
         """Extract a box of a larger volume in place (cuberille_set_region): every later whole-volume extraction still takes
@@ -460,12 +464,12 @@ class Extractor:
         start = (C.c_int64 * 3)(*[int(v) for v in start_xyz])
         size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
         _abi.check(self._ctx, self._lib.cuberille_set_region(self._ctx, start, size))
-        self._region = None if not any(int(v) for v in size_xyz) else (tuple(int(v) for v in start_xyz), tuple(int(v) for v in size_xyz))
+        self._view["region"] = None if not any(int(v) for v in size_xyz) else (tuple(int(v) for v in start_xyz), tuple(int(v) for v in size_xyz))
 
     def clear_region(self):
         """Back to the default: the buffer handed over is the image."""
         _abi.check(self._ctx, self._lib.cuberille_set_region(self._ctx, None, None))
-        self._region = None
+        self._view["region"] = None
 
     def set_interpolator(self, kind, spline_order=3, coordinate_bits=32, coefficient_bits=32):
         """The value interpolator of the walk for the later extractions (cuberille_set_interpolator): _abi.INTERP_LINEAR
@@ -633,29 +637,28 @@ class ExtractorGroup:
         ctx = self.context(i)
         _abi.check(ctx, self._lib.cuberille_debug_set_option(ctx, name.encode(), int(value)))
 
+    def _on_every_member(self, setter, *args):
+        for i in range(len(self.devices)):
+            ctx = self.context(i)
+            _abi.check(ctx, setter(ctx, *args))
+
     def set_border(self, width, value=0):
         """An implied border (Extractor.set_border) on every member: the group's extraction then raises the library's
         refusal -- the ring would have to reach across the slabs."""
-        for i in range(len(self.devices)):
-            ctx = self.context(i)
-            _abi.check(ctx, self._lib.cuberille_set_border(ctx, int(width), float(value), 0))
+        self._on_every_member(self._lib.cuberille_set_border, int(width), float(value), 0)
 
     def set_band(self, lower, upper, inside=1, outside=0):
         """A band (Extractor.set_band) on every member: the group's extraction then raises the library's refusal -- the binary
         image belongs to one context's whole volume."""
         v, vi, _ = _band_arrays((lower, upper, inside, outside))
-        for i in range(len(self.devices)):
-            ctx = self.context(i)
-            _abi.check(ctx, self._lib.cuberille_set_band(ctx, 1, v, vi))
+        self._on_every_member(self._lib.cuberille_set_band, 1, v, vi)
 
     def set_region(self, start_xyz, size_xyz):
         """A region (Extractor.set_region) on every member: the group's extraction then raises the library's refusal -- a
         box belongs to one context's whole volume."""
         start = (C.c_int64 * 3)(*[int(v) for v in start_xyz])
         size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
-        for i in range(len(self.devices)):
-            ctx = self.context(i)
-            _abi.check(ctx, self._lib.cuberille_set_region(ctx, start, size))
+        self._on_every_member(self._lib.cuberille_set_region, start, size)
 
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
@@ -714,12 +717,15 @@ class CuberilleImageToMeshFilter:
     over).  Output: Mesh with the reference's vertex ids, cell order and coordinates.
     """
 
-    # The band's state alone is held at class level, not in __init__ with the rest: Update() reads it on every call, and
-    # tests/test_region.py::test_python_filter_index_arithmetic runs Update() on a filter made by __new__ with only the
-    # attributes set that Update() read before the band existed.  An instance's setters shadow these; none is mutable.
-    _band_on = False                              # InsideBandOn: off, like the reference
-    _band = (0, 0)                                # SetInsideBand: lower, upper
-    _band_values = (1, 0)                         # SetBandValues: NumericTraits<InputPixelType>::One / Zero
+    # Off unless InsideBandOn: the one default kept at class level, since Update() reads it on every call and a filter made
+    # without __init__ (tests/test_region.py::test_python_filter_index_arithmetic) has only what Update() read before the band
+    _band_on = False
+
+    # The view settings that several devices do not offer: (attribute, its "off", the setting by name, why)
+    _NOT_IN_A_GROUP = (
+        ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
+        ("_region", None, "a region (SetExtractionRegion / cuberille_set_region)", "a box belongs to one context's whole volume"),
+        ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"))
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -746,6 +752,8 @@ class CuberilleImageToMeshFilter:
         self._pad_border = False                  # SetPadBorder: off, like the reference
         self._border_pad_value = 0                # SetBorderPadValue: NumericTraits<InputPixelType>::Zero
         self._region = None                       # SetExtractionRegion: (index_xyz, size_xyz) in ITK index space, or None
+        self._band = (0, 0)                       # SetInsideBand: lower, upper
+        self._band_values = (1, 0)                # SetBandValues: NumericTraits<InputPixelType>::One / Zero
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -962,16 +970,9 @@ class CuberilleImageToMeshFilter:
         if self._input is None:
             # the ITK pipeline throws for a missing required input (txx:33)
             raise RuntimeError("CuberilleImageToMeshFilter: input 0 is required but not set")
-        if len(self._devices) > 1 and self._pad_border:
-            # (before a device is touched: the ring would have to reach across the slabs)
-            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "an implied border (SetPadBorder / cuberille_set_border) is not "
-                                      "offered in a group: the ring would have to reach across slabs")
-        if len(self._devices) > 1 and self._region is not None:
-            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "a region (SetExtractionRegion / cuberille_set_region) is not "
-                                      "offered in a group: a box belongs to one context's whole volume")
-        if len(self._devices) > 1 and self._band_on:
-            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "a band (InsideBandOn / cuberille_set_band) is not offered in a "
-                                      "group: the binary image belongs to one context's whole volume")
+        for attr, off, name, why in self._NOT_IN_A_GROUP:      # (before a device is touched)
+            if len(self._devices) > 1 and getattr(self, attr) != off:
+                raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "%s is not offered in a group: %s" % (name, why))
         if self._band_on:
             # (before a device is touched: the four values against the input's pixel type)
             check_band(int(self._group_desc(self._input).pixel_type), self._band + self._band_values)

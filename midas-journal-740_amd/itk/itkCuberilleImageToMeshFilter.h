@@ -42,8 +42,7 @@
 #include <string>
 #include <vector>
 
-struct cuberille_ctx;     // include/cuberille_hip.h
-struct cuberille_group;
+#include "cuberille_hip.h"
 
 namespace itk
 {
@@ -317,7 +316,12 @@ private:
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them
-  void ApplyBand(::cuberille_ctx *ctx) const;   // cuberille_set_band on ctx from the four members (or off); throws on a refusal
+  // SetExtractionRegion as a position in the buffer `desc` describes: ITK index - the buffer's start index (all zero: none)
+  void BufferBox(const ::cuberille_image_desc &desc, int64_t start[3], int64_t size[3]) const;
+  // PadBorder onto ctx and, where asked for, the extraction region (a group's members take none) and the band (SetInput's
+  // reservation needs none), each on or off as the members say; returns null, or the name of the setter that refused (its
+  // text: cuberille_last_error(ctx))
+  const char *ApplyView(::cuberille_ctx *ctx, const ::cuberille_image_desc &desc, bool withBox, bool withBand) const;
   double m_LastDeviceSeconds;
   double m_LastMeshFillSeconds;
   double m_LastExtractSeconds;

@@ -605,14 +605,34 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::BandAr
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
-void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::ApplyBand(::cuberille_ctx *ctx) const
+void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::BufferBox(const ::cuberille_image_desc &desc,
+                                                                                   int64_t start[3], int64_t size[3]) const
 {
+  for (int i = 0; i < 3; i++)
+    {
+    start[i] = m_HasExtractionRegion ? static_cast<int64_t>(m_ExtractionRegion.GetIndex()[i]) - desc.index_start[i] : 0;
+    size[i] = m_HasExtractionRegion ? static_cast<int64_t>(m_ExtractionRegion.GetSize()[i]) : 0;
+    }
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+const char *CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::ApplyView(::cuberille_ctx *ctx,
+                                                                                           const ::cuberille_image_desc &desc,
+                                                                                           bool withBox, bool withBand) const
+{
+  // (a refusal would leave the context's previous setting in force: the caller reports it)
+  if (cuberille_set_border(ctx, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
+                           cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue)) != CUBERILLE_OK)
+    return "cuberille_set_border";
+  int64_t boxStart[3], boxSize[3];
+  this->BufferBox(desc, boxStart, boxSize);
+  if (withBox && cuberille_set_region(ctx, boxStart, boxSize) != CUBERILLE_OK) return "cuberille_set_region";
   double v[4];
   int64_t vi[4];
   this->BandArguments(v, vi);
-  // (a refusal would leave the context's previous band in force: reported, like the border's and the region's)
-  if (cuberille_set_band(ctx, m_InsideBand ? 1 : 0, m_InsideBand ? v : 0, m_InsideBand ? vi : 0) != CUBERILLE_OK)
-    itkExceptionMacro(<< "cuberille_set_band: " << cuberille_last_error(ctx));
+  if (withBand && cuberille_set_band(ctx, m_InsideBand ? 1 : 0, m_InsideBand ? v : 0, m_InsideBand ? vi : 0) != CUBERILLE_OK)
+    return "cuberille_set_band";
+  return 0;
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>
@@ -630,18 +650,10 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::SetInp
       }
     else if (this->AcquireContext(false))
       {
-      // (PadBorderOn() ahead of SetInput: the workspace of the image with its border)
-      (void)cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
-                                 cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
-      // (SetExtractionRegion ahead of SetInput: the workspace of the box; a box outside this image is Update()'s to report)
-      int64_t boxStart[3] = {0, 0, 0}, boxSize[3] = {0, 0, 0};
-      if (m_HasExtractionRegion)
-        for (int i = 0; i < 3; i++)
-          {
-          boxStart[i] = static_cast<int64_t>(m_ExtractionRegion.GetIndex()[i]) - desc.index_start[i];
-          boxSize[i] = static_cast<int64_t>(m_ExtractionRegion.GetSize()[i]);
-          }
-      if (cuberille_set_region(m_Context, boxStart, boxSize) != CUBERILLE_OK) (void)cuberille_set_region(m_Context, 0, 0);
+      // (PadBorderOn() / SetExtractionRegion ahead of SetInput: the workspace of the image with its border, or of the box; a
+      //  setting this image does not take is Update()'s to report)
+      //  (cuberille_set_border takes every value the members hold, so a refusal here is the box's)
+      if (this->ApplyView(m_Context, desc, true, false)) (void)cuberille_set_region(m_Context, 0, 0);
       (void)cuberille_warm_up(m_Context, &desc, 0);
       }
     }
@@ -716,15 +728,11 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     }
 
   // SetExtractionRegion: ITK index space -> a position in the buffer; inside the buffered region, and on the device's walk
-  int64_t boxStart[3] = {0, 0, 0}, boxSize[3] = {0, 0, 0};
   if (m_HasExtractionRegion)
     {
     cuberille_image_desc box;
-    for (int i = 0; i < 3; i++)
-      {
-      boxStart[i] = static_cast<int64_t>(m_ExtractionRegion.GetIndex()[i]) - desc.index_start[i];
-      boxSize[i] = static_cast<int64_t>(m_ExtractionRegion.GetSize()[i]);
-      }
+    int64_t boxStart[3], boxSize[3];
+    this->BufferBox(desc, boxStart, boxSize);
     const int rc = cuberille_region_desc(&desc, boxStart, boxSize, &box);
     if (rc == CUBERILLE_ERR_LIMIT)
       itkExceptionMacro(<< "the extraction region's index must lie within +-2^30 and, with its size, below 2^31");
@@ -748,12 +756,10 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   if (grouped)
     {
     this->AcquireGroup(true);
-    // (an implied border on the members: the group's extraction refuses it, and that message is what the caller sees)
+    // (an implied border or a band on the members: the group's extraction refuses it, and that message is what the caller sees)
     for (int i = 0; i < static_cast<int>(m_Devices.size()); i++)
-      (void)cuberille_set_border(cuberille_group_context(m_Group, i), m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
-                                 cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue));
-    // (... and a band: the same)
-    for (int i = 0; i < static_cast<int>(m_Devices.size()); i++) this->ApplyBand(cuberille_group_context(m_Group, i));
+      if (const char *setter = this->ApplyView(cuberille_group_context(m_Group, i), desc, false, true))
+        itkExceptionMacro(<< setter << ": " << cuberille_last_error(cuberille_group_context(m_Group, i)));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_group_extract_host: " << cuberille_group_last_error(m_Group));
@@ -770,12 +776,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_set_interpolator(m_Context, deviceBSpline ? CUBERILLE_INTERP_BSPLINE : CUBERILLE_INTERP_LINEAR, 3,
                                    deviceBSpline ? bsplineBits : 0, deviceBSpline ? bsplineBits : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
-    if (cuberille_set_border(m_Context, m_PadBorder ? 1 : 0, static_cast<double>(m_BorderPadValue),
-                             cuberille_detail::IsoInt<InputPixelType>::Get(m_BorderPadValue)) != CUBERILLE_OK)
-      itkExceptionMacro(<< "cuberille_set_border: " << cuberille_last_error(m_Context));
-    if (cuberille_set_region(m_Context, boxStart, boxSize) != CUBERILLE_OK)
-      itkExceptionMacro(<< "cuberille_set_region: " << cuberille_last_error(m_Context));
-    this->ApplyBand(m_Context);
+    if (const char *setter = this->ApplyView(m_Context, desc, true, true))
+      itkExceptionMacro(<< setter << ": " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
