@@ -162,7 +162,7 @@ typedef struct {
   float ms_count;           /* per-word face / created-corner counts and all prefix sums (one kernel) */
   float ms_scan;            /* 0: the scans run inside the count kernel since ABI 4 (field kept for layout) */
   float ms_emit_points;     /* vertex scatter: AddVertex without the projection (txx:256-276) */
-  float ms_project;         /* vertex projection (txx:439-474) */
+  float ms_project;         /* vertex projection (txx:439-474); with cuberille_set_point_normals on, the normals pass behind it too */
   float ms_emit_cells;      /* quad / triangle scatter incl. the diagonal split (txx:278-332) */
   float ms_total;           /* ms_pass + the emit phase (points, projection, cells).  When cuberille_emit_points started the
                                vertex phase ahead of cuberille_emit, the two phases are timed as intervals of their own and
@@ -453,6 +453,45 @@ int cuberille_region_desc(const cuberille_image_desc *img, const int64_t start[3
  * (cuberille_hold_gradient), CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN and the ADVANCED and LINESEARCH branches. */
 int cuberille_set_band(cuberille_ctx *ctx, int on, const double v[4], const int64_t vi[4]);
 int cuberille_band_check(int pixel_type, const double v[4], const int64_t vi[4]);
+/* Point normals (new symbols within ABI 13, no struct changed).  A cuberille mesh is made of axis-aligned quads: its face
+ * normals are six constant directions.  What shades the projected surface smoothly is the gradient of the image at each vertex --
+ * the vector the walk evaluates in every pass and throws away (normal = m_GradientInterpolator->Evaluate(vertex);
+ * normal.Normalize(), txx:451-452).  With the setting on, every later extraction also leaves N(p) for every point p, one
+ * definition for every route and pixel type: the three floats of p exactly as they stand in the points buffer -- behind the walk,
+ * or at the lattice start with project_vertices off -- go through the steps of the walk's contract: I4 the
+ * point to a continuous index in double; I5 the eight sites clamped to the image; I6 at each site the central-difference gradient
+ * in float with the direction transform; I7 their linear interpolation (the sum in double in counter order 0..7, zero weights
+ * skipped, stopped once the weights sum to exactly 1, each component narrowed to float); I8 Normalize(): the double sqrt of the
+ * sum of squares, each component float(double(c) / norm).  Quirk Q4: there is no zero guard -- a zero gradient (a plateau)
+ * gives NaN normals and they stay NaN.  N points the way the reference's `normal` points: TOWARDS INCREASING PIXEL VALUES, which
+ * for an object brighter than its surroundings is INTO the object; it is not flipped.  The gradient is the central one of the
+ * voxels with the B-spline interpolator too.  With a source view the image is the view's frame: the padded image
+ * (cuberille_set_border), the box (cuberille_set_region), B (cuberille_set_band).
+ * The normals are written by a pass of their own behind the walk (behind the vertex scatter with the projection off), one visit
+ * per vertex; with stage timing on its time is part of ms_project.  The buffer is one more row of the workspace, 12 bytes per
+ * point, sized where the points are (cuberille_warm_up runs its internal extraction with the setting as it stands: on, the
+ * pass's code is loaded and the row exists; off, nothing is reserved for it).  Points, cells and counters are the bytes of the
+ * same extraction with the setting off.
+ * cuberille_set_point_normals: on != 0 / 0 (the default: nothing allocated, nothing launched, every result as before the symbol
+ *   existed; turning it off also frees the row and the normals of the last mesh).  Not between cuberille_step_begin and _end.
+ * cuberille_normals_device: *d_normals = float[3*n_points] of the last extraction in point-id order, in the library's buffer
+ *   (valid until the next call on the context; it may be null for an empty mesh).  cuberille_normals_download: the same into host memory.
+ *   Both: CUBERILLE_ERR_STATE with a message when the last extraction ran with the setting off (or there is no mesh).  The point-id
+ *   offset of cuberille_emit does not touch them: entry i belongs to the i-th point of the buffer.
+ * cuberille_mesh_write_vtk on a context that holds normals appends "POINT_DATA n" / "NORMALS normals float" and the vectors, in the
+ *   points' number format; with the setting off the file is byte for byte what it always was.
+ * Offered: cuberille_extract_host, cuberille_extract_device, cuberille_extract_stream, cuberille_count + cuberille_emit_points /
+ * cuberille_emit on a whole volume; project_vertices on or off, every projection branch, both interpolators, each source view
+ * where that view is offered.  Refused with CUBERILLE_ERR_ARGUMENT and a message that says "point normals", the context left
+ * usable: a slab that is not the whole volume; the cuberille_step_* calls; cuberille_group_extract_host with a member that has the
+ * setting on; a context holding a gradient (cuberille_hold_gradient: the reference would evaluate the stale image there, and which
+ * image is meant is ambiguous); CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN. */
+int cuberille_set_point_normals(cuberille_ctx *ctx, int on);
+int cuberille_normals_device(cuberille_ctx *ctx, const float **d_normals);
+int cuberille_normals_download(cuberille_ctx *ctx, float *normals);
+/* Test aid (new symbol): the bytes of device memory the context's workspace holds at this moment -- the capacities of all its
+ * buffers added up (what cuberille_warm_up and the extractions reserved and kept). */
+int cuberille_debug_device_bytes(cuberille_ctx *ctx, size_t *bytes);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

@@ -36,6 +36,7 @@ EXPORTS = [
     "cuberille_group_plan", "cuberille_group_warm_up", "cuberille_group_extract_host", "cuberille_group_slab_result",
     "cuberille_group_mesh_host", "cuberille_group_release_host_mesh", "cuberille_group_mesh_write_vtk",
     "cuberille_group_debug_fail_alloc",
+    "cuberille_set_point_normals", "cuberille_normals_device", "cuberille_normals_download", "cuberille_debug_device_bytes",
 ]
 GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
@@ -142,6 +143,10 @@ def lib():
     L.cuberille_region_desc.argtypes = [C.POINTER(ImageDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(ImageDesc)]
     L.cuberille_set_band.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.cuberille_band_check.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.cuberille_set_point_normals.argtypes = [vp, C.c_int]
+    L.cuberille_normals_device.argtypes = [vp, C.POINTER(vp)]
+    L.cuberille_normals_download.argtypes = [vp, vp]
+    L.cuberille_debug_device_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

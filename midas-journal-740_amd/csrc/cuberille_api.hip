@@ -22,6 +22,10 @@
 #include <utility>
 #include <vector>
 
+namespace cuberille {
+// (cuberille_vtk.cpp, host code: the NORMALS block of cuberille_mesh_write_vtk)
+int append_vtk_normals(const char *path, const float *normals, uint64_t n_points, int n_threads);
+}
 using namespace cuberille;
 
 namespace {
@@ -124,6 +128,10 @@ struct cuberille_ctx {
   int64_t regionSize[3] = {0, 0, 0};     // ... and its size
   int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
+  bool pointNormals = false;             // cuberille_set_point_normals: every later extraction also leaves the normal of every point ...
+  DevBuf normals;                        // ... 3 floats per point of `points`, same order (reserved and written only while the setting is on)
+  bool countNormals = false;             // ... the setting as the running count/emit pair found it
+  bool haveNormals = false;              // ... and whether the last mesh came with its normals
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
   Totals *hostTotals = nullptr;          // pinned
@@ -185,6 +193,13 @@ namespace {
 // The timing marks of an extraction, one event each (cuberille_ctx::ev); which a mode records: mark(), by finish_result.
 enum Mark { PASS_BEGIN, CLASSIFY_END, PASS_END, CELLS_BEGIN, POINTS_BEGIN, POINTS_END, PROJECT_END, END };
 hipError_t mark(cuberille_ctx *c, Mark m);
+
+// every device buffer a context owns (cuberille_destroy frees them, cuberille_debug_device_bytes adds them up)
+std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
+  return {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
+          &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
+          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals};
+}
 
 int fail(cuberille_ctx *c, int code, const std::string &msg) {
   if (c) c->err = msg; else g_create_error = msg;
@@ -338,7 +353,12 @@ bool converts(int pixel_type, double v) {
   return hi == lo || (v > lo - 1.0 && v < hi + 1.0);
 }
 
-int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm) {
+// The entry points that differ in what they offer of a setting (the source views: resolve_view; point normals: validate).
+// ROUTE_HOST: cuberille_extract_host, which uploads a box alone.  ROUTE_WARM_UP only reserves: it looks at what changes a size
+// (the border, the region), not at the band nor at the parameters.
+enum Route { ROUTE_DEVICE, ROUTE_HOST, ROUTE_SLAB, ROUTE_STEP, ROUTE_STREAM, ROUTE_GROUP, ROUTE_WARM_UP, N_ROUTES };
+
+int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm, Route route = ROUTE_DEVICE) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!img || !vox || !prm) return fail(c, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
   if (pixel_size(img->pixel_type) == 0) return fail(c, CUBERILLE_ERR_ARGUMENT, "unknown pixel type");
@@ -366,6 +386,17 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
       return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is offered with the central-difference gradient only");
     if (c->holdGradient)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is not offered on a context holding a gradient (cuberille_hold_gradient)");
+  }
+  if (c->pointNormals) {
+    // cuberille_set_point_normals: one definition, the central-difference gradient of the CURRENT whole volume at the final vertex
+    // (a slab that is not the whole volume: count_prepare)
+    if (route == ROUTE_STEP)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to one context's whole volume: not offered with the cuberille_step_* calls");
+    if (c->holdGradient)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) are not offered on a context holding a gradient "
+                                             "(cuberille_hold_gradient): the reference would evaluate the stale image there");
+    if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) are the central-difference gradient: not offered with CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN");
   }
   // the iso value is an InputPixelType in the reference (h:180-181)
   if (!converts(img->pixel_type, prm->iso_value))
@@ -429,10 +460,7 @@ void cuberille_destroy(cuberille_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->own) (void)hipStreamSynchronize(c->own);
   if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);
-  DevBuf *bufs[] = {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
-                    &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
-                    &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch};
-  for (DevBuf *b : bufs) b->release();
+  for (DevBuf *b : device_buffers(c)) b->release();
   c->hostPoints.release();
   c->hostCells.release();
   if (c->hostTotals) (void)hipHostFree(c->hostTotals);
@@ -513,9 +541,7 @@ void resolve(const cuberille_image_desc *img, const cuberille_params *prm, Geo &
 }
 
 // ---- source views: cuberille_set_border, cuberille_set_region and cuberille_set_band as one kind of setting -----------------
-// The entry points that differ in what they offer of a view.  ROUTE_HOST: cuberille_extract_host, which uploads a box alone.
-// ROUTE_WARM_UP only reserves: it looks at what changes a size (the border, the region), not at the band nor at the parameters.
-enum Route { ROUTE_DEVICE, ROUTE_HOST, ROUTE_SLAB, ROUTE_STEP, ROUTE_STREAM, ROUTE_GROUP, ROUTE_WARM_UP, N_ROUTES };
+// (the entry points that differ in what they offer of a view: enum Route, above validate)
 
 // The one table of what is not offered: per kind its name in words and as the C function, the reason per route (null: offered)
 // and what a second image of the view's shape -- B-spline coefficients, a gradient image -- would have to be.
@@ -779,18 +805,20 @@ size_t cmap_bytes(const Grid &g, const Tuning &t) {
 struct Want { size_t bytes, cover; };
 struct EmitSizes {
   Want points, cells;                 // required
+  Want normals;                       // cuberille_set_point_normals: required while the setting is on (0 bytes: off)
   Want headV, headQ;                  // optional (4 B per 64 outputs)
   size_t cmap, escCap;                // optional; THIN_HALO: entries of the escape list (required there)
 };
 
 EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u64 nV, u64 totQ, u64 nQ, size_t planeCorners,
-                     size_t nwords) {
+                     size_t nwords, bool normals) {
   const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
   const size_t quad = (triangles ? 6 : 4) * sizeof(u64);
   const bool heads = nwords < 0xffffffffULL && !t.no_heads;
   EmitSizes s;
   s.points = {(size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float), (size_t)(nextV + planeCorners) * 3 * sizeof(float)};
   s.cells = {(size_t)(nQ ? nQ : 1) * quad, (size_t)nextQ * quad};
+  s.normals = normals && nV ? Want{(size_t)nV * 3 * sizeof(float), (size_t)nextV * 3 * sizeof(float)} : Want{0, 0};   // (a whole volume: no plane behind them)
   s.headV = heads ? Want{(size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.headQ = heads ? Want{(size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.cmap = nV < 0xffffffffULL ? cmap_bytes(g, t) : 0;   // (more than 2^32 vertices: the cell kernel recomputes ids instead)
@@ -813,6 +841,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->counted = false;
   c->pointsEmitted = false;
   c->haveMesh = false;
+  c->haveNormals = false;
   c->hostMeshValid = false;
   c->stepMode = 0;
   c->voxelHaloEvent = nullptr;
@@ -839,6 +868,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "slab ranges are inconsistent with the buffer");
+    if (c->pointNormals && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to a whole volume: not offered on slabs");
     // the owned range needs 2 slices below (ids of corners created one slice down depend on the
     // slice below that) and 1 above; with the projection on, as far as a walk can reach (both unless the
     // volume ends there)
@@ -904,6 +935,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, mark(c, PASS_BEGIN));
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
   c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
+  c->countNormals = c->pointNormals;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -1140,9 +1172,10 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   const u32 nVW = dyn ? coverVW : c->tot.nVertexWords;
   // room behind this rank's points for the positions of a plane of the rank below's vertices (quirk Q1 across slabs)
   const size_t planeCorners = (c->slabMode || c->g.extAlias) ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) : 0;
-  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords);
+  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, c->countNormals);
   HIP_TRY(c, c->points.reserve_covering(sz.points.bytes, sz.points.cover));
   HIP_TRY(c, c->cells.reserve_covering(sz.cells.bytes, sz.cells.cover));
+  if (sz.normals.bytes) HIP_TRY(c, c->normals.reserve_covering(sz.normals.bytes, sz.normals.cover));
   Workspace &w = c->w;
   w.points = (float *)c->points.p;
   w.cells = (u64 *)c->cells.p;
@@ -1231,6 +1264,9 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
       c->held.n[0] = c->g.nx; c->held.n[1] = c->g.ny; c->held.n[2] = c->g.nzb;
     }
   }
+  // cuberille_set_point_normals: the points are final -- behind the walk, or behind the vertex scatter with the projection off --
+  // and one more pass reads each of them once (with stage timing on, part of ms_project)
+  if (sz.normals.bytes) HIP_TRY(c, launch_point_normals(c->pixel_type, w, c->g, c->geo, (float *)c->normals.p, nV, dyn ? 1 : 0, s));
   if (ahead) c->pointsStartedEarly = true;   // the caller turns to the other ranks now: the cells come as an interval of their own
   HIP_TRY(c, mark(c, PROJECT_END));
   c->pointsEmitted = true;
@@ -1314,6 +1350,7 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->histShortWalks = c->prm.project && c->tot.iters > 0 && c->tot.iters < 4 * c->tot.totV;
   c->stepMode = 0;
   c->haveMesh = true;
+  c->haveNormals = c->countNormals;
   c->counted = false;                        // the workspace now belongs to this mesh
   if (res) *res = r;
   return CUBERILLE_OK;
@@ -1506,7 +1543,7 @@ extern "C" {
 int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                          const cuberille_slab *slab, const void **dev_row, size_t *row_bytes) {
   View view;
-  int rc = validate(c, img, dev_voxels, prm);
+  int rc = validate(c, img, dev_voxels, prm, ROUTE_STEP);
   if (!rc) rc = view_of(c, img, prm, ROUTE_STEP, &view);
   return rc ? rc : step_begin_impl(c, img, dev_voxels, prm, slab, view, dev_row, row_bytes);
 }
@@ -1514,7 +1551,7 @@ int cuberille_step_begin(cuberille_ctx *c, const cuberille_image_desc *img, cons
 int cuberille_step_classify(cuberille_ctx *c, const cuberille_image_desc *img, const void *dev_voxels, const cuberille_params *prm,
                             const cuberille_slab *slab, uint64_t **dev_bits, size_t *words_per_slice) {
   View view;
-  int rc = validate(c, img, dev_voxels, prm);
+  int rc = validate(c, img, dev_voxels, prm, ROUTE_STEP);
   if (!rc) rc = view_of(c, img, prm, ROUTE_STEP, &view);
   if (rc) return rc;
   if (!dev_bits || !words_per_slice) return fail(c, CUBERILLE_ERR_ARGUMENT, "null bit-plane pointer");
@@ -1928,6 +1965,7 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     }
     c->haveHistory = false;                  // (sizes of a toy volume: the first real extraction reads its own counts)
     c->haveMesh = false;
+    c->haveNormals = false;
     c->counted = false;
     c->warm = true;
   }
@@ -2137,6 +2175,52 @@ int cuberille_mesh_host(cuberille_ctx *c, float **points, uint64_t **cells) {
   return CUBERILLE_OK;
 }
 
+int cuberille_set_point_normals(cuberille_ctx *c, int on) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  c->pointNormals = on != 0;
+  if (!on && c->normals.p) {
+    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its normals go)
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
+    c->normals.release();
+    c->haveNormals = false;
+    c->countNormals = false;
+  }
+  return CUBERILLE_OK;
+}
+
+static int normals_preconditions(cuberille_ctx *c) {
+  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
+  if (!c->haveNormals)
+    return fail(c, CUBERILLE_ERR_STATE, "no point normals: the last extraction ran with the setting off (cuberille_set_point_normals)");
+  return CUBERILLE_OK;
+}
+
+int cuberille_normals_device(cuberille_ctx *c, const float **d_normals) {
+  if (!c || !d_normals) return CUBERILLE_ERR_ARGUMENT;
+  *d_normals = nullptr;
+  if (const int rc = normals_preconditions(c)) return rc;
+  *d_normals = (const float *)c->normals.p;        // (a whole volume: no ghost vertices ahead of the owned ones; null with no point)
+  return CUBERILLE_OK;
+}
+
+int cuberille_normals_download(cuberille_ctx *c, float *normals) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (const int rc = normals_preconditions(c)) return rc;
+  if (!c->res.n_points) return CUBERILLE_OK;
+  if (!normals) return fail(c, CUBERILLE_ERR_ARGUMENT, "null output pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  return download_pipelined(c, normals, c->normals.p, (size_t)c->res.n_points * 3 * sizeof(float));
+}
+
+int cuberille_debug_device_bytes(cuberille_ctx *c, size_t *bytes) {
+  if (!c || !bytes) return CUBERILLE_ERR_ARGUMENT;
+  *bytes = 0;
+  for (const DevBuf *b : device_buffers(c)) *bytes += b->cap;
+  return CUBERILLE_OK;
+}
+
 int cuberille_hold_gradient(cuberille_ctx *c, int hold) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
@@ -2262,7 +2346,14 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
   uint64_t *cells = nullptr;
   const int rc = cuberille_mesh_host(c, &pts, &cells);
   if (rc != CUBERILLE_OK) return rc;
-  const int wr = cuberille_write_vtk_buffers(path, pts, r.n_points, cells, r.n_cells, r.verts_per_cell, n_threads);
+  int wr = cuberille_write_vtk_buffers(path, pts, r.n_points, cells, r.n_cells, r.verts_per_cell, n_threads);
+  if (wr == CUBERILLE_OK && c->haveNormals) {
+    // a context that holds normals: POINT_DATA n / NORMALS normals float behind the polygons (setting off: the file as it always was)
+    std::vector<float> nrm((size_t)r.n_points * 3);
+    const int dl = cuberille_normals_download(c, nrm.data());
+    if (dl != CUBERILLE_OK) return dl;
+    wr = cuberille::append_vtk_normals(path, nrm.data(), r.n_points, n_threads);
+  }
   if (wr != CUBERILLE_OK) return fail(c, wr, std::string("cannot write ") + path);
   return CUBERILLE_OK;
 }
@@ -2498,6 +2589,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
     if (c->holdGradient)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " holds a gradient (cuberille_hold_gradient): "
                                               "it belongs to a whole volume, not offered in a group");
+    if (c->pointNormals)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has point normals set (cuberille_set_point_normals): "
+                                              "they belong to one context's whole volume, not offered in a group");
   }
   {
     const int rc = validate(g->ctx[0], img, host_voxels, prm);

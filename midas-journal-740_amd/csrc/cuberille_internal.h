@@ -253,6 +253,11 @@ hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid
 hipError_t launch_gradient_image(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *out, hipStream_t s);
 hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo,
                           const Params &p, u64 nPoints, u64 nGhost, const Tuning &t, int mode, int dyn, hipStream_t s);
+// cuberille_set_point_normals: the normalised interpolated gradient (txx:451-452) at the final position of vertices
+// [0, nPoints) of w.points, 3 floats each in id order, into `normals` -- a buffer of its own, handed over beside the
+// Workspace so that no argument block of another kernel moves
+hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *normals, u64 nPoints,
+                                int dyn, hipStream_t s);
 
 }  // namespace cuberille
 #endif

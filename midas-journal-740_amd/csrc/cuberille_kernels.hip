@@ -3911,6 +3911,72 @@ __global__ __launch_bounds__(256) void k_project_bspline(const T *__restrict__ v
 }
 
 // ---------------------------------------------------------------------------------------------
+// K4e: point normals (cuberille_set_point_normals).  The vector the walk evaluates in every pass and throws away
+// (normal = m_GradientInterpolator->Evaluate(vertex); normal.Normalize(), txx:451-452), once more at every FINAL vertex: the
+// three floats as they stand in the points buffer -- behind the walk, or at the lattice start with the projection off -- go
+// through I4 (make_cell), I5 (the eight sites clamped), I6 (the float central differences with the direction transform), I7
+// (their linear interpolation: the sum in double in counter order, zero weights skipped, stopped once the weights sum to
+// exactly 1, each component narrowed to float) and I8 (the double sqrt of the sum of squares, float(double(c) / norm) per
+// component).  Quirk Q4: no zero guard, a zero gradient gives NaN and stays NaN.  It points the way the reference's
+// `normal` points: towards increasing pixel values.
+// This is the non-gimg, non-held path of variant_normal with a view's Sampler: everything to the letter (LITERAL gather,
+// the literal loop, IEEE sqrt and divide), no shortcut whose zero sign would need an argument.  make_cell's unit form is the
+// one make_cell itself shows equal to the full product.
+// One lane per vertex in id order -- ids follow raster order, so neighbouring lanes share cells and cache lines --, no LDS,
+// no atomics, nothing written but the 12 bytes.  The image is the view's frame, as in k_project: VIEW and the four trailing
+// arguments are that kernel's.  dyn (the blind launch of cuberille_step_begin, sized from the previous extraction): the
+// vertex count is read where the walk's blind form reads it, and the lanes stride over it.
+// ---------------------------------------------------------------------------------------------
+template <class T, int VIEW>
+__global__ __launch_bounds__(256) void k_point_normals(const T *__restrict__ vox, Grid g, Geo geo, int dirIdentity,
+                                                       const float *__restrict__ points, float *__restrict__ normals, u64 nPoints,
+                                                       const Totals *__restrict__ tot, int dyn,
+                                                       typename WalkArg<T, VIEW, double>::type padD, typename WalkArg<T, VIEW, long long>::type padI,
+                                                       typename WalkArg<T, VIEW, long long>::type rowPitch,
+                                                       typename WalkArg<T, VIEW, long long>::type slicePitch) {
+  if (dyn) {
+    if (!tot->go) return;
+    nPoints = tot->totV;
+  }
+  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
+  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
+  if constexpr (VIEW == VIEW_BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
+  const int n[3] = {g.nx, g.ny, (int)g.gnz};
+  bool unitP2I = true;
+#pragma unroll
+  for (int i = 0; i < 9; i++) unitP2I = unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x; idx < nPoints; idx += stride) {
+    const double p[3] = {(double)points[3 * idx], (double)points[3 * idx + 1], (double)points[3 * idx + 2]};
+    Cell8 c;
+    make_cell(geo, unitP2I, n, p, c);                                               // I4, I5
+    float G[8][3];
+    typename SiteValue<T>::type Vd[8];
+    gather_cell<T, /*LITERAL*/ true, VIEW>(s, geo, dirIdentity != 0, c, G, Vd);       // I6
+    double acc[3] = {0.0, 0.0, 0.0}, total = 0.0;                                   // I7
+#pragma unroll
+    for (unsigned counter = 0; counter < 8; counter++) {
+      double overlap = 1.0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
+      if (overlap != 0.0 && total != 1.0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) acc[k] += overlap * (double)G[counter][k];
+        total += overlap;
+      }
+    }
+    float normal[3];
+    double sq = 0.0;                                                                // I8
+#pragma unroll
+    for (int k = 0; k < 3; k++) { normal[k] = (float)acc[k]; const double e = (double)normal[k]; sq += e * e; }
+    const double norm = sqrt(sq);
+#pragma unroll
+    for (int k = 0; k < 3; k++) normals[3 * idx + k] = (float)((double)normal[k] / norm);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <class F>
@@ -4604,6 +4670,37 @@ hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid
     else
       hipLaunchKernelGGL((k_project_bspline<T, float>), dim3(grid_for(nPoints, 256, 0)), dim3(256), 0, s, (const T *)w.vox, g, geo, p,
                          dirIdentity, w.points, nPoints, w.totals, (const float *)coef);
+    return hipGetLastError();
+  });
+}
+
+// The point normals of vertices [0, nPoints) of w.points into `normals` (K4e), behind whatever left the points final on `s`.
+// A whole volume, every slice in the buffer (the host layer offers nothing else with the setting).  dyn: nPoints is what the
+// launch is sized for, the kernel reads the real count from the device totals.
+hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *normals, u64 nPoints,
+                                int dyn, hipStream_t s) {
+  if (nPoints == 0) return hipSuccess;
+  int dirIdentity = 1;
+  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+    typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+    const View &v = w.view;
+    const unsigned blocks = grid_for(nPoints, 256, 0x7fffffffu);
+    auto launch = [&](auto viewTag) {
+      constexpr int VIEW = decltype(viewTag)::value;
+      auto go = [&](auto a0, auto a1, auto a2, auto a3) {
+        hipLaunchKernelGGL((k_point_normals<T, VIEW>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, dirIdentity,
+                           (const float *)w.points, normals, nPoints, (const Totals *)w.totals, dyn, a0, a1, a2, a3);
+      };
+      if constexpr (VIEW == VIEW_BAND)
+        go(value_as<T>(v.bandV[0], v.bandVi[0]), value_as<T>(v.bandV[1], v.bandVi[1]), value_as<T>(v.bandV[2], v.bandVi[2]),
+           value_as<T>(v.bandV[3], v.bandVi[3]));
+      else go(v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
+    };
+    if (v.kind == VIEW_BAND) launch(std::integral_constant<int, VIEW_BAND>());
+    else if (v.kind == VIEW_BORDER) launch(std::integral_constant<int, VIEW_BORDER>());
+    else if (v.kind == VIEW_REGION) launch(std::integral_constant<int, VIEW_REGION>());
+    else launch(std::integral_constant<int, VIEW_WHOLE>());
     return hipGetLastError();
   });
 }

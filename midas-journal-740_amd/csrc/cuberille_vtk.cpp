@@ -101,3 +101,20 @@ extern "C" int cuberille_write_vtk_buffers(const char *path, const float *points
   ok = (std::fclose(f) == 0) && ok;
   return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
 }
+
+// cuberille_mesh_write_vtk on a context that holds point normals (cuberille_set_point_normals): the legacy format's point
+// attribute block behind the polygons of a file cuberille_write_vtk_buffers has just written -- "POINT_DATA n",
+// "NORMALS normals float", then "x y z" per point in the points' own number format.
+namespace cuberille {
+int append_vtk_normals(const char *path, const float *normals, uint64_t n_points, int n_threads) {
+  if (!path || (n_points && !normals)) return CUBERILLE_ERR_ARGUMENT;
+  if (n_threads <= 0) n_threads = (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+  std::FILE *f = std::fopen(path, "ab");
+  if (!f) return CUBERILLE_ERR_ARGUMENT;
+  bool ok = std::fprintf(f, "POINT_DATA %llu\nNORMALS normals float\n", (unsigned long long)n_points) > 0;
+  ok = ok && write_section(f, n_points, n_threads,
+                           [&](size_t a, size_t b, std::string &s) { format_points(normals, a, b, s); });
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
+}
+}  // namespace cuberille

@@ -471,6 +471,36 @@ class Extractor:
         _abi.check(self._ctx, self._lib.cuberille_set_region(self._ctx, None, None))
         self._view["region"] = None
 
+    def set_point_normals(self, on=True):
+        """Point normals (cuberille_set_point_normals): every later extraction also leaves, for every point, the normalised
+        interpolated gradient of the image at the point's final position -- the vector the walk evaluates in every pass
+        (txx:451-452), once more where the vertex ended up (or at the lattice start with the projection off).  It points
+        towards increasing pixel values: into an object brighter than its surroundings.  A zero gradient gives NaN (quirk
+        Q4).  Points, cells and counters are unchanged.  Slabs, steps, groups, a held gradient and the recursive-Gaussian
+        gradient are refused at the extraction.  Off (the default) frees the buffer."""
+        _abi.check(self._ctx, self._lib.cuberille_set_point_normals(self._ctx, 1 if on else 0))
+
+    def download_normals(self):
+        """The normals of the last extraction as a float32 array (n, 3), in point-id order (cuberille_normals_download);
+        CuberilleError ERR_STATE when that extraction ran with the setting off."""
+        n = int(self.result.n_points) if self.result is not None else 0
+        out = np.empty((n, 3), dtype=np.float32)
+        _abi.check(self._ctx, self._lib.cuberille_normals_download(self._ctx, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def normals_device(self):
+        """Device pointer of the normals of the last extraction, 3 floats per point in the library's buffer
+        (cuberille_normals_device; it may be None for an empty mesh)."""
+        p = C.c_void_p()
+        _abi.check(self._ctx, self._lib.cuberille_normals_device(self._ctx, C.byref(p)))
+        return p.value
+
+    def device_bytes(self):
+        """Bytes of device memory the context's workspace holds at this moment (cuberille_debug_device_bytes)."""
+        n = C.c_size_t()
+        _abi.check(self._ctx, self._lib.cuberille_debug_device_bytes(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def set_interpolator(self, kind, spline_order=3, coordinate_bits=32, coefficient_bits=32):
         """The value interpolator of the walk for the later extractions (cuberille_set_interpolator): _abi.INTERP_LINEAR
         (the default) or _abi.INTERP_BSPLINE -- itk::BSplineInterpolateImageFunction of spline_order 3, <float, float>
@@ -660,6 +690,11 @@ class ExtractorGroup:
         size = (C.c_int64 * 3)(*[int(v) for v in size_xyz])
         self._on_every_member(self._lib.cuberille_set_region, start, size)
 
+    def set_point_normals(self, on=True):
+        """Point normals (Extractor.set_point_normals) on every member: the group's extraction then raises the library's
+        refusal -- they belong to one context's whole volume."""
+        self._on_every_member(self._lib.cuberille_set_point_normals, 1 if on else 0)
+
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
         (slab -1: every slab's; n < 0: off)."""
@@ -722,10 +757,13 @@ class CuberilleImageToMeshFilter:
     _band_on = False
 
     # The view settings that several devices do not offer: (attribute, its "off", the setting by name, why)
+    _normals = False       # SetGeneratePointNormals: off (class level for the same reason)
+
     _NOT_IN_A_GROUP = (
         ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
         ("_region", None, "a region (SetExtractionRegion / cuberille_set_region)", "a box belongs to one context's whole volume"),
-        ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"))
+        ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"),
+        ("_normals", False, "point normals (SetGeneratePointNormals / cuberille_set_point_normals)", "they belong to one context's whole volume"))
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -754,6 +792,8 @@ class CuberilleImageToMeshFilter:
         self._region = None                       # SetExtractionRegion: (index_xyz, size_xyz) in ITK index space, or None
         self._band = (0, 0)                       # SetInsideBand: lower, upper
         self._band_values = (1, 0)                # SetBandValues: NumericTraits<InputPixelType>::One / Zero
+        self._normals = False                     # SetGeneratePointNormals: off
+        self._point_normals = None                # GetPointNormals(): (n, 3) float32 of the last Update(), or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -962,6 +1002,25 @@ class CuberilleImageToMeshFilter:
     def GetInsideBand(self):
         return self._band_on
 
+    def SetGeneratePointNormals(self, b):
+        """Not in the reference -- the vector its walk evaluates in every pass and throws away (txx:451-452): with the switch
+        on, Update() also fills GetPointNormals() with the normalised interpolated gradient at every point's final position
+        (cuberille_set_point_normals).  It points towards increasing pixel values.  Default off."""
+        self._normals = bool(b)
+
+    def GetGeneratePointNormals(self):
+        return self._normals
+
+    def GeneratePointNormalsOn(self):
+        self.SetGeneratePointNormals(True)
+
+    def GeneratePointNormalsOff(self):
+        self.SetGeneratePointNormals(False)
+
+    def GetPointNormals(self):
+        """(n, 3) float32 in point-id order, filled by the last Update() with the switch on; None with it off."""
+        return self._point_normals
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -989,6 +1048,7 @@ class CuberilleImageToMeshFilter:
                 not (self._project and self._gradient == GRADIENT_RECURSIVE_GAUSSIAN):
             if self._group is None:
                 self._group = ExtractorGroup(self._devices)
+            self._point_normals = None
             self.last_result = self._group.extract_host(vol, prm)
             self._output = self._group.download()
             self.last_number_of_slabs = len(self._group.plan(self._group_desc(vol), prm))
@@ -1007,8 +1067,12 @@ class CuberilleImageToMeshFilter:
             self._extractor.set_band(*(self._band + self._band_values))
         else:
             self._extractor.clear_band()
+        self._extractor.set_point_normals(self._normals)
+        self._point_normals = None
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
+        if self._normals:
+            self._point_normals = self._extractor.download_normals()
         self.last_number_of_slabs = 1
 
     @staticmethod

@@ -271,6 +271,22 @@ public:
   InputPixelType GetBandInsideValue() const { return m_BandInside; }
   InputPixelType GetBandOutsideValue() const { return m_BandOutside; }
 
+  /** Not in the reference -- the vector its walk evaluates in every pass and throws away (normal =
+   *  m_GradientInterpolator->Evaluate(vertex); normal.Normalize(), txx:451-452).  GeneratePointNormalsOn(): Update() also
+   *  fills GetPointNormals() with that vector at every point's FINAL position -- 3 floats per point id, contiguous -- computed on
+   *  the device by a pass of its own behind the walk (cuberille_set_point_normals): the central-difference gradient of the
+   *  input, interpolated linearly at the point and normalised, to the letter of the walk's contract.  It points towards
+   *  increasing pixel values -- into an object brighter than its surroundings -- and a zero gradient gives NaN.  It stays an
+   *  accessor, not mesh point data: the mesh's pixel type is the caller's scalar.  The mesh itself is unchanged.  Offered where
+   *  the device walks (or nothing is projected), PadBorderOn(), SetExtractionRegion and InsideBandOn() included; with an
+   *  interpolator that takes the host walk the library never sees the final vertices, and with SetDevices of more than one
+   *  device, ReproduceStaleGradient or USE_GRADIENT_RECURSIVE_GAUSSIAN the library refuses: Update() throws an
+   *  itk::ExceptionObject that says so.  Default off: the array is empty. */
+  itkGetMacro(GeneratePointNormals, bool);
+  itkSetMacro(GeneratePointNormals, bool);
+  itkBooleanMacro(GeneratePointNormals);
+  const std::vector<float> &GetPointNormals() const { return m_PointNormals; }
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -313,6 +329,8 @@ private:
   InputPixelType m_BorderPadValue;
   RegionType m_ExtractionRegion;
   bool m_HasExtractionRegion;
+  bool m_GeneratePointNormals;
+  std::vector<float> m_PointNormals;          // GetPointNormals(): filled by Update() with the switch on, else empty
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them

@@ -500,6 +500,7 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_PadBorder = false;
   m_HasExtractionRegion = false;
   m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
+  m_GeneratePointNormals = false;
   m_InsideBand = false;
   m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
   m_BandInside = NumericTraits<InputPixelType>::One;
@@ -713,6 +714,11 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "an implied border (PadBorderOn / cuberille_set_border) is not offered with an interpolator that takes "
                          "the host walk: the caller's interpolator object is bound to the unpadded image");
 
+  m_PointNormals.clear();
+  if (m_GeneratePointNormals && hostWalk)
+    itkExceptionMacro(<< "point normals (GeneratePointNormalsOn / cuberille_set_point_normals) are not offered with an interpolator "
+                         "that takes the host walk: the library never sees the final vertices");
+
   // InsideBandOn(): the four values against the pixel type by the library's validator (lower > upper: the threshold filter
   // throws there too), and on the device's walk
   if (m_InsideBand)
@@ -758,8 +764,12 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     this->AcquireGroup(true);
     // (an implied border or a band on the members: the group's extraction refuses it, and that message is what the caller sees)
     for (int i = 0; i < static_cast<int>(m_Devices.size()); i++)
+      {
       if (const char *setter = this->ApplyView(cuberille_group_context(m_Group, i), desc, false, true))
         itkExceptionMacro(<< setter << ": " << cuberille_last_error(cuberille_group_context(m_Group, i)));
+      // (point normals on the members: the group's extraction refuses them likewise)
+      (void)cuberille_set_point_normals(cuberille_group_context(m_Group, i), m_GeneratePointNormals ? 1 : 0);
+      }
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_group_extract_host: " << cuberille_group_last_error(m_Group));
@@ -778,6 +788,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< "cuberille_set_interpolator: " << cuberille_last_error(m_Context));
     if (const char *setter = this->ApplyView(m_Context, desc, true, true))
       itkExceptionMacro(<< setter << ": " << cuberille_last_error(m_Context));
+    if (cuberille_set_point_normals(m_Context, m_GeneratePointNormals ? 1 : 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_point_normals: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
@@ -799,6 +811,12 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     }
   else if (cuberille_mesh_host(m_Context, &points, &cells) != CUBERILLE_OK)
     itkExceptionMacro(<< "cuberille_mesh_host: " << cuberille_last_error(m_Context));
+  if (m_GeneratePointNormals)                 // (the single context: a group has refused above)
+    {
+    m_PointNormals.resize(static_cast<size_t>(res.n_points) * 3);
+    if (cuberille_normals_download(m_Context, m_PointNormals.empty() ? 0 : &m_PointNormals[0]) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_normals_download: " << cuberille_last_error(m_Context));
+    }
   m_LastDownloadSeconds = cuberille_detail::WallSeconds() - downloadStart;
   struct FreeOnExit { void *p; ~FreeOnExit() { std::free(p); } } ownCells = {0};   // the host walk's triangles, when it makes them
 

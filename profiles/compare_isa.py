@@ -6,7 +6,7 @@ literals aside, which move with a kernel's place in the code object).  It compar
 
 A kernel is matched by its canonical name: the kernel and its template arguments, argument lists aside.  The one rename rule
 kept here is that of the source views: the walk's three trailing bools of the parent (PAD, REGION, BAND, at most one true)
-are its one VIEW value here (0 whole, 1 border, 2 region, 3 band).  Results: profiles/view_isa.txt; the comparisons of the
+are its one VIEW value here (0 whole, 1 border, 2 region, 3 band).  Results: profiles/view_isa.txt, profiles/point_normals_isa.txt; the comparisons of the
 changes that added the border, the region and the band (region_walk_isa.txt, band_isa.txt) were made by this script's
 predecessors, which git history keeps (profiles/README.md).
 """
@@ -37,6 +37,8 @@ def kernels(lib):
         if m:
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line.strip():
+            if line.strip() == "...":      # (zero bytes the disassembler elides: the padding behind a kernel's s_endpgm, which moves
+                continue                   #  with what the linker places next)
             t = re.sub(r"<[^>]*>", "", line.split("//")[0]).strip()
             t = re.sub(r"^(s_c?branch\w*|s_getpc\w*)\s.*", r"\1", t)
             # (the literal of a pc-relative address: s_getpc_b64 is followed by s_add_u32 sN, sN, <offset> / s_addc_u32)
