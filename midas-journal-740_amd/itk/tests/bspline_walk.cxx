@@ -9,7 +9,7 @@
 //   bspline_walk walk <in.raw> <pixel> <nx> <ny> <nz> <bits> <geometry> <iso> <thr> <step> <relax> <maxSteps> <start.raw> <n> <out.raw>
 //       the drop-in's host walk alone (HostGradient + HostWalk, what `filter ... host` runs after the device's sweep) through
 //       BSplineInterpolateImageFunction<Image, T, T> of order 3: n start points (float32 xyz) -> walked points; needs no GPU
-//       (<pixel>: u8 i16 f32)
+//       (<pixel>: all ten; the iso value travels as a double, so an 8-byte one must be one a double holds)
 //   bspline_walk filter <volume> host|device <threads> <bits> <iso> <tri> <project> <thr> <step> <relax> <maxSteps>
 //                <outPoints.raw> <outCells.raw> [raw <pixel> <nx> <ny> <nz>] [geometry <geometry>] [order <k>] [repeat <r>]
 //       the whole filter with BSplineInterpolateImageFunction<Image, T, T> (T = float for 32, double for 64 bits): `host`
@@ -298,6 +298,13 @@ int main(int argc, char **argv)
       if (px == "u8") return wide ? walk<unsigned char, double>(argv) : walk<unsigned char, float>(argv);
       if (px == "i16") return wide ? walk<short, double>(argv) : walk<short, float>(argv);
       if (px == "f32") return wide ? walk<float, double>(argv) : walk<float, float>(argv);
+      if (px == "i8") return wide ? walk<signed char, double>(argv) : walk<signed char, float>(argv);
+      if (px == "u16") return wide ? walk<unsigned short, double>(argv) : walk<unsigned short, float>(argv);
+      if (px == "u32") return wide ? walk<unsigned int, double>(argv) : walk<unsigned int, float>(argv);
+      if (px == "i32") return wide ? walk<int, double>(argv) : walk<int, float>(argv);
+      if (px == "f64") return wide ? walk<double, double>(argv) : walk<double, float>(argv);
+      if (px == "i64") return wide ? walk<long long, double>(argv) : walk<long long, float>(argv);
+      if (px == "u64") return wide ? walk<unsigned long long, double>(argv) : walk<unsigned long long, float>(argv);
       std::fprintf(stderr, "walk: unsupported pixel type %s\n", px.c_str());
       return 1;
       }

@@ -129,13 +129,18 @@ PIXEL_NAMES = {np.dtype(np.uint8): "u8", np.dtype(np.int8): "i8", np.dtype(np.ui
                np.dtype(np.float64): "f64", np.dtype(np.int64): "i64", np.dtype(np.uint64): "u64"}
 
 
+_MADE = set()
+
+
 def walk_exe():
-    """itk/build/bspline_walk, made by build(); made here when it is missing.  A binary that cannot be had is an error
+    """itk/build/bspline_walk, made by build(); make decides here, once per process, whether it is missing or older than its
+    source (a build directory from before the driver learnt a mode or a pixel type).  A binary that cannot be had is an error
     (not a skip): the tests that use it exist to run it."""
     import os
     import subprocess
     exe = os.path.join(ROOT, "midas-journal-740_amd", "itk", "build", "bspline_walk")
-    if not os.path.exists(exe):
+    if exe not in _MADE:
+        _MADE.add(exe)
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "midas-journal-740_amd", "itk"), "build/bspline_walk"])
     assert os.path.exists(exe), exe
     return exe

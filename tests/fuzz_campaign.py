@@ -4,17 +4,46 @@ a GPU box, its summary committed under profiles/:
 
     python tests/fuzz_campaign.py --seconds 600 --seed 1 > gpurun_out/fuzz_seed1.log
 
-Every case draws a volume (shape with ragged / whole-word / one-voxel-thick rows, one of the ten pixel types, a noise, blob,
+Every case is a pure function of (seed, case): draw_case() draws a RECIPE from np.random.default_rng([seed, case]) -- no GPU,
+no oracle; the recipe survives JSON and holds all that is needed to build the voxels again --, expected() asks the references
+for the mesh (and the normals), run_case() asks the library.  A recipe a run printed replays alone:
+
+    python tests/fuzz_campaign.py --seed 1 --case 4711          (or --replay '<the recipe>' / --replay recipe.json)
+
+(with the options the run had: --big, --max-voxels, --kind ... enter the draw; a FAILED line holds the whole recipe and needs
+none.  The replay runs on a fresh context: a difference that needs what earlier cases left there shows in the run alone.)
+
+A recipe holds a volume (shape with ragged / whole-word / one-voxel-thick rows, one of the ten pixel types, a noise, blob,
 plane or shell field, blanked slices for quirk Q1, non-finite voxels now and then), a geometry (spacing, origin, a rotation or a
-shear as direction matrix), the filter's eight parameters, a projection branch, and a route through the C ABI -- host upload,
-resident volume, streamed upload, Z-slabs stitched by hand, count + emit, a held gradient (quirk Q3), a development switch
-that forces a fallback kernel -- and compares ids, cell order and the float bits of every coordinate with the oracle's mesh
-of the same volume.  TEST INFRASTRUCTURE: the oracle is the checker here, never the thing measured or shipped.
+flip as direction matrix, a start index), the filter's eight parameters, a projection branch and
+
+  kind    whole   the volume as it is, through one of the eight routes of the C ABI -- host upload, resident volume, streamed
+                  upload, Z-slabs stitched by hand, count + emit, a held gradient (quirk Q3), a development switch that forces a
+                  fallback kernel;                                       reference: the oracle on the volume
+          border  cuberille_set_border(1, c): host, device, stream, count + emit;
+                                                                         reference: the oracle on np.pad(vox, 1, c), start - 1
+          region  cuberille_set_region on a buffer larger than the box: host (plain, or the chunk pipeline forced), device,
+                  count + emit;                                          reference: the oracle on the contiguous crop, start moved
+          band    cuberille_set_band: host, device, count + emit;        reference: the oracle on test_band.band_image
+          bspline cuberille_set_interpolator, 32 / 64 bits: host, device, stream;
+                                         reference: the oracle's lattice points walked by the drop-in's host walk (a subprocess)
+  normals cuberille_set_point_normals on;   reference: normals_ref.normals on the frame image at the REFERENCE's points
+  repeat  the case three times on the context, the third mesh compared (the blind launch sized by its own history)
+  refusal one call the header lists as refused, made first: CUBERILLE_ERR_ARGUMENT with that refusal's words, and the case
+          itself still equal
+
+and every case runs on the context the cases before it used, whatever they left there: the settings of a case are taken back
+behind it, the workspace and its history stay, and so does the normals row of a normals case unless its recipe drops it -- the
+next normals case then finds a row sized by another mesh (counted in the summary).  Comparisons are exact: ids, cell order,
+the float bits of every coordinate (conftest.assert_same_mesh), the bits of every normal (normals_ref.same_normals), the walk's
+counters.  TEST INFRASTRUCTURE: the oracle is the checker here, never the thing measured or shipped.
 Prints one progress line every ~20 s; exit code 1 with the failing case's recipe if a mesh ever differs."""
 import argparse
 import json
 import os
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -28,9 +57,37 @@ from conftest import assert_same_mesh  # noqa: E402
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.float32, np.float64, np.int64, np.uint64]
 XS = [1, 2, 5, 31, 63, 64, 65, 100, 127, 128, 129, 192, 200, 256, 257, 320]
 
+KINDS = ["whole", "border", "region", "band", "bspline"]
+ROUTES = {"whole": ["host", "device", "stream", "slabs", "thin_slabs", "count_emit", "held", "switch"],
+          "border": ["host", "device", "stream", "count_emit"],
+          "region": ["host", "host_chunked", "device", "count_emit"],
+          "band": ["host", "device", "count_emit"],
+          "bspline": ["host", "device", "stream"]}
+# the development switches of the "switch" route; a view case may carry one too (the views share the whole volume's launch path:
+# count, points, cells and the walk all read Tuning, whatever the sampler's form)
+SWITCHES = [("no_cmap", 1), ("no_heads", 1), ("no_vqueue", 1), ("count_variant", 1), ("count_variant", 2), ("count_variant", 3),
+            ("count_variant", 0), ("points_variant", 2), ("points_variant", 1), ("points_variant", 0), ("classify_variant", 1),
+            ("proj_literal", 1), ("cmap_linear", 1), ("no_stream_classify", 1), ("proj_short", 1), ("proj_short", 0),
+            ("count_no_fold", 1)]
+# the routes on which cuberille_set_point_normals is offered (not on slabs, not with a held gradient)
+NORMALS_ROUTES = ("host", "host_chunked", "device", "stream", "count_emit", "switch")
+# normals_ref.gradient_image calls the oracle once per voxel from Python (about 2 us each): a frame of this many voxels takes
+# well under a second; a larger case is drawn without normals
+NORMALS_MAX_VOXELS = 40000
+# one subprocess per B-spline case, and ITK's class evaluates 64 taps per step on one thread: small volumes only
+BSPLINE_MAX_VOXELS = 12000
+COUNTERS = ("proj_iterations", "proj_stop_threshold", "proj_stop_steps")
+REFUSALS = {"whole": ["normals_rg", "bspline_variant", "bspline_held"],
+            "bspline": ["normals_rg", "bspline_variant", "bspline_held"],
+            "border": ["pair", "variant", "held", "rg"],
+            "region": ["pair", "stream", "variant", "held", "rg"],
+            "band": ["pair", "stream", "variant", "held", "rg"]}
+DEFAULT_OPTIONS = dict(max_voxels=900000, big=False, recursive_gaussian=False, kind=None, dtype=None, route=None, max_rows=None)
 
-def draw_field(rng, shape, dt):
-    """(voxels, iso): the inside set is what matters to the topology, the values to the walk."""
+
+def draw_field(rng, shape, dt, big=True):
+    """(voxels, iso): the inside set is what matters to the topology, the values to the walk.  big False: the 8-byte types
+    stay below 2^53 (the draw is made all the same, so the stream does not depend on it)."""
     nz, ny, nx = shape
     kind = rng.choice(["noise", "blobs", "plane", "shell", "smooth_noise"])
     z, y, x = np.meshgrid(np.arange(nz, dtype=np.float64), np.arange(ny, dtype=np.float64), np.arange(nx, dtype=np.float64), indexing="ij")
@@ -74,10 +131,10 @@ def draw_field(rng, shape, dt):
         g = np.clip(mid + f * (hi - lo) * 0.5 * rng.choice([1.0, 0.3]), lo, hi)
         vox = np.rint(g).astype(dt)
         iso = int(np.rint(mid)) + int(rng.integers(0, 2))
-        if dt.itemsize == 8 and rng.random() < 0.5:               # beyond 2^53: a double cannot hold these
-            big = (1 << 60) if info.min == 0 else -(1 << 60)
-            vox = vox + dt.type(big)
-            iso = int(iso) + big
+        if dt.itemsize == 8 and rng.random() < 0.5 and big:       # beyond 2^53: a double cannot hold these
+            off = (1 << 60) if info.min == 0 else -(1 << 60)
+            vox = vox + dt.type(off)
+            iso = int(iso) + off
     if rng.random() < 0.25 and nz > 2:
         for _ in range(int(rng.integers(1, 3))):
             vox[int(rng.integers(0, nz))] = vox.min()                 # an empty slice (or a full one when min is inside)
@@ -108,6 +165,641 @@ def draw_geometry(rng):
     return spacing, origin, np.ascontiguousarray(d, dtype=np.float64)
 
 
+def geometry_form(recipe):
+    """identity / axis-aligned / general, by the rule of the walk's three forms (cuberille_kernels.hip, launch_project): the unit
+    direction matrix and a caller's region that starts at index 0 with unit spacing is the identity form, with any other spacing
+    the axis-aligned one; everything else -- a rotation, a flip, a region that starts elsewhere -- takes the general form.  The
+    kernels of cuberille_set_region take the start index at run time in every form: there the matrices alone decide."""
+    d = np.asarray(recipe["direction"], dtype=np.float64)
+    moved = tuple(int(v) for v in recipe["index_start"]) != (0, 0, 0) and recipe["kind"] != "region"
+    if not np.array_equal(d, np.eye(3)) or moved:
+        return "general"
+    return "identity" if tuple(recipe["spacing"]) == (1.0, 1.0, 1.0) else "axis-aligned"
+
+
+# ---- the voxels of a recipe -----------------------------------------------------------------------------------------------
+def _field(spec):
+    vox, iso = draw_field(np.random.default_rng(spec["rng"]), tuple(spec["shape"]), np.dtype(spec["dtype"]), big=spec.get("big", True))
+    return vox, iso
+
+
+def voxels(recipe):
+    """The buffer the library is handed, built again from the recipe alone."""
+    return _field(recipe["field"])[0]
+
+
+def frame_start(recipe):
+    s = [int(v) for v in recipe["index_start"]]
+    if recipe["kind"] == "border":
+        return tuple(v - 1 for v in s)
+    if recipe["kind"] == "region":
+        return tuple(a + int(b) for a, b in zip(s, recipe["region"]["start"]))
+    return tuple(s)
+
+
+def frame(recipe, vox=None):
+    """(image, start index) the reference is handed: the volume, its padded copy, the crop, or B."""
+    vox = voxels(recipe) if vox is None else vox
+    kind = recipe["kind"]
+    if kind == "border":
+        c = recipe["border"]["value"]
+        c = float(c) if vox.dtype.kind == "f" else int(c)
+        return np.pad(vox, 1, constant_values=vox.dtype.type(c)), frame_start(recipe)
+    if kind == "region":
+        (x0, y0, z0), (nx, ny, nz) = recipe["region"]["start"], recipe["region"]["size"]
+        return np.ascontiguousarray(vox[z0:z0 + nz, y0:y0 + ny, x0:x0 + nx]), frame_start(recipe)
+    if kind == "band":
+        from test_band import band_image
+        b = recipe["band"]
+        return np.ascontiguousarray(band_image(vox, _num(b["lower"]), _num(b["upper"]), _num(b["inside"]), _num(b["outside"]))[0]), frame_start(recipe)
+    return vox, frame_start(recipe)
+
+
+def _num(v):
+    """A value of a recipe: JSON has no infinities, so the float bounds that are not finite travel as strings."""
+    return float(v) if isinstance(v, str) else v
+
+
+def _jnum(v):
+    if isinstance(v, (float, np.floating)) and not np.isfinite(v):
+        return repr(float(v))
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    return float(v)
+
+
+def inside_set(img, iso):
+    """pixel >= iso in the pixel type (a NaN pixel is outside)."""
+    dt = img.dtype
+    return img >= (dt.type(iso) if dt.kind == "f" else np.asarray(int(iso), dtype=dt))
+
+
+def has_q1_gap(img, iso):
+    """An empty slice between occupied ones in the frame (quirk Q1)."""
+    occ = np.flatnonzero(inside_set(img, iso).reshape(img.shape[0], -1).any(axis=1))
+    return len(occ) >= 2 and (occ[-1] - occ[0] + 1) > len(occ)
+
+
+# ---- 1. the recipe ---------------------------------------------------------------------------------------------------------
+def draw_case(seed, case, options=None):
+    """The recipe of case `case` of seed `seed`: a dict of plain numbers, lists and strings.  options: DEFAULT_OPTIONS' keys
+    -- max_voxels, big (up to 120 rows and slices), recursive_gaussian, and kind / dtype / route to fix what a stratified
+    slice fixes (they are recorded, so the recipe alone still says everything).  Needs no GPU and no oracle."""
+    opt = dict(DEFAULT_OPTIONS)
+    opt.update(options or {})
+    rng = np.random.default_rng([int(seed), int(case)])
+    kind = opt["kind"] or str(rng.choice(KINDS, p=[0.46, 0.15, 0.17, 0.15, 0.07]))
+    top = opt["max_rows"] or (120 if opt["big"] else 40)
+    nx = int(rng.choice(XS))
+    ny = int(rng.integers(1, top + 1))
+    nz = int(rng.integers(1, top + 1))
+    cap = min(opt["max_voxels"], BSPLINE_MAX_VOXELS) if kind == "bspline" else opt["max_voxels"]
+    if kind == "bspline":
+        nx = int(rng.choice(XS[:8]))
+    while nx * ny * nz > cap:
+        ny = max(1, ny // 2)
+        nz = max(1, nz // 2)
+        if ny == 1 and nz == 1 and nx * ny * nz > cap:
+            nx = max(1, nx // 2)
+    dt = np.dtype(opt["dtype"] if opt["dtype"] is not None else DTYPES[int(rng.integers(0, len(DTYPES)))])
+    spacing, origin, direction = draw_geometry(rng)
+    start = tuple(int(v) for v in rng.integers(-3000, 3000, size=3)) if rng.random() < 0.3 else (0, 0, 0)
+    project = bool(rng.random() < 0.75)
+    variant = int(rng.choice([0, 0, 0, 1, 2])) if project and kind == "whole" else 0
+    kw = dict(triangles=bool(rng.integers(0, 2)), project=project,
+              threshold=float(rng.choice([0.0, 0.01, 0.2, 5.0])) * (1.0 if dt.kind != "f" else 0.05),
+              step=float(rng.choice([0.1, 0.25, 0.6, 1.3])) * min(spacing),
+              relax=float(rng.choice([0.5, 0.9, 0.95, 1.0])), max_steps=int(rng.choice([0, 1, 4, 25, 50])), variant=variant)
+    route = opt["route"] or str(rng.choice(ROUTES[kind]))
+    recipe = dict(seed=int(seed), case=int(case), kind=kind, dtype=dt.name, route=route, kw=kw, spacing=list(spacing), origin=list(origin),
+                  direction=direction.tolist(), index_start=list(start))
+
+    # the buffer: the box of a region case lies inside a larger one
+    shape = [nz, ny, nx]
+    if kind == "region":
+        form = str(rng.choice(["full_xy", "thin", "residue", "words_in_ragged", "ragged_in_words", "whole_buffer", "any"]))
+        size = [nx, ny, nz]
+        if form == "thin":
+            size[int(rng.integers(0, 3))] = 1
+        if form == "words_in_ragged":
+            size[0] = int(rng.choice([64, 128, 192]))
+        lo = [int(rng.integers(0, 17)), int(rng.integers(0, 4)), int(rng.integers(0, 4))]       # x0: every byte residue mod 16
+        hi = [int(rng.integers(0, 9)), int(rng.integers(0, 4)), int(rng.integers(0, 4))]
+        if form == "full_xy":
+            lo[0] = lo[1] = hi[0] = hi[1] = 0
+            lo[2] += 1
+        elif form == "whole_buffer":
+            lo, hi = [0, 0, 0], [0, 0, 0]
+        elif form == "words_in_ragged":
+            hi[0] += (lo[0] + size[0] + hi[0]) % 64 == 0
+        elif form == "ragged_in_words":
+            hi[0] += -(lo[0] + size[0] + hi[0]) % 64
+        buf = [lo[k] + size[k] + hi[k] for k in range(3)]
+        while buf[0] * buf[1] * buf[2] > 2 * opt["max_voxels"] and (size[1] > 1 or size[2] > 1):
+            size[1], size[2] = max(1, size[1] // 2), max(1, size[2] // 2)
+            buf = [lo[k] + size[k] + hi[k] for k in range(3)]
+        recipe["region"] = dict(form=form, start=lo, size=size)
+        shape = [buf[2], buf[1], buf[0]]
+    recipe["field"] = dict(rng=[int(seed), int(case), 1], shape=shape, dtype=dt.name, big=kind != "bspline")
+    vox, iso = _field(recipe["field"])
+    recipe["iso"] = iso if dt.kind == "f" else int(iso)
+
+    if kind == "border":
+        recipe["border"] = dict(value=_jnum(_draw_border_value(rng, dt, iso)))
+    elif kind == "band":
+        recipe["band"] = _draw_band(rng, dt, vox)
+        recipe["iso"] = recipe["band"].pop("iso")
+    elif kind == "bspline":
+        recipe["bspline"] = dict(bits=int(rng.choice([32, 64])))
+
+    if kind == "whole":
+        _draw_whole_route(rng, recipe, vox, opt)
+    elif kind == "region" and route == "host_chunked":
+        recipe["chunk_kib"] = int(rng.choice([1, 4, 16, 64]))
+    if kind in ("border", "region", "band") and rng.random() < 0.2:
+        name, val = SWITCHES[int(rng.integers(0, len(SWITCHES)))]
+        recipe["switch"] = [name, val]
+    if kind in ("border", "band") and recipe["route"] == "host" and rng.random() < 0.15:
+        recipe["chunk_kib"] = int(rng.choice([1, 4, 16, 64]))
+
+    img, _ = frame(recipe, vox)
+    want_normals = rng.random() < 0.3
+    recipe["normals"] = bool(want_normals and recipe["route"] in NORMALS_ROUTES and img.size <= NORMALS_MAX_VOXELS
+                             and recipe["kw"].get("gradient", 0) == 0)
+    recipe["repeat"] = 3 if rng.random() < 0.12 and recipe["route"] not in ("slabs", "thin_slabs", "held") else 1
+    pick = rng.random() < 0.15, int(rng.integers(0, 8))
+    if pick[0] and recipe["route"] not in ("slabs", "thin_slabs", "held"):
+        names = REFUSALS[kind]
+        recipe["refusal"] = names[pick[1] % len(names)]
+        if recipe["refusal"] == "rg" and min(recipe["field"]["shape"]) < 4:
+            recipe["refusal"] = "variant"       # (shorter lines are refused for their length, not for the view)
+    # behind a normals case the setting stays on -- its row, sized by this mesh, is there for the next case -- or is switched off
+    recipe["drop_normals_row"] = bool(rng.random() < 0.25)
+    return recipe
+
+
+def _draw_border_value(rng, dt, iso):
+    """What border_check accepts for the pixel type: `converts` takes a value inside the range of an 8- to 32-bit integer type
+    and ANY double for the floating types -- a NaN or an infinite ring included --; the 64-bit integer types take what they hold."""
+    if dt.kind == "f":
+        fin = np.finfo(dt)
+        return [float(fin.min), float(fin.max), 0.0, -0.0, iso - 1.0, iso + 1.0, float(iso), float("inf"), float("-inf"), float("nan")][int(rng.integers(0, 10))]
+    info = np.iinfo(dt)
+    choices = [int(info.min), int(info.max), 0 if info.min <= 0 else int(info.min), int(iso) - 1, int(iso), int(iso) + 1, int(iso) - 7, int(iso) + 7]
+    return int(min(max(choices[int(rng.integers(0, len(choices)))], int(info.min)), int(info.max)))
+
+
+def _draw_band(rng, dt, vox):
+    """Bounds from the volume's own values (the band is neither empty nor everything in most cases); now and then lower ==
+    upper, the inverted choice, the constant case, and for the floating types signed zeros and infinities as bounds."""
+    finite = vox[np.isfinite(vox)] if dt.kind == "f" else vox.ravel()
+    vals = np.unique(finite)
+    if len(vals) == 0:
+        vals = np.zeros(1, dtype=dt)
+    a, b = sorted(int(v) for v in rng.integers(0, len(vals), size=2))
+    u = rng.random()
+    if u < 0.15:
+        b = a                                                    # a single label
+    lower, upper = vals[a].item(), vals[b].item()
+    if dt.kind == "f":
+        w = rng.random()
+        if w < 0.08:
+            lower = float("-inf")
+        elif w < 0.16:
+            upper = float("inf")
+        elif w < 0.22 and upper >= 0.0:
+            lower = [0.0, -0.0][int(rng.integers(0, 2))]
+        elif w < 0.28 and lower <= 0.0:
+            upper = [0.0, -0.0][int(rng.integers(0, 2))]
+    if dt.kind == "f":
+        triples = [(1.0, 0.0, 1.0), (0.0, 1.0, 1.0), (200.0, 10.0, 100.0), (-2.5, 7.25, 0.0), (1.0, 0.0, 0.5)]
+    elif dt == np.dtype(np.int8):
+        triples = [(1, 0, 1), (0, 1, 1), (100, 10, 50), (-100, 100, 0)]
+    else:
+        triples = [(1, 0, 1), (0, 1, 1), (200, 10, 100), (7, 3, 5)]
+    inside, outside, iso = triples[int(rng.integers(0, len(triples)))]
+    if dt.itemsize == 8 and dt.kind in "iu" and rng.random() < 0.4:      # B's two values and the iso value past 2^53 as well
+        off = (1 << 61) + 1
+        inside, outside, iso = inside + off, outside + off, iso + off
+    if rng.random() < 0.07:
+        outside = inside                                          # bin == bout: the bit volume is constant, the mesh empty
+    return dict(lower=_jnum(lower), upper=_jnum(upper), inside=_jnum(inside), outside=_jnum(outside), iso=_jnum(iso))
+
+
+def _draw_whole_route(rng, recipe, vox, opt):
+    """The draws the eight routes of a whole volume make beyond the route's name."""
+    route, kw = recipe["route"], recipe["kw"]
+    nz, ny, nx = vox.shape
+    dt = vox.dtype
+    if opt["recursive_gaussian"] and kw["project"] and min(nx, ny, nz) >= 4 and route in ("host", "device", "stream", "count_emit", "switch"):
+        kw["gradient"] = 1                         # USE_GRADIENT_RECURSIVE_GAUSSIAN (whole volumes, four voxels along every axis)
+    if route == "switch":
+        name, val = SWITCHES[int(rng.integers(0, len(SWITCHES)))]
+        recipe["switch"] = [name, val]
+    elif route == "held":
+        # quirk Q3: a first volume of its own (same pixel type), then this one along the first one's gradient
+        fshape = [int(rng.integers(2, 20)), int(rng.integers(2, 20)), int(rng.choice([3, 17, 64, 70]))]
+        fs, fo, fd = draw_geometry(rng)
+        fstart = [int(v) for v in rng.integers(-100, 100, size=3)] if rng.random() < 0.3 else [0, 0, 0]
+        kw["project"] = True
+        recipe["first"] = dict(field=dict(rng=[recipe["seed"], recipe["case"], 2], shape=fshape, dtype=dt.name), spacing=list(fs),
+                               origin=list(fo), direction=fd.tolist(), index_start=fstart)
+    elif route in ("slabs", "thin_slabs"):
+        thin = route == "thin_slabs"
+        occupied = bool(inside_set(vox, recipe["iso"]).reshape(nz, -1).any(axis=1).all())
+        coin = rng.random() < 0.5
+        if nz < 3 or not occupied or kw["variant"] != 0 and (thin or coin):
+            recipe["route"] = "host"        # (quirk Q1 across a cut needs the ranks' protocol: tests/test_gpu_slabs.py)
+        else:
+            ncut = int(rng.integers(1, min(4, nz - 1) + 1))
+            recipe["cuts"] = [0] + sorted(set(int(v) for v in rng.integers(1, nz, size=ncut))) + [nz]
+
+
+# ---- 2. the references -----------------------------------------------------------------------------------------------------
+def _geo(recipe):
+    return dict(spacing=tuple(recipe["spacing"]), origin=tuple(recipe["origin"]), direction=np.asarray(recipe["direction"], dtype=np.float64))
+
+
+def _oracle_kw(recipe):
+    return dict(recipe["kw"], **_geo(recipe))
+
+
+def expected(oracle, recipe, vox=None):
+    """{"mesh": the reference mesh (with .info, the walk's counters, where the reference has them), "normals": the reference
+    normals or None}.  Never the library."""
+    img, start = frame(recipe, vox)
+    okw = _oracle_kw(recipe)
+    if recipe["kind"] == "bspline":
+        mesh = _bspline_expected(oracle, recipe, img, start)
+    elif recipe["route"] == "held":
+        f = recipe["first"]
+        first = (_field(f["field"])[0], tuple(f["spacing"]), tuple(f["origin"]), np.asarray(f["direction"], dtype=np.float64), tuple(f["index_start"]))
+        mesh = oracle.run(img, recipe["iso"], first=first, index_start=start, **okw)
+    else:
+        mesh = oracle.run(img, recipe["iso"], index_start=start, **okw)
+    normals = None
+    if recipe.get("normals"):
+        import normals_ref
+        normals = normals_ref.normals(oracle, img, mesh.points, start, **_geo(recipe)) if len(mesh.points) else np.zeros((0, 3), dtype=np.float32)
+    return {"mesh": mesh, "normals": normals}
+
+
+def _bspline_expected(oracle, recipe, img, start):
+    """The oracle's lattice points and cells (the sweep does not depend on the interpolator), every point walked by the
+    drop-in's host walk through ITK's own class (bspline_ref.walk_exe(), mode `walk`: needs no GPU)."""
+    import bspline_ref
+    kw = recipe["kw"]
+    if not kw["project"]:
+        return oracle.run(img, recipe["iso"], index_start=start, **_oracle_kw(recipe))
+    # (quads: the triangles are cut along the shorter diagonal of the WALKED quad, txx:295-307 -- ref_filter.split_quads below)
+    flat = oracle.run(img, recipe["iso"], index_start=start, **dict(_oracle_kw(recipe), project=False, triangles=False))
+    flat.info = None                                   # (the host walk keeps no counters)
+    if not len(flat.points):
+        flat.cells = flat.cells.reshape(0, 3 if kw["triangles"] else 4)
+        return flat
+    nz, ny, nx = img.shape
+    with tempfile.TemporaryDirectory() as tmp:
+        raw, sp, op = (os.path.join(tmp, n) for n in ("v.raw", "s.raw", "o.raw"))
+        img.tofile(raw)
+        flat.points.astype("<f4").tofile(sp)
+        g = _geo(recipe)
+        r = subprocess.run([bspline_ref.walk_exe(), "walk", raw, bspline_ref.PIXEL_NAMES[img.dtype], str(nx), str(ny), str(nz),
+                            str(recipe["bspline"]["bits"]), bspline_ref.geometry_arg(g["spacing"], g["origin"], g["direction"], start),
+                            repr(float(recipe["iso"])), repr(kw["threshold"]), repr(kw["step"]), repr(kw["relax"]), str(kw["max_steps"]),
+                            sp, str(len(flat.points)), op], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout, r.stderr)
+        flat.points = np.fromfile(op, dtype="<f4").reshape(-1, 3)
+    if kw["triangles"]:
+        from ref_filter import split_quads
+        flat.cells = np.ascontiguousarray(split_quads(flat.points, flat.cells)).astype(np.uint64)
+    return flat
+
+
+# ---- 3. the library --------------------------------------------------------------------------------------------------------
+def open_contexts(pkg):
+    return {"ex": pkg.Extractor(0), "held": pkg.Extractor(0)}
+
+
+def close_contexts(contexts):
+    for name in ("ex", "held"):
+        contexts[name].close()
+
+
+# what the message of each refusal says (the code alone would not tell it from another reason to refuse)
+REFUSAL_TEXT = {"pair": "together with", "stream": "cuberille_extract_stream", "variant": "default projection branch only",
+                "held": "holding a gradient", "rg": "central-difference gradient only", "normals_rg": "point normals",
+                "bspline_variant": "B-spline interpolator walks the default projection branch",
+                "bspline_held": "B-spline interpolator is not offered on a context holding a gradient"}
+
+
+def _refused(pkg, ex, recipe, vox, desc, normals_on=False):
+    """One call the header lists as refused, with this case's volume: CUBERILLE_ERR_ARGUMENT with the text of THAT refusal, and
+    the context as it was.  The normals setting is not touched (switching it off would free the row a case before left), so
+    with it on the recursive-Gaussian gradient is refused for the normals' sake first."""
+    A = pkg._abi
+    name, kind = recipe["refusal"], recipe["kind"]
+    kw = dict(recipe["kw"], project=name != "normals_rg", variant=0)     # (normals_rg: without the walk the lines may be short)
+    kw.pop("gradient", None)
+    text = "point normals" if name == "rg" and normals_on else REFUSAL_TEXT[name]
+    vol = pkg.Volume(vox, spacing=tuple(recipe["spacing"]), origin=tuple(recipe["origin"]), direction=np.asarray(recipe["direction"]),
+                     index_start=tuple(recipe["index_start"]))
+    iso = recipe["iso"]
+    try:
+        if kind in ("border", "region", "band"):
+            _set_view(ex, recipe)
+        if name == "pair":            # a second view beside the case's own
+            if kind == "border":
+                ex.set_band(iso, iso, 1, 0) if np.dtype(recipe["dtype"]).kind != "f" else ex.set_band(0.0, 1.0, 1.0, 0.0)
+            else:
+                ex.set_border(1, 0)
+            call = lambda: ex.extract_host(vol, pkg.make_params(iso, **kw))                      # noqa: E731
+        elif name == "stream":
+            call = lambda: ex.extract_stream(desc, lambda dst, z0, z1: dst.__setitem__(Ellipsis, vox[z0:z1]), pkg.make_params(iso, **kw))  # noqa: E731
+        elif name in ("variant", "bspline_variant"):
+            if name == "bspline_variant":
+                ex.set_interpolator(A.INTERP_BSPLINE, 3, 32, 32)
+            call = lambda: ex.extract_host(vol, pkg.make_params(iso, **dict(kw, variant=1 + recipe["case"] % 2)))   # noqa: E731
+        elif name in ("held", "bspline_held"):
+            if name == "bspline_held":
+                ex.set_interpolator(A.INTERP_BSPLINE, 3, 64, 64)
+            ex.hold_gradient(True)
+            call = lambda: ex.extract_host(vol, pkg.make_params(iso, **kw))                      # noqa: E731
+        elif name == "rg":
+            call = lambda: ex.extract_host(vol, pkg.make_params(iso, **dict(kw, gradient=1)))    # noqa: E731
+        elif name == "normals_rg":
+            ex.set_point_normals(True)
+            call = lambda: ex.extract_host(vol, pkg.make_params(iso, **dict(kw, gradient=1)))    # noqa: E731
+        else:
+            raise ValueError(name)
+        try:
+            call()
+        except A.CuberilleError as e:
+            assert e.code == A.ERR_ARGUMENT, "refusal %s: code %d (%s), not CUBERILLE_ERR_ARGUMENT" % (name, e.code, e)
+            assert text in str(e), "refusal %s: refused for another reason: %s" % (name, e)
+        else:
+            raise AssertionError("refusal %s: the call was accepted" % name)
+    finally:
+        _clear_settings(pkg, ex)
+
+
+def _set_view(ex, recipe):
+    kind = recipe["kind"]
+    if kind == "border":
+        ex.set_border(1, _num(recipe["border"]["value"]))
+    elif kind == "region":
+        ex.set_region(recipe["region"]["start"], recipe["region"]["size"])
+    elif kind == "band":
+        b = recipe["band"]
+        ex.set_band(_num(b["lower"]), _num(b["upper"]), _num(b["inside"]), _num(b["outside"]))
+
+
+def _clear_settings(pkg, ex):
+    ex.set_border(0, 0)
+    ex.clear_region()
+    ex.clear_band()
+    ex.hold_gradient(False)
+    ex.set_interpolator(pkg._abi.INTERP_LINEAR)
+    ex.debug_option("defaults", 0)         # (cuberille_set_point_normals is the case's to set: off would free the row)
+
+
+def run_case(pkg, contexts, recipe, vox=None, stats=None):
+    """{"mesh", "normals" (or None), "counters" (or None), "row_before"} of the library for the recipe, on the contexts as the
+    cases before left them (the settings a case makes are taken back behind it; the workspace, its sizes, its history and --
+    unless the recipe drops it -- the normals row of a normals case stay).  row_before: the points of the mesh whose normals row
+    the context still held when the case began, or None."""
+    import torch
+    vox = voxels(recipe) if vox is None else vox
+    dt = vox.dtype
+    nz, ny, nx = vox.shape
+    kind, route, kw, iso = recipe["kind"], recipe["route"], recipe["kw"], recipe["iso"]
+    spacing, origin, direction, start = tuple(recipe["spacing"]), tuple(recipe["origin"]), np.asarray(recipe["direction"], dtype=np.float64), tuple(recipe["index_start"])
+    ex = contexts["held"] if route == "held" else contexts["ex"]
+    vol = pkg.Volume(vox, spacing=spacing, origin=origin, direction=direction, index_start=start)
+    desc = pkg.make_desc(dt, (nx, ny, nz), spacing, origin, direction, start)
+    prm = pkg.make_params(iso, **kw)
+    row_before = contexts.get("normals_row") if route != "held" else None
+    if recipe.get("refusal"):
+        _refused(pkg, ex, recipe, vox, desc, row_before is not None)
+    mesh = normals = counters = None
+    try:
+        _set_view(ex, recipe)
+        if kind == "bspline":
+            ex.set_interpolator(pkg._abi.INTERP_BSPLINE, 3, recipe["bspline"]["bits"], recipe["bspline"]["bits"])
+        if recipe.get("switch"):
+            ex.debug_option(recipe["switch"][0], recipe["switch"][1])
+        if recipe.get("chunk_kib"):
+            ex.debug_option("upload_chunk_kib", recipe["chunk_kib"])
+        ex.set_point_normals(bool(recipe.get("normals")))
+        for _ in range(int(recipe.get("repeat", 1))):
+            res = None
+            if route in ("host", "host_chunked", "switch"):
+                res = ex.extract_host(vol, prm)
+                mesh = ex.download()
+            elif route == "device":
+                dev = to_device(torch, vox)
+                torch.cuda.synchronize()
+                res = ex.extract_device(dev.data_ptr(), desc, prm)
+                mesh = ex.mesh_host()
+                mesh = pkg.Mesh(mesh.points.copy(), mesh.cells.copy())
+            elif route == "stream":
+                def source(dst, z0, z1):
+                    dst[...] = vox[z0:z1]
+                res = ex.extract_stream(desc, source, prm)
+                mesh = ex.download()
+            elif route == "count_emit":
+                dev = to_device(torch, vox)
+                torch.cuda.synchronize()
+                n_p, n_c = ex.count(dev.data_ptr(), desc, prm)
+                res = ex.emit(0)
+                mesh = ex.download()
+                assert (n_p, n_c) == (mesh.points.shape[0], mesh.cells.shape[0])
+            elif route == "held":
+                # quirk Q3: a first volume of its own (same pixel type), then this one along the first one's gradient
+                f = recipe["first"]
+                fvox = _field(f["field"])[0]
+                ex.hold_gradient(False)
+                ex.hold_gradient(True)
+                ex.extract_host(pkg.Volume(fvox, spacing=tuple(f["spacing"]), origin=tuple(f["origin"]),
+                                           direction=np.asarray(f["direction"], dtype=np.float64), index_start=tuple(f["index_start"])), prm)
+                ex.extract_host(vol, prm)
+                mesh = ex.download()
+            else:   # slabs stitched by hand: counts, id offsets, concatenation; thin: 3 + 3 halo slices, escaped walks again
+                thin = route == "thin_slabs"
+                below, above = pkg.required_halo(desc, prm)
+                cuts = recipe["cuts"]
+                pts, cells, poff = [], [], 0
+                tb, ta = pkg.cuberille.minimum_halo(desc, prm)
+                for a, b in zip(cuts[:-1], cuts[1:]):
+                    lo, hi = (max(a - tb - 1, 0), min(b + ta + 1, nz)) if thin else (max(a - below, 0), min(b + above, nz))
+                    dev = to_device(torch, vox[lo:hi])
+                    torch.cuda.synchronize()
+                    sdesc = pkg.make_desc(dt, (nx, ny, hi - lo), spacing, origin, direction, start)
+                    n_p, n_c = ex.count(dev.data_ptr(), sdesc, prm, pkg._abi.Slab(nz, lo, a, b, 0, pkg._abi.SLAB_THIN_HALO if thin else 0))
+                    if thin:
+                        ex.emit_points()
+                        n_esc = ex.escaped_count()
+                        if stats is not None:
+                            stats["escaped_walks"] = stats.get("escaped_walks", 0) + int(n_esc)
+                        if n_esc:
+                            dlo, dhi = max(a - below, 0), min(b + above, nz)
+                            deep = to_device(torch, vox[dlo:dhi])
+                            torch.cuda.synchronize()
+                            ex.reproject_escaped(deep.data_ptr(), dlo, dhi - dlo)
+                    ex.emit(poff)
+                    m = ex.download()
+                    pts.append(m.points)
+                    cells.append(m.cells)
+                    poff += n_p
+                mesh = pkg.Mesh(np.concatenate(pts), np.concatenate(cells))
+            if res is not None:
+                counters = {k: int(getattr(res, k)) for k in COUNTERS}
+            if recipe.get("normals"):
+                normals = ex.download_normals()
+    finally:
+        _clear_settings(pkg, ex)
+        if route != "held":
+            contexts["normals_row"] = None
+    if route != "held":
+        contexts["normals_row"] = row_after(recipe, int(mesh.points.shape[0]))
+        if contexts["normals_row"] is None:
+            ex.set_point_normals(False)
+    return {"mesh": mesh, "normals": normals, "counters": counters, "row_before": row_before}
+
+
+def row_after(recipe, n_points):
+    """The points of the mesh whose normals row a case leaves on its context (None: no row -- no normals, or dropped)."""
+    return n_points if recipe.get("normals") and not recipe.get("drop_normals_row") else None
+
+
+def meets_row_of_another_size(row_before, recipe, n_points):
+    """A normals case on a context that still holds the row of a mesh of another size."""
+    return bool(recipe.get("normals")) and row_before is not None and row_before != n_points
+
+
+def compare(got, want):
+    """The first difference as an AssertionError: mesh, then counters, then normals."""
+    import normals_ref
+    assert_same_mesh(got["mesh"], want["mesh"])
+    info = getattr(want["mesh"], "info", None)
+    if got["counters"] is not None and info is not None:
+        assert got["counters"] == {k: info[k] for k in COUNTERS}, ("counters", got["counters"], {k: info[k] for k in COUNTERS})
+    if want["normals"] is not None:
+        assert got["normals"] is not None, "no normals came back"
+        normals_ref.same_normals(got["normals"], want["normals"], "normals")
+
+
+def tally(stats, recipe, got, want):
+    mesh = got["mesh"]
+    stats["cases"] += 1
+    stats["points"] += int(mesh.points.shape[0])
+    stats["cells"] += int(mesh.cells.shape[0])
+    stats["nan_points"] += int(np.isnan(mesh.points).any(axis=1).sum()) if mesh.points.size else 0
+    for key, val in (("routes", recipe["route"]), ("dtypes", recipe["dtype"]), ("kinds", recipe["kind"])):
+        stats[key][val] = stats[key].get(val, 0) + 1
+    stats["with_normals"] += int(bool(recipe.get("normals")))
+    stats["normals_on_a_row_of_another_size"] += int(meets_row_of_another_size(got.get("row_before"), recipe, int(mesh.points.shape[0])))
+    stats["nan_normals"] += int(np.isnan(want["normals"]).any(axis=1).sum()) if want["normals"] is not None and want["normals"].size else 0
+    stats["repeats"] += int(recipe.get("repeat", 1) > 1)
+    stats["after_refusal"] += int(bool(recipe.get("refusal")))
+    stats["with_switch"] += int(bool(recipe.get("switch")) or bool(recipe.get("chunk_kib")))
+    if recipe.get("refusal"):
+        key = "%s:%s" % (recipe["kind"], recipe["refusal"])
+        stats["refusals"][key] = stats["refusals"].get(key, 0) + 1
+
+
+def new_stats():
+    return {"cases": 0, "points": 0, "cells": 0, "routes": {}, "dtypes": {}, "kinds": {}, "with_normals": 0, "normals_on_a_row_of_another_size": 0, "nan_normals": 0, "repeats": 0,
+            "after_refusal": 0, "refusals": {}, "with_switch": 0, "refused_slab_alias": 0, "nan_points": 0}
+
+
+def one_case(pkg, oracle, contexts, recipe, stats=None):
+    """Run and compare one recipe; returns (got, want).  Raises at the first difference."""
+    vox = voxels(recipe)
+    want = expected(oracle, recipe, vox)
+    got = run_case(pkg, contexts, recipe, vox, stats)
+    compare(got, want)
+    return got, want
+
+
+# ---- the seeded slice of the GPU suite (tests/test_gpu_campaign.py; its conditions: tests/test_campaign_scripts.py) ------------
+# kind: (seed, number of cases).  Case i of a kind takes pixel type DTYPES[i % 10] and the kind's routes in turn; everything else
+# is drawn.  The seeds are the first for which the oracle alone shows every condition of slice_conditions().
+SLICE_OPTIONS = dict(max_rows=12, max_voxels=30000)
+SLICE = {"whole": (54, 24), "border": (4, 20), "region": (1, 20), "band": (1, 20), "bspline": (5, 20)}
+
+
+def slice_recipes(kind, seed=None, n=None):
+    seed = SLICE[kind][0] if seed is None else seed
+    n = SLICE[kind][1] if n is None else n
+    return [draw_case(seed, i, dict(SLICE_OPTIONS, kind=kind, dtype=np.dtype(DTYPES[i % len(DTYPES)]).name,
+                                    route=ROUTES[kind][i % len(ROUTES[kind])])) for i in range(n)]
+
+
+def slice_facts(recipe, want, row_before=None):
+    """What one executed case of the slice contributes to the conditions, from the recipe and the reference alone.  row_before:
+    what row_after() gave for the case before it on the context (slice_sequence_facts follows it through a kind's cases)."""
+    img, _ = frame(recipe)
+    pts, nrm = want["mesh"].points, want["normals"]
+    return dict(walks=bool(recipe["kw"]["project"]) and recipe["kw"]["max_steps"] > 0 and len(pts) > 0,
+                other_row=meets_row_of_another_size(row_before, recipe, len(pts)),
+                kind=recipe["kind"], dtype=recipe["dtype"], route=recipe["route"], triangles=bool(recipe["kw"]["triangles"]),
+                project=bool(recipe["kw"]["project"]), form=geometry_form(recipe), moved=any(int(v) for v in recipe["index_start"]),
+                q1=bool(has_q1_gap(img, recipe["iso"])), empty=len(pts) == 0, nan_points=bool(np.isnan(pts).any()),
+                normals=nrm is not None and len(nrm) > 0, nan_normals=nrm is not None and bool(np.isnan(nrm).any()),
+                repeat=recipe.get("repeat", 1) > 1, refusal=recipe.get("refusal"))
+
+
+def slice_sequence_facts(recipes, wants):
+    """slice_facts of a kind's cases in the order they run on their one context."""
+    facts, row = [], None
+    for recipe, want in zip(recipes, wants):
+        held = recipe["route"] == "held"                      # (a context of its own, never with normals)
+        facts.append(slice_facts(recipe, want, None if held else row))
+        if not held:
+            row = row_after(recipe, len(want["mesh"].points))
+    return facts
+
+
+def slice_conditions(kind, facts):
+    """The conditions a kind's slice must meet, as a list of those it misses (empty: all hold)."""
+    missing = []
+    def need(ok, what):
+        if not ok:
+            missing.append("%s: %s" % (kind, what))
+    need(all(f["kind"] == kind for f in facts), "a case of another kind")
+    need({f["dtype"] for f in facts} == {np.dtype(d).name for d in DTYPES}, "all ten pixel types")
+    for r in ROUTES[kind]:
+        need(sum(f["route"] == r for f in facts) >= 2, "route %s at least twice" % r)
+    need({f["triangles"] for f in facts} == {True, False}, "quads and triangles")
+    need({f["project"] for f in facts} == {True, False}, "projection on and off")
+    # (the form is the walk kernel's: it exists where vertices are projected with at least one step)
+    need({f["form"] for f in facts if f["walks"]} == {"identity", "axis-aligned", "general"}, "the three geometry forms, each on a case that walks")
+    need(any(f["moved"] for f in facts), "a start index other than 0")
+    need(any(f["q1"] and not f["empty"] for f in facts), "an empty slice between occupied ones (quirk Q1)")
+    if kind in ("border", "region", "band"):
+        need(any(f["refusal"] for f in facts), "a case behind a refused call")
+    need(4 * sum(f["empty"] for f in facts) <= len(facts), "at most a quarter of the cases with an empty reference mesh")
+    return missing
+
+
+def slice_conditions_overall(facts):
+    """... and those of the whole slice (facts: of every kind together)."""
+    missing = []
+    def need(ok, what):
+        if not ok:
+            missing.append(what)
+    need(any(f["nan_points"] for f in facts), "a case with NaN coordinates in the reference mesh")
+    need(any(f["normals"] and f["nan_normals"] for f in facts), "a normals case with a NaN normal")
+    need(any(f["normals"] and not f["nan_normals"] for f in facts), "a normals case without a NaN normal")
+    need(any(f["repeat"] for f in facts), "a repeat case")
+    need(any(f["repeat"] and f["normals"] for f in facts), "a repeat case with normals")
+    need(any(f["other_row"] for f in facts), "a normals case on a context whose previous case left a normals row of another size")
+    need({f["kind"] for f in facts} == set(KINDS), "the cases of every kind")
+    for k in ("border", "region", "band"):
+        need(any(f["kind"] == k and f["refusal"] for f in facts), "a refusal case of kind %s" % k)
+    return missing
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300.0)
@@ -115,152 +807,55 @@ def main():
     ap.add_argument("--max-voxels", type=int, default=900000)
     ap.add_argument("--recursive-gaussian", action="store_true", help="every case that can takes the recursive-Gaussian gradient (h:21)")
     ap.add_argument("--big", action="store_true", help="up to 120 rows and slices (fewer, larger cases: set --max-voxels too)")
+    ap.add_argument("--kind", choices=KINDS, default=None, help="draw this kind only")
+    ap.add_argument("--dtype", default=None, help="draw this pixel type only (a numpy name)")
+    ap.add_argument("--route", default=None, help="draw this route only (with --kind)")
+    ap.add_argument("--max-rows", type=int, default=None, help="rows and slices up to this many (default 40, 120 with --big)")
+    ap.add_argument("--case", type=int, default=None, help="run this one case of --seed (with the options the run had) and print the first difference")
+    ap.add_argument("--replay", default=None, help="run one recipe: its JSON, or a file that holds it (a FAILED line is accepted as it is)")
     args = ap.parse_args()
-    import torch
+    options = dict(max_voxels=args.max_voxels, big=args.big, recursive_gaussian=args.recursive_gaussian, kind=args.kind,
+                   dtype=args.dtype, route=args.route, max_rows=args.max_rows)
     pkg = graft.load_package()
     oracle = graft.load_oracle()
     oracle.build()
-    rng = np.random.default_rng(args.seed)
-    ex = pkg.Extractor(0)
-    held = pkg.Extractor(0)
-    t0 = last = time.time()
-    stats = {"cases": 0, "points": 0, "cells": 0, "routes": {}, "dtypes": {}, "refused_slab_alias": 0, "nan_points": 0}
-    case = -1
+    contexts = open_contexts(pkg)
     try:
-        while time.time() - t0 < args.seconds:
-            case += 1
-            nx = int(rng.choice(XS))
-            ny = int(rng.integers(1, 121 if args.big else 41))
-            nz = int(rng.integers(1, 121 if args.big else 41))
-            while nx * ny * nz > args.max_voxels:
-                ny = max(1, ny // 2)
-                nz = max(1, nz // 2)
-            dt = DTYPES[int(rng.integers(0, len(DTYPES)))]
-            vox, iso = draw_field(rng, (nz, ny, nx), dt)
-            spacing, origin, direction = draw_geometry(rng)
-            # the buffered region's start index (a cropped image keeps the index it was cut at)
-            start = tuple(int(v) for v in rng.integers(-3000, 3000, size=3)) if rng.random() < 0.3 else (0, 0, 0)
-            project = bool(rng.random() < 0.75)
-            variant = int(rng.choice([0, 0, 0, 1, 2])) if project else 0
-            kw = dict(triangles=bool(rng.integers(0, 2)), project=project,
-                      threshold=float(rng.choice([0.0, 0.01, 0.2, 5.0])) * (1.0 if np.dtype(dt).kind != "f" else 0.05),
-                      step=float(rng.choice([0.1, 0.25, 0.6, 1.3])) * min(spacing),
-                      relax=float(rng.choice([0.5, 0.9, 0.95, 1.0])), max_steps=int(rng.choice([0, 1, 4, 25, 50])), variant=variant)
-            route = str(rng.choice(["host", "device", "stream", "slabs", "thin_slabs", "count_emit", "held", "switch"]))
-            if args.recursive_gaussian and project and min(nx, ny, nz) >= 4 and route in ("host", "device", "stream", "count_emit", "switch"):
-                kw["gradient"] = 1                         # USE_GRADIENT_RECURSIVE_GAUSSIAN (whole volumes, four voxels along every axis)
-            vol = pkg.Volume(vox, spacing=spacing, origin=origin, direction=direction, index_start=start)
-            okw = dict(kw, spacing=spacing, origin=origin, direction=direction, index_start=start)
-            recipe = dict(case=case, seed=args.seed, shape=[nz, ny, nx], dtype=np.dtype(dt).name, iso=iso, route=route, kw=kw,
-                          spacing=spacing, origin=origin, direction=direction.tolist(), index_start=start)
-            prm = pkg.make_params(iso, **kw)
-            desc = pkg.make_desc(vox.dtype, (nx, ny, nz), spacing, origin, direction, start)
+        if args.replay is not None or args.case is not None:
+            if args.replay is not None:
+                text = open(args.replay).read() if os.path.exists(args.replay) else args.replay
+                recipe = json.loads(text)
+                recipe = recipe.get("FAILED", recipe)
+            else:
+                recipe = draw_case(args.seed, args.case, options)
+            print(json.dumps({"recipe": recipe}), flush=True)
             try:
-                ref = None
-                if route == "host":
-                    ex.extract_host(vol, prm)
-                    mesh = ex.download()
-                elif route == "device":
-                    dev = to_device(torch, vox)
-                    ex.extract_device(dev.data_ptr(), desc, prm)
-                    mesh = ex.mesh_host()
-                    mesh = pkg.Mesh(mesh.points.copy(), mesh.cells.copy())
-                elif route == "stream":
-                    def source(dst, z0, z1):
-                        dst[...] = vox[z0:z1]
-                    ex.extract_stream(desc, source, prm)
-                    mesh = ex.download()
-                elif route == "count_emit":
-                    dev = to_device(torch, vox)
-                    n_p, n_c = ex.count(dev.data_ptr(), desc, prm)
-                    ex.emit(0)
-                    mesh = ex.download()
-                    assert (n_p, n_c) == (mesh.points.shape[0], mesh.cells.shape[0])
-                elif route == "switch":
-                    name, val = [("no_cmap", 1), ("no_heads", 1), ("no_vqueue", 1), ("count_variant", 1), ("count_variant", 2),
-                                 ("count_variant", 3), ("count_variant", 0), ("points_variant", 2), ("points_variant", 1),
-                                 ("points_variant", 0), ("classify_variant", 1), ("proj_literal", 1), ("cmap_linear", 1),
-                                 ("no_stream_classify", 1), ("proj_short", 1), ("proj_short", 0), ("count_no_fold", 1)][int(rng.integers(0, 17))]
-                    recipe["switch"] = [name, val]
-                    ex.debug_option(name, val)
-                    try:
-                        ex.extract_host(vol, prm)
-                        mesh = ex.download()
-                    finally:
-                        ex.debug_option("defaults", 0)
-                elif route == "held":
-                    # quirk Q3: a first volume of its own (same pixel type), then this one along the first one's gradient
-                    fshape = (int(rng.integers(2, 20)), int(rng.integers(2, 20)), int(rng.choice([3, 17, 64, 70])))
-                    fvox, _ = draw_field(rng, fshape, dt)
-                    fs, fo, fd = draw_geometry(rng)
-                    fstart = tuple(int(v) for v in rng.integers(-100, 100, size=3)) if rng.random() < 0.3 else (0, 0, 0)
-                    held.hold_gradient(False)
-                    held.hold_gradient(True)
-                    if not project:
-                        kw["project"] = okw["project"] = True
-                        prm = pkg.make_params(iso, **kw)
-                    held.extract_host(pkg.Volume(fvox, spacing=fs, origin=fo, direction=fd, index_start=fstart), prm)
-                    held.extract_host(vol, prm)
-                    mesh = held.download()
-                    recipe["first"] = dict(shape=list(fshape), spacing=fs, origin=fo, direction=fd.tolist(), index_start=fstart)
-                    ref = oracle.run(vox, iso, first=(fvox, fs, fo, fd, fstart), **okw)
-                else:   # slabs stitched by hand: counts, id offsets, concatenation; thin: 3 + 3 halo slices, escaped walks again
-                    thin = route == "thin_slabs"
-                    occupied = True
-                    ins = vox >= (np.dtype(dt).type(iso) if np.dtype(dt).kind != "f" else iso)
-                    if np.dtype(dt).kind == "f":
-                        ins = ins & ~np.isnan(vox)
-                    occupied = bool(ins.reshape(nz, -1).any(axis=1).all())
-                    if nz < 3 or not occupied or variant != 0 and (thin or rng.random() < 0.5):
-                        route = recipe["route"] = "host"        # (quirk Q1 across a cut needs the ranks' protocol: tests/test_gpu_slabs.py)
-                        ex.extract_host(vol, prm)
-                        mesh = ex.download()
-                    else:
-                        below, above = pkg.required_halo(desc, prm)
-                        ncut = int(rng.integers(1, min(4, nz - 1) + 1))
-                        cuts = [0] + sorted(set(int(v) for v in rng.integers(1, nz, size=ncut))) + [nz]
-                        recipe["cuts"] = cuts
-                        pts, cells, poff = [], [], 0
-                        tb, ta = pkg.cuberille.minimum_halo(desc, prm)
-                        for a, b in zip(cuts[:-1], cuts[1:]):
-                            lo, hi = (max(a - tb - 1, 0), min(b + ta + 1, nz)) if thin else (max(a - below, 0), min(b + above, nz))
-                            dev = to_device(torch, vox[lo:hi])
-                            sdesc = pkg.make_desc(vox.dtype, (nx, ny, hi - lo), spacing, origin, direction, start)
-                            n_p, n_c = ex.count(dev.data_ptr(), sdesc, prm, pkg._abi.Slab(nz, lo, a, b, 0, pkg._abi.SLAB_THIN_HALO if thin else 0))
-                            if thin:
-                                ex.emit_points()
-                                n_esc = ex.escaped_count()
-                                stats["escaped_walks"] = stats.get("escaped_walks", 0) + int(n_esc)
-                                if n_esc:
-                                    dlo, dhi = max(a - below, 0), min(b + above, nz)
-                                    deep = to_device(torch, vox[dlo:dhi])
-                                    ex.reproject_escaped(deep.data_ptr(), dlo, dhi - dlo)
-                            ex.emit(poff)
-                            m = ex.download()
-                            pts.append(m.points)
-                            cells.append(m.cells)
-                            poff += n_p
-                        mesh = pkg.Mesh(np.concatenate(pts), np.concatenate(cells))
-                if ref is None:
-                    ref = oracle.run(vox, iso, **okw)
-                assert_same_mesh(mesh, ref)
+                got, _ = one_case(pkg, oracle, contexts, recipe)
             except Exception as e:  # noqa: BLE001
                 print(json.dumps({"FAILED": recipe, "error": "%s: %s" % (type(e).__name__, str(e)[:400])}), flush=True)
                 return 1
-            stats["cases"] += 1
-            stats["points"] += int(mesh.points.shape[0])
-            stats["cells"] += int(mesh.cells.shape[0])
-            stats["nan_points"] += int(np.isnan(mesh.points).any(axis=1).sum()) if mesh.points.size else 0
-            stats["routes"][route] = stats["routes"].get(route, 0) + 1
-            stats["dtypes"][np.dtype(dt).name] = stats["dtypes"].get(np.dtype(dt).name, 0) + 1
+            print(json.dumps({"identical": True, "points": int(got["mesh"].points.shape[0]), "cells": int(got["mesh"].cells.shape[0])}), flush=True)
+            return 0
+        t0 = last = time.time()
+        stats = new_stats()
+        case = -1
+        while time.time() - t0 < args.seconds:
+            case += 1
+            recipe = draw_case(args.seed, case, options)
+            try:
+                got, want = one_case(pkg, oracle, contexts, recipe, stats)
+            except Exception as e:  # noqa: BLE001
+                print(json.dumps({"FAILED": recipe, "error": "%s: %s" % (type(e).__name__, str(e)[:400])}), flush=True)
+                return 1
+            tally(stats, recipe, got, want)
             if time.time() - last > 20:
                 last = time.time()
                 print("t %.0f s: %d cases, %d points, %d cells, all identical" % (last - t0, stats["cases"], stats["points"], stats["cells"]), flush=True)
     finally:
-        ex.close()
-        held.close()
+        close_contexts(contexts)
     stats["seconds"] = round(time.time() - t0, 1)
     stats["seed"] = args.seed
+    stats["options"] = {k: v for k, v in options.items() if v not in (None, False)}
     stats["identical"] = True
     print(json.dumps(stats), flush=True)
     return 0

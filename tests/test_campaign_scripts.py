@@ -1,7 +1,10 @@
 """-m "not gpu": the hand-run campaign and profile scripts stay importable, and the campaign's generators stay inside what the
 oracle accepts (every drawn volume, geometry, start index and held first volume runs through it) -- so that the scripts do not rot
-between the rounds in which somebody runs them on a GPU box."""
+between the rounds in which somebody runs them on a GPU box.  The campaign's new dimensions too: every drawn border value, box
+and band passes its validator, every drawn recipe survives JSON, rebuilds the same bytes and runs through expected(); and the
+seeded slice of tests/test_gpu_campaign.py holds the conditions that keep it from hiding a failure, shown on the oracle alone."""
 import glob
+import json
 import os
 import py_compile
 
@@ -54,3 +57,154 @@ def test_campaign_generators_run_through_the_oracle(oracle):
         a = (np.arange(24).reshape(2, 3, 4) * 1000).astype(dt)
         b = fz.to_device(_T, a)
         assert b.tobytes() == a.tobytes() and b.dtype.itemsize == a.dtype.itemsize
+
+
+def _recipes(n, **options):
+    import fuzz_campaign as fz
+    return [fz.draw_case(23, case, dict(max_rows=10, max_voxels=20000, **options)) for case in range(n)]
+
+
+def test_drawn_views_pass_their_validators(pkg):
+    """No GPU: the ring's value by border_check's rule (check_border for the 64-bit integer types, the range of the type for the
+    others -- `converts` takes any double for the floating types, a NaN or infinite ring included), the box by
+    cuberille_region_desc, the band by cuberille_band_check."""
+    import fuzz_campaign as fz
+    seen = {"nonfinite_ring": 0, "single_label": 0, "constant_band": 0, "inf_bound": 0, "zero_bound": 0, "forms": set(), "residues": set()}
+    for kind in ("border", "region", "band"):
+        for r in _recipes(300, kind=kind):
+            dt = np.dtype(r["dtype"])
+            code = int(pkg.make_desc(dt, (1, 1, 1)).pixel_type)
+            nz, ny, nx = r["field"]["shape"]
+            desc = pkg.make_desc(dt, (nx, ny, nz), r["spacing"], r["origin"], np.asarray(r["direction"]), r["index_start"])
+            if kind == "border":
+                c = fz._num(r["border"]["value"])
+                if dt.kind == "f":
+                    seen["nonfinite_ring"] += int(not np.isfinite(c))
+                else:
+                    info = np.iinfo(dt)
+                    assert isinstance(c, int) and int(info.min) <= c <= int(info.max), r
+                    pkg.cuberille.check_border(code, (1, c))
+            elif kind == "region":
+                box = pkg.region_desc(desc, r["region"]["start"], r["region"]["size"])
+                assert list(box.dims) == r["region"]["size"] and list(box.index_start) == list(fz.frame_start(r))
+                seen["forms"].add(r["region"]["form"])
+                seen["residues"].add((r["region"]["start"][0] * dt.itemsize) % 16)
+                if r["region"]["form"] == "full_xy":
+                    assert r["region"]["size"][:2] == [nx, ny] and r["region"]["start"][:2] == [0, 0]
+                if r["region"]["form"] == "whole_buffer":
+                    assert r["region"]["size"] == [nx, ny, nz]
+                if r["region"]["form"] == "words_in_ragged":
+                    assert r["region"]["size"][0] % 64 == 0 and nx % 64 != 0
+                if r["region"]["form"] == "ragged_in_words":
+                    assert nx % 64 == 0
+            else:
+                b = [fz._num(r["band"][k]) for k in ("lower", "upper", "inside", "outside")]
+                pkg.check_band(code, tuple(b))
+                seen["single_label"] += int(b[0] == b[1])
+                seen["constant_band"] += int(b[2] == b[3])
+                seen["inf_bound"] += int(dt.kind == "f" and (np.isinf(b[0]) or np.isinf(b[1])))
+                seen["zero_bound"] += int(dt.kind == "f" and (b[0] == 0.0 or b[1] == 0.0))
+    assert seen["forms"] == {"full_xy", "thin", "residue", "words_in_ragged", "ragged_in_words", "whole_buffer", "any"}
+    assert seen["residues"] == set(range(16))
+    assert min(seen[k] for k in ("nonfinite_ring", "single_label", "constant_band", "inf_bound", "zero_bound")) > 0, seen
+
+
+def test_recipes_survive_json_and_run_through_the_references(oracle):
+    """Every kind, route, normals, repeat and refusal the campaign draws: the recipe is plain data, its JSON round trip rebuilds
+    the same voxel bytes and the same expected mesh (and normals), and draw_case is a pure function of (seed, case)."""
+    import fuzz_campaign as fz
+    from conftest import assert_same_mesh
+    from normals_ref import same_normals
+    seen = {"kinds": set(), "routes": set(), "normals": 0, "repeat": 0, "refusals": set(), "switch": 0, "beyond_2_53": 0}
+    recipes = _recipes(160)
+    assert recipes == _recipes(160)
+    for r in recipes:
+        text = json.dumps(r)
+        back = json.loads(text)
+        assert back == r and json.dumps(back) == text
+        vox = fz.voxels(r)
+        assert fz.voxels(back).tobytes() == vox.tobytes() and vox.dtype == np.dtype(r["dtype"]) and list(vox.shape) == r["field"]["shape"]
+        want, again = fz.expected(oracle, r), fz.expected(oracle, back)
+        assert_same_mesh(again["mesh"], want["mesh"])
+        assert want["mesh"].cells.shape[1] == (3 if r["kw"]["triangles"] else 4)
+        assert (want["normals"] is not None) == bool(r["normals"])
+        if r["normals"]:
+            same_normals(again["normals"], want["normals"])
+            assert want["normals"].shape == want["mesh"].points.shape
+            assert fz.frame(r)[0].size <= fz.NORMALS_MAX_VOXELS and r["route"] in fz.NORMALS_ROUTES
+        if r["kind"] != "whole":
+            assert r["kw"]["variant"] == 0 and "gradient" not in r["kw"] and r["route"] in fz.ROUTES[r["kind"]]
+        if r["kind"] == "bspline":
+            assert vox.size <= fz.BSPLINE_MAX_VOXELS and r["bspline"]["bits"] in (32, 64)
+        seen["kinds"].add(r["kind"])
+        seen["routes"].add(r["route"])
+        seen["normals"] += int(r["normals"])
+        seen["repeat"] += int(r["repeat"] == 3)
+        seen["switch"] += int("switch" in r and r["kind"] != "whole")
+        seen["beyond_2_53"] += int(vox.dtype.itemsize == 8 and vox.dtype.kind in "iu" and abs(int(vox.ravel()[0])) > 1 << 53)
+        assert isinstance(r["drop_normals_row"], bool)
+        if r.get("refusal"):
+            assert r["refusal"] in fz.REFUSALS[r["kind"]] and r["refusal"] in fz.REFUSAL_TEXT
+            assert r["refusal"] != "rg" or min(r["field"]["shape"]) >= 4     # (else the lines' length would be the reason)
+            seen["refusals"].add(r["refusal"])
+    assert seen["kinds"] == set(fz.KINDS)
+    assert seen["routes"] >= {"host", "device", "stream", "slabs", "thin_slabs", "count_emit", "held", "switch", "host_chunked"}
+    assert len(seen["refusals"]) >= 5 and min(seen[k] for k in ("normals", "repeat", "switch", "beyond_2_53")) > 0, seen
+
+
+def test_gpu_slice_conditions_hold_on_the_oracle(oracle):
+    """The seeded slice of tests/test_gpu_campaign.py, from draw_case and the oracle alone: per kind and over the whole slice."""
+    import fuzz_campaign as fz
+    facts = []
+    for kind in fz.KINDS:
+        recipes = fz.slice_recipes(kind)
+        assert len(recipes) == fz.SLICE[kind][1] >= 20
+        for i, r in enumerate(recipes):
+            assert (r["seed"], r["case"], r["kind"]) == (fz.SLICE[kind][0], i, kind)
+            assert r["dtype"] == np.dtype(fz.DTYPES[i % 10]).name
+            buf = r["field"]["shape"]                                        # [nz, ny, nx]
+            box = r["region"]["size"][::-1] if kind == "region" else buf
+            assert max(box[:2]) <= 12 and box[2] <= max(fz.XS) and np.prod(box) <= 30000
+            assert all(0 <= b - a <= m for a, b, m in zip(box, buf, (7, 7, 87))) and np.prod(buf) <= 60000
+        mine = fz.slice_sequence_facts(recipes, [fz.expected(oracle, r) for r in recipes])
+        assert fz.slice_conditions(kind, mine) == []
+        facts += mine
+    assert fz.slice_conditions_overall(facts) == []
+
+
+def test_compare_sees_one_bit(oracle):
+    """compare() is the campaign's only judge: a mesh against itself passes, and one flipped bit of a coordinate, a swapped cell,
+    a counter off by one or one flipped bit of a normal each fail."""
+    import copy
+    import fuzz_campaign as fz
+    import pytest
+    r = next(r for r in _recipes(200, kind="border") if r["normals"] and r["kw"]["project"])
+    want = fz.expected(oracle, r)
+    assert len(want["mesh"].points) > 3 and len(want["mesh"].cells) > 1
+
+    def got():
+        m = want["mesh"]
+        return {"mesh": copy.deepcopy(m), "normals": want["normals"].copy(), "counters": {k: m.info[k] for k in fz.COUNTERS}}
+    fz.compare(got(), want)
+    g = got()
+    g["mesh"].points.view(np.uint32)[2, 1] ^= 1
+    with pytest.raises(AssertionError):
+        fz.compare(g, want)
+    g = got()
+    g["mesh"].cells[[0, 1]] = g["mesh"].cells[[1, 0]]
+    with pytest.raises(AssertionError):
+        fz.compare(g, want)
+    g = got()
+    g["counters"]["proj_iterations"] += 1
+    with pytest.raises(AssertionError):
+        fz.compare(g, want)
+    g = got()
+    finite = np.argwhere(np.isfinite(g["normals"]))
+    assert len(finite)
+    g["normals"].view(np.uint32)[tuple(finite[0])] ^= 1
+    with pytest.raises(AssertionError):
+        fz.compare(g, want)
+    g = got()
+    g["normals"] = None
+    with pytest.raises(AssertionError):
+        fz.compare(g, want)
