@@ -163,7 +163,8 @@ typedef struct {
   float ms_scan;            /* 0: the scans run inside the count kernel since ABI 4 (field kept for layout) */
   float ms_emit_points;     /* vertex scatter: AddVertex without the projection (txx:256-276) */
   float ms_project;         /* vertex projection (txx:439-474); with cuberille_set_point_normals on, the normals pass behind it too */
-  float ms_emit_cells;      /* quad / triangle scatter incl. the diagonal split (txx:278-332) */
+  float ms_emit_cells;      /* quad / triangle scatter incl. the diagonal split (txx:278-332); with cuberille_set_cell_pixels on, the
+                               cell-pixel pass behind it too */
   float ms_total;           /* ms_pass + the emit phase (points, projection, cells).  When cuberille_emit_points started the
                                vertex phase ahead of cuberille_emit, the two phases are timed as intervals of their own and
                                added: the device's wait for the host's all-gather in between is in neither.  Inside
@@ -492,6 +493,44 @@ int cuberille_normals_download(cuberille_ctx *ctx, float *normals);
 /* Test aid (new symbol): the bytes of device memory the context's workspace holds at this moment -- the capacities of all its
  * buffers added up (what cuberille_warm_up and the extractions reserved and kept). */
 int cuberille_debug_device_bytes(cuberille_ctx *ctx, size_t *bytes);
+/* Cell pixels (new symbols within ABI 13, no struct changed).  Which voxel a face belongs to: behind every cell it adds the
+ * reference keeps a commented-out mesh->SetCellData( id, (OutputPixelType)0 ) (txx:314, 321, 330), and the maintained successor of
+ * the filter offers the pixel there as a switch.  With the setting on, every later extraction also leaves one value per cell, one
+ * definition for every route, pixel type and source view: quad (u, f) -- it exists when u is inside and its neighbour across face f
+ * is not; quads are in voxel raster order, then f ascending -- carries I(u), the pixel of its INSIDE voxel u in the image's own
+ * pixel type, copied byte for byte (a NaN keeps its payload, -0.0 stays -0.0, an 8-byte integer no double holds stays exact).  With
+ * generate_triangles cells 2k and 2k + 1 both carry the pixel of quad k.  It does not depend on the projection, its branch, the
+ * interpolator or the gradient.  With a source view I is the view's frame BEFORE any band mapping: the padded image
+ * (cuberille_set_border; a quad whose inside voxel lies on the ring -- possible when the constant is not below the iso value --
+ * carries the constant), the box (cuberille_set_region), and with cuberille_set_band the caller's RAW pixel, not `inside` /
+ * `outside`.  That is deliberate: the mesh is that of the thresholded image B, but B's cell data would be one constant and say
+ * nothing, while the raw pixel says which label -- one extraction of the band [1, 255] gives the outer surface of all labels, to be
+ * split per label afterwards.
+ * The values are written by a pass of its own behind the cell pass, one lane per quad and one load each; with stage timing on its
+ * time is part of ms_emit_cells.  The buffer is one more row of the workspace, one pixel per cell, sized where the cells are
+ * (cuberille_warm_up runs its internal extraction with the setting as it stands: on, the pass's code is loaded and the row exists;
+ * off, nothing is reserved for it).  Points, cells and counters are the bytes of the same extraction with the setting off.
+ * With the setting on cuberille_emit READS THE VOXELS: a caller of cuberille_count + cuberille_emit keeps the voxel buffer it
+ * counted valid and unchanged until cuberille_emit returns.
+ * cuberille_set_cell_pixels: on != 0 / 0 (the default: nothing allocated, nothing launched, every result as before the symbol
+ *   existed; turning it off also frees the row and the cell pixels of the last mesh).  Not between cuberille_step_begin and _end.
+ * cuberille_cell_pixels_device: *d_pixels = n_cells values of the last extraction in cell order, in the library's buffer (valid
+ *   until the next call on the context; null for an empty mesh), *pixel_type (may be null) their CUBERILLE_PIX_* type.
+ * cuberille_cell_pixels_download: the same into host memory; CUBERILLE_ERR_ARGUMENT when capacity_bytes is below n_cells pixels.
+ *   Both: CUBERILLE_ERR_STATE with a message when the last extraction ran with the setting off (or there is no mesh).  The
+ *   point-id offset of cuberille_emit does not touch them.
+ * cuberille_mesh_write_vtk on a context that holds cell pixels appends, behind the polygons and behind the POINT_DATA / NORMALS
+ *   block where there is one, "CELL_DATA n" / "SCALARS pixel <vtk type> 1" / "LOOKUP_TABLE default" and one value per line
+ *   (integers in decimal, float32 as %.9g, float64 as %.17g; the 8-byte integers as vtktypeint64 / vtktypeuint64); with the
+ *   setting off the file is byte for byte what it was.
+ * Offered: cuberille_extract_host (chunked upload included), cuberille_extract_device, cuberille_extract_stream, cuberille_count +
+ * cuberille_emit_points / cuberille_emit on a whole volume; quads and triangles, the projection on or off, every branch, both
+ * interpolators, a held or recursive-Gaussian gradient, each source view where that view is offered.  Refused with
+ * CUBERILLE_ERR_ARGUMENT and a message that says "cell pixels", the context left usable: a slab that is not the whole volume; the
+ * cuberille_step_* calls; cuberille_group_extract_host with a member that has the setting on. */
+int cuberille_set_cell_pixels(cuberille_ctx *ctx, int on);
+int cuberille_cell_pixels_device(cuberille_ctx *ctx, const void **d_pixels, int *pixel_type);
+int cuberille_cell_pixels_download(cuberille_ctx *ctx, void *out, size_t capacity_bytes);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

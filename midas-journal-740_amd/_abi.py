@@ -37,6 +37,7 @@ EXPORTS = [
     "cuberille_group_mesh_host", "cuberille_group_release_host_mesh", "cuberille_group_mesh_write_vtk",
     "cuberille_group_debug_fail_alloc",
     "cuberille_set_point_normals", "cuberille_normals_device", "cuberille_normals_download", "cuberille_debug_device_bytes",
+    "cuberille_set_cell_pixels", "cuberille_cell_pixels_device", "cuberille_cell_pixels_download",
 ]
 GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
@@ -147,6 +148,9 @@ def lib():
     L.cuberille_normals_device.argtypes = [vp, C.POINTER(vp)]
     L.cuberille_normals_download.argtypes = [vp, vp]
     L.cuberille_debug_device_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.cuberille_set_cell_pixels.argtypes = [vp, C.c_int]
+    L.cuberille_cell_pixels_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.cuberille_cell_pixels_download.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

@@ -25,6 +25,8 @@
 namespace cuberille {
 // (cuberille_vtk.cpp, host code: the NORMALS block of cuberille_mesh_write_vtk)
 int append_vtk_normals(const char *path, const float *normals, uint64_t n_points, int n_threads);
+// (the CELL_DATA block: n_cells values of pixel_type, behind everything else in the file)
+int append_vtk_cell_pixels(const char *path, const void *pixels, int pixel_type, uint64_t n_cells);
 }
 using namespace cuberille;
 
@@ -132,6 +134,10 @@ struct cuberille_ctx {
   DevBuf normals;                        // ... 3 floats per point of `points`, same order (reserved and written only while the setting is on)
   bool countNormals = false;             // ... the setting as the running count/emit pair found it
   bool haveNormals = false;              // ... and whether the last mesh came with its normals
+  bool cellPixels = false;               // cuberille_set_cell_pixels: every later extraction also leaves the pixel of every cell's voxel ...
+  DevBuf cellPix;                        // ... one value of the pixel type per cell of `cells`, same order (reserved and written only while the setting is on)
+  bool countCellPixels = false;          // ... the setting as the running count/emit pair found it
+  bool haveCellPixels = false;           // ... and whether the last mesh came with them
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
   Totals *hostTotals = nullptr;          // pinned
@@ -198,7 +204,7 @@ hipError_t mark(cuberille_ctx *c, Mark m);
 std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
   return {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
           &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
-          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals};
+          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals, &c->cellPix};
 }
 
 int fail(cuberille_ctx *c, int code, const std::string &msg) {
@@ -398,6 +404,10 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
     if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) are the central-difference gradient: not offered with CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN");
   }
+  // cuberille_set_cell_pixels: the pixel of each cell's voxel in ONE context's whole volume (a slab that is not the whole volume:
+  // count_prepare)
+  if (c->cellPixels && route == ROUTE_STEP)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to one context's whole volume: not offered with the cuberille_step_* calls");
   // the iso value is an InputPixelType in the reference (h:180-181)
   if (!converts(img->pixel_type, prm->iso_value))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
@@ -806,12 +816,13 @@ struct Want { size_t bytes, cover; };
 struct EmitSizes {
   Want points, cells;                 // required
   Want normals;                       // cuberille_set_point_normals: required while the setting is on (0 bytes: off)
+  Want cellPix;                       // cuberille_set_cell_pixels: likewise, one pixel per cell
   Want headV, headQ;                  // optional (4 B per 64 outputs)
   size_t cmap, escCap;                // optional; THIN_HALO: entries of the escape list (required there)
 };
 
 EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u64 nV, u64 totQ, u64 nQ, size_t planeCorners,
-                     size_t nwords, bool normals) {
+                     size_t nwords, bool normals, size_t cellPixelBytes = 0) {
   const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
   const size_t quad = (triangles ? 6 : 4) * sizeof(u64);
   const bool heads = nwords < 0xffffffffULL && !t.no_heads;
@@ -819,6 +830,9 @@ EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u
   s.points = {(size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float), (size_t)(nextV + planeCorners) * 3 * sizeof(float)};
   s.cells = {(size_t)(nQ ? nQ : 1) * quad, (size_t)nextQ * quad};
   s.normals = normals && nV ? Want{(size_t)nV * 3 * sizeof(float), (size_t)nextV * 3 * sizeof(float)} : Want{0, 0};   // (a whole volume: no plane behind them)
+  // (cellPixelBytes: the size of a pixel, 0 with the setting off; a quad is one cell or two)
+  const size_t perQuad = (triangles ? 2 : 1) * cellPixelBytes;
+  s.cellPix = perQuad && nQ ? Want{(size_t)nQ * perQuad, (size_t)nextQ * perQuad} : Want{0, 0};
   s.headV = heads ? Want{(size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.headQ = heads ? Want{(size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.cmap = nV < 0xffffffffULL ? cmap_bytes(g, t) : 0;   // (more than 2^32 vertices: the cell kernel recomputes ids instead)
@@ -842,6 +856,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->pointsEmitted = false;
   c->haveMesh = false;
   c->haveNormals = false;
+  c->haveCellPixels = false;
   c->hostMeshValid = false;
   c->stepMode = 0;
   c->voxelHaloEvent = nullptr;
@@ -870,6 +885,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
       return fail(c, CUBERILLE_ERR_ARGUMENT, "slab ranges are inconsistent with the buffer");
     if (c->pointNormals && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
       return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to a whole volume: not offered on slabs");
+    if (c->cellPixels && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to a whole volume: not offered on slabs");
     // the owned range needs 2 slices below (ids of corners created one slice down depend on the
     // slice below that) and 1 above; with the projection on, as far as a walk can reach (both unless the
     // volume ends there)
@@ -936,6 +953,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
   c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
   c->countNormals = c->pointNormals;
+  c->countCellPixels = c->cellPixels;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -1172,10 +1190,12 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   const u32 nVW = dyn ? coverVW : c->tot.nVertexWords;
   // room behind this rank's points for the positions of a plane of the rank below's vertices (quirk Q1 across slabs)
   const size_t planeCorners = (c->slabMode || c->g.extAlias) ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) : 0;
-  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, c->countNormals);
+  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, c->countNormals,
+                                  c->countCellPixels ? pixel_size(c->pixel_type) : 0);
   HIP_TRY(c, c->points.reserve_covering(sz.points.bytes, sz.points.cover));
   HIP_TRY(c, c->cells.reserve_covering(sz.cells.bytes, sz.cells.cover));
   if (sz.normals.bytes) HIP_TRY(c, c->normals.reserve_covering(sz.normals.bytes, sz.normals.cover));
+  if (sz.cellPix.bytes) HIP_TRY(c, c->cellPix.reserve_covering(sz.cellPix.bytes, sz.cellPix.cover));
   Workspace &w = c->w;
   w.points = (float *)c->points.p;
   w.cells = (u64 *)c->cells.p;
@@ -1351,6 +1371,7 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->stepMode = 0;
   c->haveMesh = true;
   c->haveNormals = c->countNormals;
+  c->haveCellPixels = c->countCellPixels;
   c->counted = false;                        // the workspace now belongs to this mesh
   if (res) *res = r;
   return CUBERILLE_OK;
@@ -1459,6 +1480,9 @@ int cuberille_emit(cuberille_ctx *c, uint64_t point_id_offset, cuberille_result 
     HIP_TRY(c, hipMemcpyAsync(w.points + 3 * nV, c->extPts, planeCorners * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, launch_emit_cells(w, c->g, c->prm.triangles, c->prm.q1, point_id_offset, nQ, needPlane ? c->extIds : nullptr,
                                nullptr, 0, 0, 0, s));
+  // cuberille_set_cell_pixels: one more pass over the quads reads each one's voxel (with stage timing on, part of ms_emit_cells)
+  if (c->countCellPixels)
+    HIP_TRY(c, launch_cell_pixels(c->pixel_type, w, c->g, c->prm.triangles, c->cellPix.p, nQ, 0, s));
   HIP_TRY(c, mark(c, END));
   HIP_TRY(c, hipMemcpyAsync(c->hostTotals, w.totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -1606,6 +1630,9 @@ int step_end_impl(cuberille_ctx *c, const void *dev_rows, int n_ranks, int rank,
     const u64 nQ = blind ? c->histQ + c->histQ / 4 + 4096 : c->tot.totQ - c->tot.Q0;
     HIP_TRY(c, launch_emit_cells(c->w, c->g, c->prm.triangles, c->prm.q1, base, nQ, nullptr, (const Totals *)dev_rows, n_ranks, rank,
                                  blind ? 1 : 0, s));
+    // (cuberille_set_cell_pixels: the one-call routes alone come here with it, the context their only rank -- the step calls refuse)
+    if (c->countCellPixels)
+      HIP_TRY(c, launch_cell_pixels(c->pixel_type, c->w, c->g, c->prm.triangles, c->cellPix.p, nQ, blind ? 1 : 0, s));
   }
   HIP_TRY(c, mark(c, END));
   {
@@ -1749,7 +1776,13 @@ struct StagePool {
       threads_.emplace_back([this, t, total, chunk, move] {
         for (size_t i = 0; i < done_.size(); i++) {
           while (released_.load(std::memory_order_acquire) < (long long)i) {
-            if (abort_.load(std::memory_order_relaxed)) return;
+            // (the destructor follows the last release at once: a thread that read released_ just before that release and
+            //  abort_ just after the destructor's store must look again, or it leaves without moving its share of the last
+            //  chunk -- the destination then keeps whatever the memory held)
+            if (abort_.load(std::memory_order_acquire)) {
+              if (released_.load(std::memory_order_acquire) >= (long long)i) break;
+              return;
+            }
             std::this_thread::yield();
           }
           const size_t cb = total - i * chunk < chunk ? total - i * chunk : chunk;
@@ -1966,6 +1999,7 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     c->haveHistory = false;                  // (sizes of a toy volume: the first real extraction reads its own counts)
     c->haveMesh = false;
     c->haveNormals = false;
+    c->haveCellPixels = false;
     c->counted = false;
     c->warm = true;
   }
@@ -2214,6 +2248,49 @@ int cuberille_normals_download(cuberille_ctx *c, float *normals) {
   return download_pipelined(c, normals, c->normals.p, (size_t)c->res.n_points * 3 * sizeof(float));
 }
 
+int cuberille_set_cell_pixels(cuberille_ctx *c, int on) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  c->cellPixels = on != 0;
+  if (!on && c->cellPix.p) {
+    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its cell pixels go)
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
+    c->cellPix.release();
+    c->haveCellPixels = false;
+    c->countCellPixels = false;
+  }
+  return CUBERILLE_OK;
+}
+
+static int cell_pixels_preconditions(cuberille_ctx *c) {
+  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
+  if (!c->haveCellPixels)
+    return fail(c, CUBERILLE_ERR_STATE, "no cell pixels: the last extraction ran with the setting off (cuberille_set_cell_pixels)");
+  return CUBERILLE_OK;
+}
+
+int cuberille_cell_pixels_device(cuberille_ctx *c, const void **d_pixels, int *pixel_type) {
+  if (!c || !d_pixels) return CUBERILLE_ERR_ARGUMENT;
+  *d_pixels = nullptr;
+  if (const int rc = cell_pixels_preconditions(c)) return rc;
+  *d_pixels = c->res.n_cells ? c->cellPix.p : nullptr;   // (a row sized by an earlier mesh is no value of an empty one)
+  if (pixel_type) *pixel_type = c->pixel_type;
+  return CUBERILLE_OK;
+}
+
+int cuberille_cell_pixels_download(cuberille_ctx *c, void *out, size_t capacity_bytes) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (const int rc = cell_pixels_preconditions(c)) return rc;
+  const size_t bytes = (size_t)c->res.n_cells * pixel_size(c->pixel_type);
+  if (capacity_bytes < bytes)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "the cell pixels take " + std::to_string(bytes) + " bytes, the buffer holds " + std::to_string(capacity_bytes));
+  if (!bytes) return CUBERILLE_OK;
+  if (!out) return fail(c, CUBERILLE_ERR_ARGUMENT, "null output pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  return download_pipelined(c, out, c->cellPix.p, bytes);
+}
+
 int cuberille_debug_device_bytes(cuberille_ctx *c, size_t *bytes) {
   if (!c || !bytes) return CUBERILLE_ERR_ARGUMENT;
   *bytes = 0;
@@ -2353,6 +2430,13 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
     const int dl = cuberille_normals_download(c, nrm.data());
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_normals(path, nrm.data(), r.n_points, n_threads);
+  }
+  if (wr == CUBERILLE_OK && c->haveCellPixels) {
+    // a context that holds cell pixels: CELL_DATA n / SCALARS pixel <type> 1 behind everything else (setting off: the file as it was)
+    std::vector<char> pix((size_t)r.n_cells * pixel_size(c->pixel_type));
+    const int dl = cuberille_cell_pixels_download(c, pix.data(), pix.size());
+    if (dl != CUBERILLE_OK) return dl;
+    wr = cuberille::append_vtk_cell_pixels(path, pix.data(), c->pixel_type, r.n_cells);
   }
   if (wr != CUBERILLE_OK) return fail(c, wr, std::string("cannot write ") + path);
   return CUBERILLE_OK;
@@ -2591,6 +2675,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
                                               "it belongs to a whole volume, not offered in a group");
     if (c->pointNormals)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has point normals set (cuberille_set_point_normals): "
+                                              "they belong to one context's whole volume, not offered in a group");
+    if (c->cellPixels)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has cell pixels set (cuberille_set_cell_pixels): "
                                               "they belong to one context's whole volume, not offered in a group");
   }
   {

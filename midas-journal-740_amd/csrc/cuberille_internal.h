@@ -258,6 +258,10 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
 // Workspace so that no argument block of another kernel moves
 hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *normals, u64 nPoints,
                                 int dyn, hipStream_t s);
+// cuberille_set_cell_pixels: the pixel of the inside voxel of quads [0, nQ) of the owned range, in the pixel type, one per cell
+// in cell order (two per quad with triangles), into `out` -- a buffer of its own beside the Workspace, as the normals' is
+hipError_t launch_cell_pixels(int pixel_type, const Workspace &w, const Grid &g, int triangles, void *out, u64 nQ, int dyn,
+                              hipStream_t s);
 
 }  // namespace cuberille
 #endif

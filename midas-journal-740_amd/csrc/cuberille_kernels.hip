@@ -3977,6 +3977,48 @@ __global__ __launch_bounds__(256) void k_point_normals(const T *__restrict__ vox
 }
 
 // ---------------------------------------------------------------------------------------------
+// K3c: cell pixels (cuberille_set_cell_pixels).  What the reference's commented-out mesh->SetCellData( id, ... ) behind every
+// cell it adds (txx:314, 321, 330) would carry: quad (u, f) -- inside voxel u, face f, numbered as DESIGN.md section 2 item 1
+// says -- gets I(u), the pixel of its inside voxel in the image's own type T, moved as bits (a NaN keeps its payload, -0.0
+// stays -0.0, an 8-byte integer no double holds stays exact).  TRI: cells 2q and 2q + 1 both carry quad q's pixel, whichever
+// diagonal split them.
+// One lane per quad in k_emit_cells' launch shape: the 64 lanes of a wave are 64 consecutive quads and search their words
+// together (locate_quad: the head table, or the per-lane search where the table was dropped), then each lane does ONE load at
+// its voxel -- quads follow raster order, so the lanes of a wave read from a few rows -- and one store at out[q] (TRI: the
+// pair as one store of 2 sizeof(T) <= 16 bytes).  No LDS, no atomics, nothing written but that.
+// I is the view's FRAME before any band mapping: VIEW_WHOLE reads the buffer (it serves cuberille_set_band too: the caller's
+// raw pixel, never Sampler::map), VIEW_BORDER goes through at_buffer (a ring voxel yields the constant, nothing outside the
+// caller's buffer is addressed), VIEW_REGION through the buffer's pitches.  A whole volume (the host layer offers nothing
+// else with the setting): z of locate_quad is the buffer's slice.  dyn: the count and the go flag as k_emit_cells reads them.
+// ---------------------------------------------------------------------------------------------
+template <class T> struct alignas(2 * sizeof(T)) PixelPair { T a, b; };
+
+template <class T, int VIEW, bool TRI>
+__global__ __launch_bounds__(256) void k_cell_pixels(const T *__restrict__ vox, EmitArgs a, Grid g, size_t nwords, u64 nQ,
+                                                     T *__restrict__ out, double padD, long long padI, long long rowPitch,
+                                                     long long slicePitch) {
+  const int lane = threadIdx.x & 63;
+  const u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 waveFirst = q - lane;
+  if (a.dyn) {
+    if (!a.tot->go) return;
+    nQ = a.tot->totQ - a.tot->Q0;
+  }
+  if (waveFirst >= nQ) return;                   // wave-uniform
+  const u64 Q0 = a.tot->Q0;
+  int x, y, z = 0, f;
+  if (!locate_quad(a, g, nwords, q, q < nQ, Q0, x, y, z, f)) return;
+  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
+  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
+  T v;
+  if constexpr (VIEW == VIEW_BORDER) v = s.at_buffer(x, y, z);
+  else v = s.at(x, y, z);
+  if constexpr (TRI) reinterpret_cast<PixelPair<T> *>(out)[q] = PixelPair<T>{v, v};
+  else out[q] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <class F>
@@ -4699,6 +4741,36 @@ hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &
     };
     if (v.kind == VIEW_BAND) launch(std::integral_constant<int, VIEW_BAND>());
     else if (v.kind == VIEW_BORDER) launch(std::integral_constant<int, VIEW_BORDER>());
+    else if (v.kind == VIEW_REGION) launch(std::integral_constant<int, VIEW_REGION>());
+    else launch(std::integral_constant<int, VIEW_WHOLE>());
+    return hipGetLastError();
+  });
+}
+
+// The cell pixels of quads [0, nQ) of the owned range into `out` (K3c: one value per quad, two with triangles), behind the
+// cell pass on `s` -- it needs what that pass needs of the workspace (bits, prefix sums, the head table where there is one)
+// and the voxels.  dyn: nQ is what the launch is sized for, as in launch_emit_cells.  A band takes the VIEW_WHOLE form: the
+// caller's raw pixel is what says which label.
+hipError_t launch_cell_pixels(int pixel_type, const Workspace &w, const Grid &g, int triangles, void *out, u64 nQ, int dyn,
+                              hipStream_t s) {
+  if (!nQ) return hipSuccess;
+  const size_t nwords = (size_t)(g.oz1 - g.cz0) * g.ny * g.W;
+  EmitArgs a = emit_args(w, g, 0, 0);
+  a.dyn = dyn;
+  const dim3 grid(grid_for(nQ, 256, 0)), block(256);
+  return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+    typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+    const View &v = w.view;
+    auto launch = [&](auto viewTag) {
+      constexpr int VIEW = decltype(viewTag)::value;
+      if (triangles)
+        hipLaunchKernelGGL((k_cell_pixels<T, VIEW, true>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out,
+                           v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
+      else
+        hipLaunchKernelGGL((k_cell_pixels<T, VIEW, false>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out,
+                           v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
+    };
+    if (v.kind == VIEW_BORDER) launch(std::integral_constant<int, VIEW_BORDER>());
     else if (v.kind == VIEW_REGION) launch(std::integral_constant<int, VIEW_REGION>());
     else launch(std::integral_constant<int, VIEW_WHOLE>());
     return hipGetLastError();

@@ -117,4 +117,58 @@ int append_vtk_normals(const char *path, const float *normals, uint64_t n_points
   ok = (std::fclose(f) == 0) && ok;
   return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
 }
+
+// ... and on one that holds cell pixels (cuberille_set_cell_pixels): the cell attribute block, LAST in the file (behind the
+// normals where there are any, so that a file with normals alone stays what it was) -- "CELL_DATA n", "SCALARS pixel <type> 1",
+// "LOOKUP_TABLE default", then one value per line: integers in decimal, float32 / float64 with the digits that read back to the
+// same value (%.9g / %.17g).
+int append_vtk_cell_pixels(const char *path, const void *pixels, int pixel_type, uint64_t n_cells) {
+  if (!path || (n_cells && !pixels)) return CUBERILLE_ERR_ARGUMENT;
+  const char *name = nullptr;
+  switch (pixel_type) {
+    case CUBERILLE_PIX_U8: name = "unsigned_char"; break;
+    case CUBERILLE_PIX_I8: name = "char"; break;
+    case CUBERILLE_PIX_U16: name = "unsigned_short"; break;
+    case CUBERILLE_PIX_I16: name = "short"; break;
+    case CUBERILLE_PIX_U32: name = "unsigned_int"; break;
+    case CUBERILLE_PIX_I32: name = "int"; break;
+    case CUBERILLE_PIX_F32: name = "float"; break;
+    case CUBERILLE_PIX_F64: name = "double"; break;
+    case CUBERILLE_PIX_I64: name = "vtktypeint64"; break;
+    case CUBERILLE_PIX_U64: name = "vtktypeuint64"; break;
+    default: return CUBERILLE_ERR_ARGUMENT;
+  }
+  std::FILE *f = std::fopen(path, "ab");
+  if (!f) return CUBERILLE_ERR_ARGUMENT;
+  bool ok = std::fprintf(f, "CELL_DATA %llu\nSCALARS pixel %s 1\nLOOKUP_TABLE default\n", (unsigned long long)n_cells, name) > 0;
+  auto value = [&](char *p, size_t i) -> char * {
+    switch (pixel_type) {
+      case CUBERILLE_PIX_U8: return put_u64(p, ((const uint8_t *)pixels)[i]);
+      case CUBERILLE_PIX_I8: return std::to_chars(p, p + 24, (long long)((const int8_t *)pixels)[i]).ptr;
+      case CUBERILLE_PIX_U16: return put_u64(p, ((const uint16_t *)pixels)[i]);
+      case CUBERILLE_PIX_I16: return std::to_chars(p, p + 24, (long long)((const int16_t *)pixels)[i]).ptr;
+      case CUBERILLE_PIX_U32: return put_u64(p, ((const uint32_t *)pixels)[i]);
+      case CUBERILLE_PIX_I32: return std::to_chars(p, p + 24, (long long)((const int32_t *)pixels)[i]).ptr;
+      case CUBERILLE_PIX_F32: return put_float(p, ((const float *)pixels)[i]);
+      case CUBERILLE_PIX_F64: return p + std::snprintf(p, 40, "%.17g", ((const double *)pixels)[i]);
+      case CUBERILLE_PIX_I64: return std::to_chars(p, p + 24, (long long)((const int64_t *)pixels)[i]).ptr;
+      default: return put_u64(p, ((const uint64_t *)pixels)[i]);
+    }
+  };
+  std::string buf;
+  const size_t chunk = 1u << 16;
+  for (size_t i0 = 0; ok && i0 < n_cells; i0 += chunk) {
+    const size_t i1 = std::min<size_t>(n_cells, i0 + chunk);
+    buf.resize((i1 - i0) * 41 + 16);
+    char *p = &buf[0];
+    for (size_t i = i0; i < i1; i++) {
+      p = value(p, i);
+      *p++ = '\n';
+    }
+    const size_t n = (size_t)(p - &buf[0]);
+    ok = std::fwrite(buf.data(), 1, n, f) == n;
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
+}
 }  // namespace cuberille

@@ -495,6 +495,31 @@ class Extractor:
         _abi.check(self._ctx, self._lib.cuberille_normals_device(self._ctx, C.byref(p)))
         return p.value
 
+    def set_cell_pixels(self, on=True):
+        """Cell pixels (cuberille_set_cell_pixels): every later extraction also leaves, for every cell, the pixel of the
+        inside voxel of the cell's quad, in the volume's own dtype -- the value the reference's commented-out SetCellData
+        (txx:314, 321, 330) would carry.  Both triangles of a quad carry the quad's pixel.  With a band it is the caller's raw
+        pixel (which label), with a border the padded image's, with a region the box's.  Points, cells and counters are
+        unchanged.  Slabs, steps and groups are refused at the extraction.  Off (the default) frees the buffer."""
+        _abi.check(self._ctx, self._lib.cuberille_set_cell_pixels(self._ctx, 1 if on else 0))
+
+    def cell_pixels_device(self):
+        """(device pointer, CUBERILLE_PIX_* type) of the cell pixels of the last extraction, one value per cell in the
+        library's buffer (cuberille_cell_pixels_device; the pointer is None for an empty mesh)."""
+        p, t = C.c_void_p(), C.c_int(-1)
+        _abi.check(self._ctx, self._lib.cuberille_cell_pixels_device(self._ctx, C.byref(p), C.byref(t)))
+        return p.value, int(t.value)
+
+    def download_cell_pixels(self):
+        """The cell pixels of the last extraction as a numpy array of the volume's dtype and length n_cells, in cell order
+        (cuberille_cell_pixels_download); CuberilleError ERR_STATE when that extraction ran with the setting off."""
+        _, t = self.cell_pixels_device()
+        dtype = np.dtype(PIXEL_DTYPES[t])
+        n = int(self.result.n_cells) if self.result is not None else 0
+        out = np.empty(n, dtype=dtype)
+        _abi.check(self._ctx, self._lib.cuberille_cell_pixels_download(self._ctx, C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
     def device_bytes(self):
         """Bytes of device memory the context's workspace holds at this moment (cuberille_debug_device_bytes)."""
         n = C.c_size_t()
@@ -695,6 +720,11 @@ class ExtractorGroup:
         refusal -- they belong to one context's whole volume."""
         self._on_every_member(self._lib.cuberille_set_point_normals, 1 if on else 0)
 
+    def set_cell_pixels(self, on=True):
+        """Cell pixels (Extractor.set_cell_pixels) on every member: the group's extraction then raises the library's
+        refusal -- they belong to one context's whole volume."""
+        self._on_every_member(self._lib.cuberille_set_cell_pixels, 1 if on else 0)
+
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
         (slab -1: every slab's; n < 0: off)."""
@@ -758,12 +788,14 @@ class CuberilleImageToMeshFilter:
 
     # The view settings that several devices do not offer: (attribute, its "off", the setting by name, why)
     _normals = False       # SetGeneratePointNormals: off (class level for the same reason)
+    _cell_pixels_on = False   # SetSavePixelAsCellData: off (likewise)
 
     _NOT_IN_A_GROUP = (
         ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
         ("_region", None, "a region (SetExtractionRegion / cuberille_set_region)", "a box belongs to one context's whole volume"),
         ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"),
-        ("_normals", False, "point normals (SetGeneratePointNormals / cuberille_set_point_normals)", "they belong to one context's whole volume"))
+        ("_normals", False, "point normals (SetGeneratePointNormals / cuberille_set_point_normals)", "they belong to one context's whole volume"),
+        ("_cell_pixels_on", False, "cell pixels (SetSavePixelAsCellData / cuberille_set_cell_pixels)", "they belong to one context's whole volume"))
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -794,6 +826,8 @@ class CuberilleImageToMeshFilter:
         self._band_values = (1, 0)                # SetBandValues: NumericTraits<InputPixelType>::One / Zero
         self._normals = False                     # SetGeneratePointNormals: off
         self._point_normals = None                # GetPointNormals(): (n, 3) float32 of the last Update(), or None
+        self._cell_pixels_on = False              # SetSavePixelAsCellData: off
+        self._cell_pixels = None                  # GetCellPixels(): one pixel per cell of the last Update(), or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -1021,6 +1055,25 @@ class CuberilleImageToMeshFilter:
         """(n, 3) float32 in point-id order, filled by the last Update() with the switch on; None with it off."""
         return self._point_normals
 
+    def SetSavePixelAsCellData(self, b):
+        """The switch of the filter's maintained successor; the reference reserves the place with a commented-out
+        mesh->SetCellData( id, ... ) behind every cell (txx:314, 321, 330).  On: Update() also fills GetCellPixels() with
+        the pixel of each cell's inside voxel (cuberille_set_cell_pixels).  Default off."""
+        self._cell_pixels_on = bool(b)
+
+    def GetSavePixelAsCellData(self):
+        return self._cell_pixels_on
+
+    def SavePixelAsCellDataOn(self):
+        self.SetSavePixelAsCellData(True)
+
+    def SavePixelAsCellDataOff(self):
+        self.SetSavePixelAsCellData(False)
+
+    def GetCellPixels(self):
+        """One value of the input's dtype per cell id, filled by the last Update() with the switch on; None with it off."""
+        return self._cell_pixels
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -1049,6 +1102,7 @@ class CuberilleImageToMeshFilter:
             if self._group is None:
                 self._group = ExtractorGroup(self._devices)
             self._point_normals = None
+            self._cell_pixels = None
             self.last_result = self._group.extract_host(vol, prm)
             self._output = self._group.download()
             self.last_number_of_slabs = len(self._group.plan(self._group_desc(vol), prm))
@@ -1069,10 +1123,14 @@ class CuberilleImageToMeshFilter:
             self._extractor.clear_band()
         self._extractor.set_point_normals(self._normals)
         self._point_normals = None
+        self._extractor.set_cell_pixels(self._cell_pixels_on)
+        self._cell_pixels = None
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
         if self._normals:
             self._point_normals = self._extractor.download_normals()
+        if self._cell_pixels_on:
+            self._cell_pixels = self._extractor.download_cell_pixels()
         self.last_number_of_slabs = 1
 
     @staticmethod

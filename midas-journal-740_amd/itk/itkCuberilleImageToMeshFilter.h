@@ -287,6 +287,20 @@ public:
   itkBooleanMacro(GeneratePointNormals);
   const std::vector<float> &GetPointNormals() const { return m_PointNormals; }
 
+  /** The switch of this filter's maintained successor; the reference reserves the place with a commented-out
+   *  mesh->SetCellData( id, (OutputPixelType)0 ) behind every cell it adds (txx:314, 321, 330).  SavePixelAsCellDataOn():
+   *  Update() also fills GetCellPixels() with the pixel of the inside voxel of each cell's quad -- one InputPixelType per cell
+   *  id, both triangles of a quad carrying the quad's -- written on the device by a pass of its own behind the cell pass
+   *  (cuberille_set_cell_pixels), and the mesh's cell data with static_cast<OutputPixelType>(pixel) per cell id.  With
+   *  InsideBandOn() it is the input's RAW pixel (which label), with PadBorderOn() the padded image's, with SetExtractionRegion
+   *  the box's.  Offered on every route of a single device, the host walk included (its triangles repeat the quad's value on the
+   *  host); with SetDevices of more than one device the library refuses and Update() throws an itk::ExceptionObject that says
+   *  so.  Default off: the array is empty and the mesh has no cell-data container. */
+  itkGetMacro(SavePixelAsCellData, bool);
+  itkSetMacro(SavePixelAsCellData, bool);
+  itkBooleanMacro(SavePixelAsCellData);
+  const std::vector<InputPixelType> &GetCellPixels() const { return m_CellPixels; }
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -331,6 +345,8 @@ private:
   bool m_HasExtractionRegion;
   bool m_GeneratePointNormals;
   std::vector<float> m_PointNormals;          // GetPointNormals(): filled by Update() with the switch on, else empty
+  bool m_SavePixelAsCellData;
+  std::vector<InputPixelType> m_CellPixels;   // GetCellPixels(): filled by Update() with the switch on, else empty
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them

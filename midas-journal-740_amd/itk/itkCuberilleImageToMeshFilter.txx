@@ -501,6 +501,7 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_HasExtractionRegion = false;
   m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
   m_GeneratePointNormals = false;
+  m_SavePixelAsCellData = false;
   m_InsideBand = false;
   m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
   m_BandInside = NumericTraits<InputPixelType>::One;
@@ -769,6 +770,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
         itkExceptionMacro(<< setter << ": " << cuberille_last_error(cuberille_group_context(m_Group, i)));
       // (point normals on the members: the group's extraction refuses them likewise)
       (void)cuberille_set_point_normals(cuberille_group_context(m_Group, i), m_GeneratePointNormals ? 1 : 0);
+      (void)cuberille_set_cell_pixels(cuberille_group_context(m_Group, i), m_SavePixelAsCellData ? 1 : 0);
       }
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
@@ -790,6 +792,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< setter << ": " << cuberille_last_error(m_Context));
     if (cuberille_set_point_normals(m_Context, m_GeneratePointNormals ? 1 : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_point_normals: " << cuberille_last_error(m_Context));
+    if (cuberille_set_cell_pixels(m_Context, m_SavePixelAsCellData ? 1 : 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_cell_pixels: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
@@ -817,6 +821,14 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_normals_download(m_Context, m_PointNormals.empty() ? 0 : &m_PointNormals[0]) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_normals_download: " << cuberille_last_error(m_Context));
     }
+  m_CellPixels.clear();
+  if (m_SavePixelAsCellData)                  // (the single context: a group has refused above)
+    {
+    m_CellPixels.resize(static_cast<size_t>(res.n_cells));
+    if (cuberille_cell_pixels_download(m_Context, m_CellPixels.empty() ? 0 : &m_CellPixels[0],
+                                       m_CellPixels.size() * sizeof(InputPixelType)) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_cell_pixels_download: " << cuberille_last_error(m_Context));
+    }
   m_LastDownloadSeconds = cuberille_detail::WallSeconds() - downloadStart;
   struct FreeOnExit { void *p; ~FreeOnExit() { std::free(p); } } ownCells = {0};   // the host walk's triangles, when it makes them
 
@@ -838,6 +850,11 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       cells = static_cast<uint64_t *>(ownCells.p);
       res.n_cells *= 2;
       res.verts_per_cell = 3;
+      if (m_SavePixelAsCellData)              // the device left one pixel per quad: both of a quad's triangles carry it
+        {
+        m_CellPixels.resize(static_cast<size_t>(res.n_cells));
+        for (size_t q = m_CellPixels.size() / 2; q-- > 0;) m_CellPixels[2 * q] = m_CellPixels[2 * q + 1] = m_CellPixels[q];
+        }
       }
     }
 
@@ -853,6 +870,11 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   typedef cuberille_detail::FillTag<cuberille_detail::CastsToVectorOf<CellsContainerType, BaseCellType *>::Value> CellFillTag;
   if (res.verts_per_cell == 3) cuberille_detail::FillCells<OutputMeshType, TriangleCellType, 3>(mesh.GetPointer(), cells, res.n_cells, CellFillTag());
   else cuberille_detail::FillCells<OutputMeshType, QuadrilateralCellType, 4>(mesh.GetPointer(), cells, res.n_cells, CellFillTag());
+  // SavePixelAsCellDataOn(): what the reference's commented-out mesh->SetCellData( id, (OutputPixelType)0 ) would store (txx:314,
+  // 321, 330), with the pixel in the zero's place; off: the mesh has no cell-data container
+  mesh->SetCellData(static_cast<typename OutputMeshType::CellDataContainer *>(0));
+  for (size_t i = 0; i < m_CellPixels.size(); i++)
+    mesh->SetCellData(static_cast<typename OutputMeshType::CellIdentifier>(i), static_cast<OutputPixelType>(m_CellPixels[i]));
   m_LastMeshFillSeconds = cuberille_detail::WallSeconds() - fillStart;
   if (m_ReleaseHostMeshAfterFill)
     {

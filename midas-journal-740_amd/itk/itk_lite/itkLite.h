@@ -457,6 +457,7 @@ public:
   void InsertElement(ElementIdentifier id, const Element &e) { if (m_V.size() <= id) m_V.resize(id + 1); m_V[id] = e; }
   const Element &GetElement(ElementIdentifier id) const { return m_V[id]; }
   Element &ElementAt(ElementIdentifier id) { return m_V[id]; }
+  bool IndexExists(ElementIdentifier id) const { return id < m_V.size(); }
   void Reserve(ElementIdentifier n) { m_V.reserve(n); }
   ElementIdentifier Size() const { return m_V.size(); }
   void Initialize() { m_V.clear(); }
@@ -513,6 +514,7 @@ public:
   typedef CellInterface<CellPixelType, CellTraits> CellType;
   typedef VectorContainer<PointIdentifier, PointType> PointsContainer;
   typedef VectorContainer<CellIdentifier, CellType *> CellsContainer;
+  typedef VectorContainer<CellIdentifier, CellPixelType> CellDataContainer;
 };
 
 // itk::DefaultDynamicMeshTraits: the same names, points and cells in MapContainers
@@ -524,6 +526,7 @@ class DefaultDynamicMeshTraits
 public:
   typedef MapContainer<typename Base::PointIdentifier, typename Base::PointType> PointsContainer;
   typedef MapContainer<typename Base::CellIdentifier, typename Base::CellType *> CellsContainer;
+  typedef MapContainer<typename Base::CellIdentifier, typename Base::CellPixelType> CellDataContainer;
 };
 
 template <class TPixelType, class TCellTraits> class CellInterface {
@@ -599,6 +602,9 @@ public:
   typedef typename PointsContainer::Pointer PointsContainerPointer;
   typedef typename MeshTraits::CellsContainer CellsContainer;
   typedef typename CellsContainer::Pointer CellsContainerPointer;
+  typedef typename MeshTraits::CellPixelType CellPixelType;
+  typedef typename MeshTraits::CellDataContainer CellDataContainer;
+  typedef typename CellDataContainer::Pointer CellDataContainerPointer;
 
   PointsContainer *GetPoints() { if (m_Points.IsNull()) m_Points = PointsContainer::New(); return m_Points; }
   CellsContainer *GetCells() { if (m_Cells.IsNull()) m_Cells = CellsContainer::New(); return m_Cells; }
@@ -628,8 +634,20 @@ public:
     cell.TakeNoOwnership(m_Cells->GetElement(id));
     return true;
   }
+  // cell data as itk::Mesh keeps it: a container of its own, made by the first SetCellData (null until then, and again after
+  // Initialize()); GetCellData(id, &v) says whether the cell has a value
+  void SetCellData(CellIdentifier id, CellPixelType v) { if (m_CellData.IsNull()) m_CellData = CellDataContainer::New(); m_CellData->InsertElement(id, v); }
+  bool GetCellData(CellIdentifier id, CellPixelType *v) const {
+    if (m_CellData.IsNull() || !m_CellData->IndexExists(id)) return false;
+    *v = m_CellData->GetElement(id);
+    return true;
+  }
+  CellDataContainer *GetCellData() { return m_CellData.GetPointer(); }
+  const CellDataContainer *GetCellData() const { return m_CellData.GetPointer(); }
+  void SetCellData(CellDataContainer *data) { if (m_CellData.GetPointer() != data) { m_CellData = data; this->Modified(); } }
   virtual void Initialize() {
     ReleaseCellsMemory();
+    m_CellData = 0;
     m_CellsAllocationMethod = CellsAllocatedDynamicallyCellByCell;
     if (m_Points.IsNotNull()) m_Points->Initialize();
   }
@@ -646,6 +664,7 @@ protected:
   }
   PointsContainerPointer m_Points;
   CellsContainerPointer m_Cells;
+  CellDataContainerPointer m_CellData;
   CellsAllocationMethodType m_CellsAllocationMethod;
 };
 
