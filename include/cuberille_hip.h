@@ -164,7 +164,7 @@ typedef struct {
   float ms_emit_points;     /* vertex scatter: AddVertex without the projection (txx:256-276) */
   float ms_project;         /* vertex projection (txx:439-474); with cuberille_set_point_normals on, the normals pass behind it too */
   float ms_emit_cells;      /* quad / triangle scatter incl. the diagonal split (txx:278-332); with cuberille_set_cell_pixels on, the
-                               cell-pixel pass behind it too */
+                               cell-pixel pass behind it too, with cuberille_set_components on the component pass */
   float ms_total;           /* ms_pass + the emit phase (points, projection, cells).  When cuberille_emit_points started the
                                vertex phase ahead of cuberille_emit, the two phases are timed as intervals of their own and
                                added: the device's wait for the host's all-gather in between is in neither.  Inside
@@ -531,6 +531,45 @@ int cuberille_debug_device_bytes(cuberille_ctx *ctx, size_t *bytes);
 int cuberille_set_cell_pixels(cuberille_ctx *ctx, int on);
 int cuberille_cell_pixels_device(cuberille_ctx *ctx, const void **d_pixels, int *pixel_type);
 int cuberille_cell_pixels_download(cuberille_ctx *ctx, void *out, size_t capacity_bytes);
+/* Surface components (new symbols within ABI 13, no struct changed).  What a caller of itk::ConnectedRegionsMeshFilter does with the
+ * mesh -- find the connected surfaces, count them, keep the largest, drop the specks -- on the device, where the mesh already is.
+ * One definition for every route, pixel type and source view, quads or triangles, on the final mesh exactly as
+ * cuberille_mesh_device hands it out (n_points points, n_cells cells): two points are JOINED when one cell holds both; a COMPONENT
+ * is a class of the transitive closure; a point that no cell holds is a component of its own with zero cells; components are
+ * numbered 0 .. K-1 in the order of their smallest point index.  The point index is the position in `points`: with
+ * cuberille_emit(offset) the cells hold index + offset, the pass takes the offset off and the labels never carry it.  A lattice
+ * corner is one vertex, so voxels that touch at an edge or a corner only are one component.  The result is a pure function of the
+ * mesh; with generate_triangles the point labels and K are those of the quads and the counts exactly doubled.
+ *   point_component  uint32[n_points]  the number of the point's component
+ *   cell_component   uint32[n_cells]   the component of the cell's first point, in cell order
+ *   component_cells  uint64[K]         the cells per component
+ * A lock-free union-find over the cells, a scan that numbers the roots and a relabelling pass run behind the cell pass (and behind
+ * the cell-pixel pass where that is on); with stage timing on their time is part of ms_emit_cells.  The rows are buffers of their
+ * own, sized where the points and cells are: 16 B per point, 4 B per cell and the scan's block sums.  Points, cells and counters
+ * are the bytes of the same extraction with the setting off.  Labels are 32-bit: an extraction of 2^32 points or more is refused.
+ * cuberille_set_components: on != 0 / 0 (the default: nothing allocated, nothing launched, every result as before the symbol
+ *   existed; turning it off also frees the rows and the components of the last mesh).  Not between cuberille_step_begin and _end.
+ * cuberille_components_info: *n_components = K of the last extraction.
+ * cuberille_components_device: the three rows of the last extraction in the library's buffers (valid until the next call on the
+ *   context); each pointer may be null if not wanted; null results for an empty mesh.
+ * cuberille_components_download: the same into host memory, each pointer null if not wanted; CUBERILLE_ERR_ARGUMENT when
+ *   component_cells is wanted and capacity_components is below K.
+ *   All three: CUBERILLE_ERR_STATE with a message when the last extraction ran with the setting off (or there is no mesh).
+ * cuberille_mesh_write_vtk on a context that holds components writes "SCALARS component unsigned_int 1" / "LOOKUP_TABLE default"
+ *   twice: in POINT_DATA (behind NORMALS where there are any) the point labels, in CELL_DATA (behind the cell pixels' array where
+ *   there is one) the cell labels, creating either block where it does not yet exist; with the setting off the file is byte for
+ *   byte what it was.
+ * Offered: cuberille_extract_host, cuberille_extract_device, cuberille_extract_stream, cuberille_count + cuberille_emit_points /
+ * cuberille_emit on a whole volume; with every source view, and with point normals and cell pixels on as well (it reads the mesh,
+ * not the voxels).  Refused with CUBERILLE_ERR_ARGUMENT and a message that says "components", the context left usable: a slab that
+ * is not the whole volume; the cuberille_step_* calls; cuberille_group_extract_host with a member that has the setting on -- a
+ * component does not stop at a slab's face. */
+int cuberille_set_components(cuberille_ctx *ctx, int on);
+int cuberille_components_info(cuberille_ctx *ctx, uint64_t *n_components);
+int cuberille_components_device(cuberille_ctx *ctx, const uint32_t **d_point_component, const uint32_t **d_cell_component,
+                                const uint64_t **d_component_cells);
+int cuberille_components_download(cuberille_ctx *ctx, uint32_t *point_component, uint32_t *cell_component,
+                                  uint64_t *component_cells, size_t capacity_components);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

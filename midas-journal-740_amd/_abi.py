@@ -38,6 +38,7 @@ EXPORTS = [
     "cuberille_group_debug_fail_alloc",
     "cuberille_set_point_normals", "cuberille_normals_device", "cuberille_normals_download", "cuberille_debug_device_bytes",
     "cuberille_set_cell_pixels", "cuberille_cell_pixels_device", "cuberille_cell_pixels_download",
+    "cuberille_set_components", "cuberille_components_info", "cuberille_components_device", "cuberille_components_download",
 ]
 GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
@@ -151,6 +152,10 @@ def lib():
     L.cuberille_set_cell_pixels.argtypes = [vp, C.c_int]
     L.cuberille_cell_pixels_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int)]
     L.cuberille_cell_pixels_download.argtypes = [vp, vp, C.c_size_t]
+    L.cuberille_set_components.argtypes = [vp, C.c_int]
+    L.cuberille_components_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cuberille_components_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.cuberille_components_download.argtypes = [vp, vp, vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

@@ -27,6 +27,9 @@ namespace cuberille {
 int append_vtk_normals(const char *path, const float *normals, uint64_t n_points, int n_threads);
 // (the CELL_DATA block: n_cells values of pixel_type, behind everything else in the file)
 int append_vtk_cell_pixels(const char *path, const void *pixels, int pixel_type, uint64_t n_cells);
+// (the component array of the POINT_DATA or the CELL_DATA block; block: "POINT_DATA" / "CELL_DATA" where this array opens the
+//  block, null where the block exists)
+int append_vtk_components(const char *path, const char *block, const uint32_t *labels, uint64_t n);
 }
 using namespace cuberille;
 
@@ -138,6 +141,12 @@ struct cuberille_ctx {
   DevBuf cellPix;                        // ... one value of the pixel type per cell of `cells`, same order (reserved and written only while the setting is on)
   bool countCellPixels = false;          // ... the setting as the running count/emit pair found it
   bool haveCellPixels = false;           // ... and whether the last mesh came with them
+  bool components = false;               // cuberille_set_components: every later extraction also labels the mesh's connected surfaces ...
+  DevBuf compParent, compPoint, compCell, compCount, compScan;   // ... the rows of CompRows (reserved and written only while the setting is on)
+  u64 *hostK = nullptr;                  // ... K on its way to the host (pinned; allocated with the first extraction that has the setting on)
+  bool countComponents = false;          // ... the setting as the running count/emit pair found it
+  bool haveComponents = false;           // ... and whether the last mesh came with them
+  u64 nComponents = 0;                   // ... K of the last mesh
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
   Totals *hostTotals = nullptr;          // pinned
@@ -204,7 +213,13 @@ hipError_t mark(cuberille_ctx *c, Mark m);
 std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
   return {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
           &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
-          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals, &c->cellPix};
+          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals, &c->cellPix,
+          &c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan};
+}
+
+// cuberille_set_components: the rows as their kernels take them
+CompRows comp_rows(cuberille_ctx *c) {
+  return {(u32 *)c->compParent.p, (u32 *)c->compPoint.p, (u32 *)c->compCell.p, (u64 *)c->compCount.p, c->compScan.p};
 }
 
 int fail(cuberille_ctx *c, int code, const std::string &msg) {
@@ -408,6 +423,9 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
   // count_prepare)
   if (c->cellPixels && route == ROUTE_STEP)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to one context's whole volume: not offered with the cuberille_step_* calls");
+  // cuberille_set_components: a component does not stop at a slab's face (a slab that is not the whole volume: count_prepare)
+  if (c->components && route == ROUTE_STEP)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) belong to one context's whole volume: not offered with the cuberille_step_* calls");
   // the iso value is an InputPixelType in the reference (h:180-181)
   if (!converts(img->pixel_type, prm->iso_value))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
@@ -476,6 +494,7 @@ void cuberille_destroy(cuberille_ctx *c) {
   if (c->hostTotals) (void)hipHostFree(c->hostTotals);
   if (c->hostOcc) (void)hipHostFree(c->hostOcc);
   if (c->hostRows) (void)hipHostFree(c->hostRows);
+  if (c->hostK) (void)hipHostFree(c->hostK);
   for (int i = 0; i < 2; i++) {
     if (c->stage[i]) (void)hipHostFree(c->stage[i]);
     if (c->stageFree[i]) (void)hipEventDestroy(c->stageFree[i]);
@@ -817,12 +836,15 @@ struct EmitSizes {
   Want points, cells;                 // required
   Want normals;                       // cuberille_set_point_normals: required while the setting is on (0 bytes: off)
   Want cellPix;                       // cuberille_set_cell_pixels: likewise, one pixel per cell
+  Want compPoint, compCell, compCount, compScan;   // cuberille_set_components: likewise -- 4 B per point (twice: the forest and the
+                                      // labels), 4 B per cell, 8 B per point (K <= points), the numbering's scan row
   Want headV, headQ;                  // optional (4 B per 64 outputs)
   size_t cmap, escCap;                // optional; THIN_HALO: entries of the escape list (required there)
 };
 
 EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u64 nV, u64 totQ, u64 nQ, size_t planeCorners,
-                     size_t nwords, bool normals, size_t cellPixelBytes = 0) {
+                     size_t nwords, bool normals, size_t cellPixelBytes = 0,
+                     bool components = false) {
   const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
   const size_t quad = (triangles ? 6 : 4) * sizeof(u64);
   const bool heads = nwords < 0xffffffffULL && !t.no_heads;
@@ -833,6 +855,13 @@ EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u
   // (cellPixelBytes: the size of a pixel, 0 with the setting off; a quad is one cell or two)
   const size_t perQuad = (triangles ? 2 : 1) * cellPixelBytes;
   s.cellPix = perQuad && nQ ? Want{(size_t)nQ * perQuad, (size_t)nextQ * perQuad} : Want{0, 0};
+  // (components: the point and cell figures of `points` and `cells`, the same covering sizes; a whole volume: no plane, no ghosts)
+  const u64 nC = nQ * (triangles ? 2 : 1), nextC = nextQ * (triangles ? 2 : 1);
+  const bool comp = components && nV;
+  s.compPoint = comp ? Want{(size_t)nV * sizeof(u32), (size_t)nextV * sizeof(u32)} : Want{0, 0};
+  s.compCell = comp ? Want{(size_t)(nC ? nC : 1) * sizeof(u32), (size_t)nextC * sizeof(u32)} : Want{0, 0};
+  s.compCount = comp ? Want{(size_t)nV * sizeof(u64), (size_t)nextV * sizeof(u64)} : Want{0, 0};
+  s.compScan = components ? Want{comp_scan_bytes(nV), comp_scan_bytes(nextV)} : Want{0, 0};   // (K's slot also for an empty mesh)
   s.headV = heads ? Want{(size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.headQ = heads ? Want{(size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.cmap = nV < 0xffffffffULL ? cmap_bytes(g, t) : 0;   // (more than 2^32 vertices: the cell kernel recomputes ids instead)
@@ -857,6 +886,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->haveMesh = false;
   c->haveNormals = false;
   c->haveCellPixels = false;
+  c->haveComponents = false;
   c->hostMeshValid = false;
   c->stepMode = 0;
   c->voxelHaloEvent = nullptr;
@@ -887,6 +917,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
       return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to a whole volume: not offered on slabs");
     if (c->cellPixels && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
       return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to a whole volume: not offered on slabs");
+    if (c->components && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) belong to a whole volume: not offered on slabs");
     // the owned range needs 2 slices below (ids of corners created one slice down depend on the
     // slice below that) and 1 above; with the projection on, as far as a walk can reach (both unless the
     // volume ends there)
@@ -954,6 +986,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
   c->countNormals = c->pointNormals;
   c->countCellPixels = c->cellPixels;
+  c->countComponents = c->components;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -1191,11 +1224,24 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   // room behind this rank's points for the positions of a plane of the rank below's vertices (quirk Q1 across slabs)
   const size_t planeCorners = (c->slabMode || c->g.extAlias) ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) : 0;
   const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, c->countNormals,
-                                  c->countCellPixels ? pixel_size(c->pixel_type) : 0);
+                                  c->countCellPixels ? pixel_size(c->pixel_type) : 0, c->countComponents);
+  // (cuberille_set_components: uint32 labels, like the corner map's entries)
+  if (c->countComponents && nV >= 0xffffffffULL)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) are 32-bit labels: not offered with 2^32 points or more");
   HIP_TRY(c, c->points.reserve_covering(sz.points.bytes, sz.points.cover));
   HIP_TRY(c, c->cells.reserve_covering(sz.cells.bytes, sz.cells.cover));
   if (sz.normals.bytes) HIP_TRY(c, c->normals.reserve_covering(sz.normals.bytes, sz.normals.cover));
   if (sz.cellPix.bytes) HIP_TRY(c, c->cellPix.reserve_covering(sz.cellPix.bytes, sz.cellPix.cover));
+  if (sz.compPoint.bytes) {
+    HIP_TRY(c, c->compParent.reserve_covering(sz.compPoint.bytes, sz.compPoint.cover));
+    HIP_TRY(c, c->compPoint.reserve_covering(sz.compPoint.bytes, sz.compPoint.cover));
+    HIP_TRY(c, c->compCell.reserve_covering(sz.compCell.bytes, sz.compCell.cover));
+    HIP_TRY(c, c->compCount.reserve_covering(sz.compCount.bytes, sz.compCount.cover));
+  }
+  if (sz.compScan.bytes) {
+    HIP_TRY(c, c->compScan.reserve_covering(sz.compScan.bytes, sz.compScan.cover));
+    if (!c->hostK) HIP_TRY(c, hipHostMalloc((void **)&c->hostK, sizeof(u64), hipHostMallocDefault));
+  }
   Workspace &w = c->w;
   w.points = (float *)c->points.p;
   w.cells = (u64 *)c->cells.p;
@@ -1372,6 +1418,8 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->haveMesh = true;
   c->haveNormals = c->countNormals;
   c->haveCellPixels = c->countCellPixels;
+  c->haveComponents = c->countComponents;
+  c->nComponents = c->countComponents && c->hostK ? *c->hostK : 0;
   c->counted = false;                        // the workspace now belongs to this mesh
   if (res) *res = r;
   return CUBERILLE_OK;
@@ -1483,7 +1531,12 @@ int cuberille_emit(cuberille_ctx *c, uint64_t point_id_offset, cuberille_result 
   // cuberille_set_cell_pixels: one more pass over the quads reads each one's voxel (with stage timing on, part of ms_emit_cells)
   if (c->countCellPixels)
     HIP_TRY(c, launch_cell_pixels(c->pixel_type, w, c->g, c->prm.triangles, c->cellPix.p, nQ, 0, s));
+  // cuberille_set_components: the cells are written -- the union-find over them, the numbering, the labels (likewise part of
+  // ms_emit_cells); K rides behind the totals, ahead of the one wait
+  if (c->countComponents)
+    HIP_TRY(c, launch_components(w, comp_rows(c), c->prm.triangles, point_id_offset, nV, nQ, 0, s));
   HIP_TRY(c, mark(c, END));
+  if (c->countComponents && c->hostK && c->compScan.p) HIP_TRY(c, hipMemcpyAsync(c->hostK, c->compScan.p, sizeof(u64), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(c->hostTotals, w.totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return finish_result(c, res);
@@ -1633,8 +1686,15 @@ int step_end_impl(cuberille_ctx *c, const void *dev_rows, int n_ranks, int rank,
     // (cuberille_set_cell_pixels: the one-call routes alone come here with it, the context their only rank -- the step calls refuse)
     if (c->countCellPixels)
       HIP_TRY(c, launch_cell_pixels(c->pixel_type, c->w, c->g, c->prm.triangles, c->cellPix.p, nQ, blind ? 1 : 0, s));
+    // (cuberille_set_components: likewise; blind, the rows are sized as the points and cells were, by the gate's cover)
+    if (c->countComponents) {
+      const u64 nV = blind ? c->histV + c->histV / 4 + 4096 : c->tot.totV;
+      HIP_TRY(c, launch_components(c->w, comp_rows(c), c->prm.triangles, base, nV, nQ, blind ? 1 : 0, s));
+    }
   }
   HIP_TRY(c, mark(c, END));
+  // (K rides with the totals in the step's one wait; a flagged step leaves it unread)
+  if (c->countComponents && c->hostK && c->compScan.p) HIP_TRY(c, hipMemcpyAsync(c->hostK, c->compScan.p, sizeof(u64), hipMemcpyDeviceToHost, s));
   {
     const int rc = totals_to_host(c);
     if (rc) return rc;
@@ -2000,6 +2060,7 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     c->haveMesh = false;
     c->haveNormals = false;
     c->haveCellPixels = false;
+    c->haveComponents = false;
     c->counted = false;
     c->warm = true;
   }
@@ -2291,6 +2352,68 @@ int cuberille_cell_pixels_download(cuberille_ctx *c, void *out, size_t capacity_
   return download_pipelined(c, out, c->cellPix.p, bytes);
 }
 
+int cuberille_set_components(cuberille_ctx *c, int on) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  c->components = on != 0;
+  if (!on && (c->compScan.p || c->compParent.p)) {
+    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its components go)
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
+    for (DevBuf *b : {&c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan}) b->release();
+    c->haveComponents = false;
+    c->countComponents = false;
+    c->nComponents = 0;
+  }
+  return CUBERILLE_OK;
+}
+
+static int components_preconditions(cuberille_ctx *c) {
+  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
+  if (!c->haveComponents)
+    return fail(c, CUBERILLE_ERR_STATE, "no components: the last extraction ran with the setting off (cuberille_set_components)");
+  return CUBERILLE_OK;
+}
+
+int cuberille_components_info(cuberille_ctx *c, uint64_t *n_components) {
+  if (!c || !n_components) return CUBERILLE_ERR_ARGUMENT;
+  *n_components = 0;
+  if (const int rc = components_preconditions(c)) return rc;
+  *n_components = c->nComponents;
+  return CUBERILLE_OK;
+}
+
+int cuberille_components_device(cuberille_ctx *c, const uint32_t **d_point_component, const uint32_t **d_cell_component,
+                                const uint64_t **d_component_cells) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (d_point_component) *d_point_component = nullptr;
+  if (d_cell_component) *d_cell_component = nullptr;
+  if (d_component_cells) *d_component_cells = nullptr;
+  if (const int rc = components_preconditions(c)) return rc;
+  // (rows sized by an earlier mesh are no values of an empty one)
+  if (d_point_component && c->res.n_points) *d_point_component = (const uint32_t *)c->compPoint.p;
+  if (d_cell_component && c->res.n_cells) *d_cell_component = (const uint32_t *)c->compCell.p;
+  if (d_component_cells && c->nComponents) *d_component_cells = (const uint64_t *)c->compCount.p;
+  return CUBERILLE_OK;
+}
+
+int cuberille_components_download(cuberille_ctx *c, uint32_t *point_component, uint32_t *cell_component, uint64_t *component_cells,
+                                  size_t capacity_components) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (const int rc = components_preconditions(c)) return rc;
+  if (component_cells && capacity_components < c->nComponents)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "the mesh has " + std::to_string(c->nComponents) + " components, the buffer holds " +
+                                           std::to_string(capacity_components));
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (point_component && c->res.n_points)
+    if (const int rc = download_pipelined(c, point_component, c->compPoint.p, (size_t)c->res.n_points * sizeof(uint32_t))) return rc;
+  if (cell_component && c->res.n_cells)
+    if (const int rc = download_pipelined(c, cell_component, c->compCell.p, (size_t)c->res.n_cells * sizeof(uint32_t))) return rc;
+  if (component_cells && c->nComponents)
+    if (const int rc = download_pipelined(c, component_cells, c->compCount.p, (size_t)c->nComponents * sizeof(uint64_t))) return rc;
+  return CUBERILLE_OK;
+}
+
 int cuberille_debug_device_bytes(cuberille_ctx *c, size_t *bytes) {
   if (!c || !bytes) return CUBERILLE_ERR_ARGUMENT;
   *bytes = 0;
@@ -2431,6 +2554,16 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_normals(path, nrm.data(), r.n_points, n_threads);
   }
+  // a context that holds components: SCALARS component unsigned_int 1 in POINT_DATA (behind the normals) and in CELL_DATA (behind
+  // the cell pixels), either block opened here where nothing else has (setting off: the file as it was)
+  std::vector<uint32_t> pointComp, cellComp;
+  if (wr == CUBERILLE_OK && c->haveComponents) {
+    pointComp.resize((size_t)r.n_points);
+    cellComp.resize((size_t)r.n_cells);
+    const int dl = cuberille_components_download(c, pointComp.data(), cellComp.data(), nullptr, 0);
+    if (dl != CUBERILLE_OK) return dl;
+    wr = cuberille::append_vtk_components(path, c->haveNormals ? nullptr : "POINT_DATA", pointComp.data(), r.n_points);
+  }
   if (wr == CUBERILLE_OK && c->haveCellPixels) {
     // a context that holds cell pixels: CELL_DATA n / SCALARS pixel <type> 1 behind everything else (setting off: the file as it was)
     std::vector<char> pix((size_t)r.n_cells * pixel_size(c->pixel_type));
@@ -2438,6 +2571,8 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_cell_pixels(path, pix.data(), c->pixel_type, r.n_cells);
   }
+  if (wr == CUBERILLE_OK && c->haveComponents)
+    wr = cuberille::append_vtk_components(path, c->haveCellPixels ? nullptr : "CELL_DATA", cellComp.data(), r.n_cells);
   if (wr != CUBERILLE_OK) return fail(c, wr, std::string("cannot write ") + path);
   return CUBERILLE_OK;
 }
@@ -2678,6 +2813,9 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
                                               "they belong to one context's whole volume, not offered in a group");
     if (c->cellPixels)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has cell pixels set (cuberille_set_cell_pixels): "
+                                              "they belong to one context's whole volume, not offered in a group");
+    if (c->components)
+      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has components set (cuberille_set_components): "
                                               "they belong to one context's whole volume, not offered in a group");
   }
   {

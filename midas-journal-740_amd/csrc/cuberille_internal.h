@@ -263,5 +263,40 @@ hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &
 hipError_t launch_cell_pixels(int pixel_type, const Workspace &w, const Grid &g, int triangles, void *out, u64 nQ, int dyn,
                               hipStream_t s);
 
+// cuberille_set_components: the rows of the component pass, buffers of their own handed to their kernels beside the Workspace
+// (as the normals' and the cell pixels' are), and the plan of the numbering's scan.
+constexpr int COMP_SCAN_B = 256;      // entries a block of the scan sums / scans
+struct CompScanPlan {                 // the levels of block sums over nP flags: level 0 has one entry per COMP_SCAN_B points, level
+  int levels;                         // l + 1 one per COMP_SCAN_B entries of level l; the top level (levels - 1) fits one block
+  size_t off[8], len[8];              // where each level starts in the scan row (entries), and its length
+  size_t entries;                     // all levels together
+};
+inline CompScanPlan comp_scan_plan(u64 nP) {
+  CompScanPlan p{};
+  u64 n = nP;
+  do {                                // (2^64 points would take 8 levels: off / len cannot overflow)
+    n = (n + COMP_SCAN_B - 1) / COMP_SCAN_B;
+    p.off[p.levels] = p.entries;
+    p.len[p.levels] = (size_t)n;
+    p.entries += (size_t)n;
+    p.levels++;
+  } while (n > (u64)COMP_SCAN_B);
+  return p;
+}
+// bytes of the scan row for nP points: K (one u64) ahead of the levels
+inline size_t comp_scan_bytes(u64 nP) { return sizeof(u64) + comp_scan_plan(nP).entries * sizeof(u32); }
+struct CompRows {
+  u32 *parent;         // [n_points] the union-find's forest; behind the numbering, number[root]
+  u32 *pointComp;      // [n_points] the root, then the number of the point's component
+  u32 *cellComp;       // [n_cells]
+  u64 *compCells;      // [n_points]: K <= n_points rows are used
+  void *scan;          // comp_scan_bytes(n_points): K, then the levels of block sums
+};
+// The components of the mesh in w.cells (ids = index + pointOffset; a whole volume, this context the only rank) into the rows,
+// behind the cell pass on `s`; K is left in the first 8 bytes of r.scan.  nP / nQ: points and quads, or with dyn what the
+// launches and the rows are sized for (the kernels read the counts and the go flag from w.totals).
+hipError_t launch_components(const Workspace &w, const CompRows &r, int triangles, u64 pointOffset, u64 nP, u64 nQ, int dyn,
+                             hipStream_t s);
+
 }  // namespace cuberille
 #endif

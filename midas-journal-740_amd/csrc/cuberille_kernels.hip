@@ -4019,6 +4019,279 @@ __global__ __launch_bounds__(256) void k_cell_pixels(const T *__restrict__ vox, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// K3d: surface components (cuberille_set_components).  Two points are joined when one cell holds both; a component is a class
+// of the transitive closure; components are numbered in the order of their smallest point index.  The kernels read the cells
+// buffer the cell pass left (ids = index in `points` + pointOffset, which is taken off) and nothing else of the extraction:
+// quirk Q1 and the non-manifold edges and corners of a cuberille mesh are no special case.
+//   k_comp_init       parent[p] = p
+//   k_comp_hook       one lane per cell -- the 64 lanes of a wave are 64 consecutive cells, neighbours in raster order that
+//                     share most of their points -- unites the cell's first point with its others in a lock-free union-find
+//   k_comp_flatten    label[p] = root(p), behind a kernel boundary: parent is only read
+//   k_comp_root_sums, k_comp_sums, k_comp_scan, k_comp_number
+//                     roots are flagged (label[p] == p) and numbered by an exclusive scan built from plain launches: sums of
+//                     blocks of COMP_SCAN_B up the levels, the top level scanned by one block (its total is K), then every level
+//                     below scanned in its blocks with the level above as base; the root's number goes where its parent entry
+//                     was, and its row of component_cells is zeroed
+//   k_comp_relabel_points, k_comp_relabel_cells
+//                     point_component[p] = number[label[p]]; cell_component[c] = point_component[first point of c];
+//                     component_cells += 1 by integer atomics, one add per run of equal labels within a wave's span of cells
+// The union-find.  Invariants, which hold at every moment of k_comp_hook, whatever the lanes' order:
+//   (1) parent[x] <= x, and every value parent[x] has ever held is a point of x's true component: a link stores, at a point
+//       that IS a root (the compare-and-swap expects parent[hi] == hi and is decided on the true value at the agent's point of
+//       coherence), a smaller point that a cell chain joins to it; the halving stores, by an atomic minimum, a point reached
+//       from x by following parents, which is of the same component and smaller than what stood there.
+//   (2) so every entry only ever decreases, a point that has ceased to be a root never becomes one again, and following
+//       parents from any point strictly descends: comp_find ends after at most x steps, with no help from any other lane.
+//   (3) a stale read (every read of parent here is an agent-scope relaxed atomic load, never a cached plain load; but between
+//       a load and its use another lane may have moved on) returns a value the entry held earlier: by (1) a point of the same
+//       component, at or above the present one.  It can make comp_find return a point that is a root no longer.  If two walks
+//       meet in one point the two ends are in one tree already, truly; if they do not, the compare-and-swap on the larger is
+//       what decides: it succeeds only if that point is a root NOW, and then links it to a smaller point of the other cell
+//       end's component -- a correct link whether or not that one is still a root.  A wrong class cannot come of it.
+//   Termination: the only loop that goes round again is comp_unite's, and only when its compare-and-swap failed, which means
+//   parent[hi] != hi: another lane's link of hi succeeded.  There are at most n_points - 1 successful links in all, the loop
+//   resumes from the value the failed swap returned (smaller), and no lane ever waits for another lane's store: no lock, no
+//   polled flag, no spin.
+//   The root is the minimum: comp_unite returns only when both ends were seen in one tree or it linked their trees, and trees
+//   never split ((1): a new parent is an ancestor), so at the kernel's end each component is one tree.  Its smallest point m has
+//   no smaller point of its component to point at, so by (1) parent[m] == m: m is the tree's one root.
+// The result is a pure function of the cells: labels are roots = minima, numbers a scan over them, counts integer sums.
+// dyn: the counts and the go flag from Totals as k_emit_cells reads them (a whole volume: V0 = Q0 = 0 in effect); a flagged
+// step writes nothing.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 comp_load(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ u32 comp_find(u32 *parent, u32 x) {
+  for (;;) {
+    const u32 p = comp_load(parent + x);
+    if (p == x) return x;
+    const u32 gp = comp_load(parent + p);
+    if (gp == p) return p;
+    // path halving: x skips its parent (gp < p: the minimum can only lower the entry, and to an ancestor)
+    (void)__hip_atomic_fetch_min(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = gp;
+  }
+}
+
+__device__ __forceinline__ void comp_unite(u32 *parent, u32 a, u32 b) {
+  for (;;) {
+    a = comp_find(parent, a);
+    b = comp_find(parent, b);
+    if (a == b) return;
+    const u32 hi = a > b ? a : b, lo = a > b ? b : a;
+    u32 seen = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      return;
+    a = seen;            // hi was linked by another lane meanwhile: go on from its parent
+    b = lo;
+  }
+}
+
+// the counts of a blind launch (false: the step is flagged, nothing runs)
+__device__ __forceinline__ bool comp_counts(const Totals *tot, int dyn, u64 &nP, u64 &nQ) {
+  if (dyn) {
+    if (!tot->go) return false;
+    nP = tot->totV - tot->V0;
+    nQ = tot->totQ - tot->Q0;
+  }
+  return true;
+}
+
+// entries of scan level `level` for nP points (level 0: one per block of points)
+__device__ __forceinline__ u64 comp_level_len(u64 nP, int level) {
+  u64 n = nP;
+  for (int l = 0; l <= level; l++) n = (n + COMP_SCAN_B - 1) / COMP_SCAN_B;
+  return n;
+}
+
+// exclusive scan of one value per thread over a block of COMP_SCAN_B (every thread of the block calls it, once per kernel)
+__device__ __forceinline__ u32 comp_block_scan(u32 v, u32 *waveSum, u32 &total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  u32 incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u32 t = __shfl_up(incl, d);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) waveSum[wv] = incl;
+  __syncthreads();
+  u32 base = 0;
+  total = 0;
+#pragma unroll
+  for (int i = 0; i < COMP_SCAN_B / 64; i++) {
+    if (i < wv) base += waveSum[i];
+    total += waveSum[i];
+  }
+  return base + incl - v;
+}
+
+__global__ __launch_bounds__(256) void k_comp_init(u32 *__restrict__ parent, const Totals *tot, int dyn, u64 nP) {
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < nP) parent[p] = (u32)p;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_comp_hook(const u64 *__restrict__ cells, u32 *parent, const Totals *tot, int dyn, u64 nP,
+                                                   u64 nQ, u64 pointOffset) {
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 nC = nQ * (NV == 3 ? 2 : 1);
+  const u64 c = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nC) return;
+  const u64 *ids = cells + c * NV;
+  u64 id[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) id[i] = ids[i] - pointOffset;
+  if (id[0] >= nP) return;                       // (no cell holds such an id: nothing outside the rows is ever addressed)
+  // the parents of the cell's points, the loads back to back: two points that have (or had: invariant (3)) the same parent
+  // hang in one tree already, and trees never split -- no walk for them.  Most cells of a mesh end here: each point is in
+  // four cells or more, and one link per point is all a component needs.
+  u32 up[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) up[i] = id[i] < nP ? comp_load(parent + id[i]) : 0u;
+#pragma unroll
+  for (int i = 1; i < NV; i++)
+    if (id[i] < nP && up[i] != up[0]) comp_unite(parent, up[0], up[i]);     // (from the parents: points of the same trees)
+}
+
+__global__ __launch_bounds__(256) void k_comp_flatten(const u32 *__restrict__ parent, u32 *__restrict__ label, const Totals *tot,
+                                                      int dyn, u64 nP) {
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nP) return;
+  u32 x = (u32)p, up = parent[x];
+  while (up != x) { x = up; up = parent[x]; }    // (strictly descending: invariant (1))
+  label[p] = x;
+}
+
+// level 0 of the sums: the roots among each block of COMP_SCAN_B points
+__global__ __launch_bounds__(COMP_SCAN_B) void k_comp_root_sums(const u32 *__restrict__ label, u32 *__restrict__ sums,
+                                                                const Totals *tot, int dyn, u64 nP) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 p = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  if ((u64)blockIdx.x * COMP_SCAN_B >= nP) return;           // block-uniform
+  u32 total;
+  (void)comp_block_scan(p < nP && label[p] == (u32)p ? 1u : 0u, waveSum, total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// level `level` (>= 1) of the sums from the level below
+__global__ __launch_bounds__(COMP_SCAN_B) void k_comp_sums(const u32 *__restrict__ in, u32 *__restrict__ out, int level,
+                                                           const Totals *tot, int dyn, u64 nP) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 n = comp_level_len(nP, level - 1);
+  const u64 i = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  if ((u64)blockIdx.x * COMP_SCAN_B >= n) return;            // block-uniform
+  u32 total;
+  (void)comp_block_scan(i < n ? in[i] : 0u, waveSum, total);
+  if (threadIdx.x == 0) out[blockIdx.x] = total;
+}
+
+// the entries of level `level` become their exclusive prefixes: within the block, plus the block's entry of the level above
+// (already scanned); the top level is one block, has no level above and leaves its total: K
+__global__ __launch_bounds__(COMP_SCAN_B) void k_comp_scan(u32 *__restrict__ a, const u32 *__restrict__ base, u64 *__restrict__ K,
+                                                           int level, const Totals *tot, int dyn, u64 nP) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 n = comp_level_len(nP, level);
+  const u64 i = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  if ((u64)blockIdx.x * COMP_SCAN_B >= n && !(K && blockIdx.x == 0)) return;   // block-uniform (the top block also runs for n = 0)
+  const u32 v = i < n ? a[i] : 0u;
+  u32 total;
+  const u32 ex = comp_block_scan(v, waveSum, total);
+  if (i < n) a[i] = ex + (base ? base[blockIdx.x] : 0u);
+  if (K && blockIdx.x == 0 && threadIdx.x == 0) *K = total;
+}
+
+// the number of every root: its rank among the roots; left at number[root] (the root's parent entry, no longer needed), and
+// the root's row of component_cells zeroed for the atomics of k_comp_relabel_cells
+__global__ __launch_bounds__(COMP_SCAN_B) void k_comp_number(const u32 *__restrict__ label, const u32 *__restrict__ base,
+                                                             u32 *__restrict__ number, u64 *__restrict__ compCells,
+                                                             const Totals *tot, int dyn, u64 nP) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 p = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  if ((u64)blockIdx.x * COMP_SCAN_B >= nP) return;           // block-uniform
+  const bool root = p < nP && label[p] == (u32)p;
+  u32 total;
+  const u32 k = comp_block_scan(root ? 1u : 0u, waveSum, total) + base[blockIdx.x];
+  if (root) {
+    number[p] = k;
+    compCells[k] = 0ull;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_comp_relabel_points(u32 *__restrict__ pointComp, const u32 *__restrict__ number,
+                                                             const Totals *tot, int dyn, u64 nP) {
+  u64 nQ = 0;
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < nP) pointComp[p] = number[pointComp[p]];           // (in: the root; a lane reads and writes its own entry only)
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void k_comp_relabel_cells(const u64 *__restrict__ cells, const u32 *__restrict__ pointComp,
+                                                            u32 *__restrict__ cellComp, u64 *compCells, const Totals *tot, int dyn,
+                                                            u64 nP, u64 nQ, u64 pointOffset) {
+  if (!comp_counts(tot, dyn, nP, nQ)) return;
+  const u64 nC = nQ * (NV == 3 ? 2 : 1);
+  const int lane = threadIdx.x & 63;
+  // A wave takes a span of consecutive chunks of 64 cells.  One add per run of equal labels: the lane that starts a run adds
+  // its length; the last run of a chunk is held back (pendK, pendN: wave-uniform) and joins the first run of the next chunk
+  // when that has the same label -- a mesh of one component costs one add per wave, not one per 64 cells on one address
+  // (4.2 ms of adds for 22 M cells before).  Integer sums: the order of the adds shows nowhere.
+  const u64 nWaves = (u64)gridDim.x * (blockDim.x >> 6), wave = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const u64 nChunks = (nC + 63) / 64, span = (nChunks + nWaves - 1) / nWaves;
+  const u64 chunk0 = wave * span, chunk1 = chunk0 + span < nChunks ? chunk0 + span : nChunks;
+  u32 pendK = 0;
+  u64 pendN = 0;
+  for (u64 chunk = chunk0; chunk < chunk1; chunk++) {          // wave-uniform bounds
+    const u64 c = chunk * 64 + lane;
+    bool have = c < nC;
+    u32 k = 0;
+    if (have) {
+      const u64 first = cells[c * NV] - pointOffset;
+      have = first < nP;
+      if (have) {
+        k = pointComp[first];
+        cellComp[c] = k;
+      }
+    }
+    const u32 before = __shfl_up(k, 1);
+    const bool beforeHave = __shfl_up(have ? 1 : 0, 1) != 0;
+    const bool head = have && (lane == 0 || !beforeHave || before != k);
+    const unsigned long long heads = __ballot(head), lanes = __ballot(have);
+    if (!heads) continue;
+    // a run ends ahead of the next head, or of the first lane without a cell
+    const unsigned long long above = lane == 63 ? 0ull : (~0ull << (lane + 1));
+    const unsigned long long stop = (heads | ~lanes) & above;
+    u64 len = head ? (u64)((stop ? __builtin_ctzll(stop) : 64) - lane) : 0ull;
+    // what the chunk before held back: into lane 0's run when that goes on with the same label, else added now
+    const u32 k0 = __shfl(k, 0);
+    if (pendN) {
+      if ((heads & 1ull) && k0 == pendK) {
+        if (lane == 0) len += pendN;
+      } else if (lane == 0) {
+        (void)__hip_atomic_fetch_add(compCells + pendK, pendN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    const int last = 63 - __builtin_clzll(heads);
+    if (head && lane != last) (void)__hip_atomic_fetch_add(compCells + k, len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pendK = __shfl(k, last);
+    pendN = (u64)__shfl((unsigned)len, last) | ((u64)__shfl((unsigned)(len >> 32), last) << 32);
+  }
+  if (pendN && lane == 0) (void)__hip_atomic_fetch_add(compCells + pendK, pendN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <class F>
@@ -4775,6 +5048,51 @@ hipError_t launch_cell_pixels(int pixel_type, const Workspace &w, const Grid &g,
     else launch(std::integral_constant<int, VIEW_WHOLE>());
     return hipGetLastError();
   });
+}
+
+// The components of the mesh the cell pass left (K3d), behind it on `s`.  dyn: nP and nQ are what the launches and the rows
+// are sized for; the offsets of the scan's levels come from that size, their lengths in the kernels from the real count,
+// which is no larger.
+hipError_t launch_components(const Workspace &w, const CompRows &r, int triangles, u64 pointOffset, u64 nP, u64 nQ, int dyn,
+                             hipStream_t s) {
+  u64 *K = (u64 *)r.scan;
+  if (!nP) return hipMemsetAsync(K, 0, sizeof(u64), s);      // an empty mesh: K = 0, nothing else
+  u32 *levels = (u32 *)(K + 1);
+  const CompScanPlan plan = comp_scan_plan(nP);
+  const Totals *tot = w.totals;
+  const u64 nC = nQ * (triangles ? 2 : 1);
+  const dim3 block(256), perPoint(grid_for(nP, 256, 0)), perCell(grid_for(nC, 256, 0));
+  hipLaunchKernelGGL(k_comp_init, perPoint, block, 0, s, r.parent, tot, dyn, nP);
+  if (nC) {
+    if (triangles) hipLaunchKernelGGL(k_comp_hook<3>, perCell, block, 0, s, w.cells, r.parent, tot, dyn, nP, nQ, pointOffset);
+    else hipLaunchKernelGGL(k_comp_hook<4>, perCell, block, 0, s, w.cells, r.parent, tot, dyn, nP, nQ, pointOffset);
+  }
+  hipLaunchKernelGGL(k_comp_flatten, perPoint, block, 0, s, r.parent, r.pointComp, tot, dyn, nP);
+  // the numbering: sums up the levels, the top level scanned by one block, the levels below it scanned downwards
+  const dim3 scanBlock(COMP_SCAN_B);
+  hipLaunchKernelGGL(k_comp_root_sums, dim3((unsigned)plan.len[0]), scanBlock, 0, s, r.pointComp, levels + plan.off[0], tot, dyn, nP);
+  for (int l = 1; l < plan.levels; l++)
+    hipLaunchKernelGGL(k_comp_sums, dim3((unsigned)plan.len[l]), scanBlock, 0, s, levels + plan.off[l - 1], levels + plan.off[l], l,
+                       tot, dyn, nP);
+  for (int l = plan.levels - 1; l >= 0; l--) {
+    const bool top = l == plan.levels - 1;
+    hipLaunchKernelGGL(k_comp_scan, dim3(top ? 1u : grid_for(plan.len[l], COMP_SCAN_B, 0)), scanBlock, 0, s, levels + plan.off[l],
+                       top ? (const u32 *)nullptr : levels + plan.off[l + 1], top ? K : (u64 *)nullptr, l, tot, dyn, nP);
+  }
+  hipLaunchKernelGGL(k_comp_number, dim3((unsigned)plan.len[0]), scanBlock, 0, s, r.pointComp, levels + plan.off[0], r.parent,
+                     r.compCells, tot, dyn, nP);
+  hipLaunchKernelGGL(k_comp_relabel_points, perPoint, block, 0, s, r.pointComp, r.parent, tot, dyn, nP);
+  if (nC) {
+    // (a wave takes a span of chunks and holds a run back across them: at most 4096 workgroups, two rounds of the device's wave slots)
+    const dim3 perSpan(grid_for(nC, 256, 4096));
+    if (triangles)
+      hipLaunchKernelGGL(k_comp_relabel_cells<3>, perSpan, block, 0, s, w.cells, r.pointComp, r.cellComp, r.compCells, tot, dyn, nP, nQ,
+                         pointOffset);
+    else
+      hipLaunchKernelGGL(k_comp_relabel_cells<4>, perSpan, block, 0, s, w.cells, r.pointComp, r.cellComp, r.compCells, tot, dyn, nP, nQ,
+                         pointOffset);
+  }
+  return hipGetLastError();
 }
 
 }  // namespace cuberille

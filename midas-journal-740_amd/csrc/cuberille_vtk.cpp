@@ -171,4 +171,31 @@ int append_vtk_cell_pixels(const char *path, const void *pixels, int pixel_type,
   ok = (std::fclose(f) == 0) && ok;
   return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
 }
+
+// ... and on one that holds components (cuberille_set_components): "SCALARS component unsigned_int 1", "LOOKUP_TABLE default",
+// one label per line -- once in the point attribute block behind the normals, once in the cell attribute block behind the cell
+// pixels.  block: "POINT_DATA" / "CELL_DATA" where this array is the block's first and opens it, null where the block exists.
+int append_vtk_components(const char *path, const char *block, const uint32_t *labels, uint64_t n) {
+  if (!path || (n && !labels)) return CUBERILLE_ERR_ARGUMENT;
+  std::FILE *f = std::fopen(path, "ab");
+  if (!f) return CUBERILLE_ERR_ARGUMENT;
+  bool ok = true;
+  if (block) ok = std::fprintf(f, "%s %llu\n", block, (unsigned long long)n) > 0;
+  ok = ok && std::fprintf(f, "SCALARS component unsigned_int 1\nLOOKUP_TABLE default\n") > 0;
+  std::string buf;
+  const size_t chunk = 1u << 16;
+  for (size_t i0 = 0; ok && i0 < n; i0 += chunk) {
+    const size_t i1 = std::min<size_t>(n, i0 + chunk);
+    buf.resize((i1 - i0) * 11 + 16);               // (a uint32 takes at most 10 digits)
+    char *p = &buf[0];
+    for (size_t i = i0; i < i1; i++) {
+      p = put_u64(p, labels[i]);
+      *p++ = '\n';
+    }
+    const size_t len = (size_t)(p - &buf[0]);
+    ok = std::fwrite(buf.data(), 1, len, f) == len;
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
+}
 }  // namespace cuberille

@@ -520,6 +520,38 @@ class Extractor:
         _abi.check(self._ctx, self._lib.cuberille_cell_pixels_download(self._ctx, C.c_void_p(out.ctypes.data), out.nbytes))
         return out
 
+    def set_components(self, on=True):
+        """Surface components (cuberille_set_components): every later extraction also labels the connected surfaces of its
+        mesh on the device -- two points are joined when one cell holds both, components are numbered in the order of their
+        smallest point index.  Points, cells and counters are unchanged.  Slabs, steps and groups are refused at the
+        extraction.  Off (the default) frees the rows."""
+        _abi.check(self._ctx, self._lib.cuberille_set_components(self._ctx, 1 if on else 0))
+
+    def n_components(self):
+        """K, the number of components of the last extraction (cuberille_components_info); CuberilleError ERR_STATE when that
+        extraction ran with the setting off."""
+        k = C.c_uint64()
+        _abi.check(self._ctx, self._lib.cuberille_components_info(self._ctx, C.byref(k)))
+        return int(k.value)
+
+    def components_device(self):
+        """Device pointers (point_component, cell_component, component_cells) of the last extraction, in the library's
+        buffers (cuberille_components_device; None each for an empty mesh)."""
+        p, q, r = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _abi.check(self._ctx, self._lib.cuberille_components_device(self._ctx, C.byref(p), C.byref(q), C.byref(r)))
+        return p.value, q.value, r.value
+
+    def download_components(self):
+        """(point_component uint32[n_points], cell_component uint32[n_cells], component_cells uint64[K]) of the last
+        extraction as numpy arrays (cuberille_components_download)."""
+        k = self.n_components()
+        n_points = int(self.result.n_points) if self.result is not None else 0
+        n_cells = int(self.result.n_cells) if self.result is not None else 0
+        pc, cc, counts = np.empty(n_points, np.uint32), np.empty(n_cells, np.uint32), np.empty(k, np.uint64)
+        _abi.check(self._ctx, self._lib.cuberille_components_download(
+            self._ctx, C.c_void_p(pc.ctypes.data), C.c_void_p(cc.ctypes.data), C.c_void_p(counts.ctypes.data), k))
+        return pc, cc, counts
+
     def device_bytes(self):
         """Bytes of device memory the context's workspace holds at this moment (cuberille_debug_device_bytes)."""
         n = C.c_size_t()
@@ -725,6 +757,11 @@ class ExtractorGroup:
         refusal -- they belong to one context's whole volume."""
         self._on_every_member(self._lib.cuberille_set_cell_pixels, 1 if on else 0)
 
+    def set_components(self, on=True):
+        """Components (Extractor.set_components) on every member: the group's extraction then raises the library's
+        refusal -- a component does not stop at a slab's face."""
+        self._on_every_member(self._lib.cuberille_set_components, 1 if on else 0)
+
     def debug_fail_alloc(self, slab, n):
         """Failure drill: the n-th device allocation of slab `slab`'s upload and count in the next extraction fails
         (slab -1: every slab's; n < 0: off)."""
@@ -789,13 +826,15 @@ class CuberilleImageToMeshFilter:
     # The view settings that several devices do not offer: (attribute, its "off", the setting by name, why)
     _normals = False       # SetGeneratePointNormals: off (class level for the same reason)
     _cell_pixels_on = False   # SetSavePixelAsCellData: off (likewise)
+    _components_on = False    # SetGenerateComponents: off (likewise)
 
     _NOT_IN_A_GROUP = (
         ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
         ("_region", None, "a region (SetExtractionRegion / cuberille_set_region)", "a box belongs to one context's whole volume"),
         ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"),
         ("_normals", False, "point normals (SetGeneratePointNormals / cuberille_set_point_normals)", "they belong to one context's whole volume"),
-        ("_cell_pixels_on", False, "cell pixels (SetSavePixelAsCellData / cuberille_set_cell_pixels)", "they belong to one context's whole volume"))
+        ("_cell_pixels_on", False, "cell pixels (SetSavePixelAsCellData / cuberille_set_cell_pixels)", "they belong to one context's whole volume"),
+        ("_components_on", False, "components (SetGenerateComponents / cuberille_set_components)", "a component does not stop at a slab's face"))
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -828,6 +867,8 @@ class CuberilleImageToMeshFilter:
         self._point_normals = None                # GetPointNormals(): (n, 3) float32 of the last Update(), or None
         self._cell_pixels_on = False              # SetSavePixelAsCellData: off
         self._cell_pixels = None                  # GetCellPixels(): one pixel per cell of the last Update(), or None
+        self._components_on = False               # SetGenerateComponents: off
+        self._components = None                   # (point_component, cell_component, component_cells) of the last Update(), or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -1074,6 +1115,37 @@ class CuberilleImageToMeshFilter:
         """One value of the input's dtype per cell id, filled by the last Update() with the switch on; None with it off."""
         return self._cell_pixels
 
+    def SetGenerateComponents(self, b):
+        """Not in the reference.  On: Update() also labels the connected surfaces of the mesh on the device
+        (cuberille_set_components) and fills GetPointComponents() / GetCellComponents() / GetComponentCellCounts() /
+        GetNumberOfComponents().  Default off."""
+        self._components_on = bool(b)
+
+    def GetGenerateComponents(self):
+        return self._components_on
+
+    def GenerateComponentsOn(self):
+        self.SetGenerateComponents(True)
+
+    def GenerateComponentsOff(self):
+        self.SetGenerateComponents(False)
+
+    def GetPointComponents(self):
+        """uint32 per point id, filled by the last Update() with the switch on; None with it off."""
+        return None if self._components is None else self._components[0]
+
+    def GetCellComponents(self):
+        """uint32 per cell id: the component of the cell's first point; None with the switch off."""
+        return None if self._components is None else self._components[1]
+
+    def GetComponentCellCounts(self):
+        """uint64 per component: its cells; None with the switch off."""
+        return None if self._components is None else self._components[2]
+
+    def GetNumberOfComponents(self):
+        """K of the last Update() with the switch on; 0 with it off."""
+        return 0 if self._components is None else int(self._components[2].shape[0])
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -1103,6 +1175,7 @@ class CuberilleImageToMeshFilter:
                 self._group = ExtractorGroup(self._devices)
             self._point_normals = None
             self._cell_pixels = None
+            self._components = None
             self.last_result = self._group.extract_host(vol, prm)
             self._output = self._group.download()
             self.last_number_of_slabs = len(self._group.plan(self._group_desc(vol), prm))
@@ -1125,12 +1198,16 @@ class CuberilleImageToMeshFilter:
         self._point_normals = None
         self._extractor.set_cell_pixels(self._cell_pixels_on)
         self._cell_pixels = None
+        self._extractor.set_components(self._components_on)
+        self._components = None
         self.last_result = self._extractor.extract_host(vol, prm)
         self._output = self._extractor.download()
         if self._normals:
             self._point_normals = self._extractor.download_normals()
         if self._cell_pixels_on:
             self._cell_pixels = self._extractor.download_cell_pixels()
+        if self._components_on:
+            self._components = self._extractor.download_components()
         self.last_number_of_slabs = 1
 
     @staticmethod

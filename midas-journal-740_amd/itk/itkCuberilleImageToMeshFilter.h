@@ -301,6 +301,22 @@ public:
   itkBooleanMacro(SavePixelAsCellData);
   const std::vector<InputPixelType> &GetCellPixels() const { return m_CellPixels; }
 
+  /** Not in the reference: what a caller does with the mesh in itk::ConnectedRegionsMeshFilter, on the device.
+   *  GenerateComponentsOn(): Update() also labels the connected surfaces of the output mesh (cuberille_set_components) -- two
+   *  points are joined when one cell holds both, components are numbered in the order of their smallest point id -- and fills
+   *  GetPointComponents() (one label per point id), GetCellComponents() (per cell id: the component of the cell's first point),
+   *  GetComponentCellCounts() (cells per component) and GetNumberOfComponents().  The mesh's cell data stays the cell pixels'.
+   *  Offered on every route of a single device (after the host walk's split of quads into triangles the cell labels are
+   *  repeated and the counts doubled on the host); with SetDevices of more than one device the library refuses and Update()
+   *  throws an itk::ExceptionObject that says so.  Default off: the vectors are empty, the number is 0. */
+  itkGetMacro(GenerateComponents, bool);
+  itkSetMacro(GenerateComponents, bool);
+  itkBooleanMacro(GenerateComponents);
+  const std::vector<uint32_t> &GetPointComponents() const { return m_PointComponents; }
+  const std::vector<uint32_t> &GetCellComponents() const { return m_CellComponents; }
+  const std::vector<uint64_t> &GetComponentCellCounts() const { return m_ComponentCellCounts; }
+  size_t GetNumberOfComponents() const { return m_ComponentCellCounts.size(); }
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -347,6 +363,9 @@ private:
   std::vector<float> m_PointNormals;          // GetPointNormals(): filled by Update() with the switch on, else empty
   bool m_SavePixelAsCellData;
   std::vector<InputPixelType> m_CellPixels;   // GetCellPixels(): filled by Update() with the switch on, else empty
+  bool m_GenerateComponents;
+  std::vector<uint32_t> m_PointComponents, m_CellComponents;   // filled by Update() with the switch on, else empty
+  std::vector<uint64_t> m_ComponentCellCounts;
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them

@@ -502,6 +502,7 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_BorderPadValue = NumericTraits<InputPixelType>::Zero;
   m_GeneratePointNormals = false;
   m_SavePixelAsCellData = false;
+  m_GenerateComponents = false;
   m_InsideBand = false;
   m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
   m_BandInside = NumericTraits<InputPixelType>::One;
@@ -771,6 +772,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       // (point normals on the members: the group's extraction refuses them likewise)
       (void)cuberille_set_point_normals(cuberille_group_context(m_Group, i), m_GeneratePointNormals ? 1 : 0);
       (void)cuberille_set_cell_pixels(cuberille_group_context(m_Group, i), m_SavePixelAsCellData ? 1 : 0);
+      (void)cuberille_set_components(cuberille_group_context(m_Group, i), m_GenerateComponents ? 1 : 0);
       }
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
@@ -794,6 +796,8 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< "cuberille_set_point_normals: " << cuberille_last_error(m_Context));
     if (cuberille_set_cell_pixels(m_Context, m_SavePixelAsCellData ? 1 : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_cell_pixels: " << cuberille_last_error(m_Context));
+    if (cuberille_set_components(m_Context, m_GenerateComponents ? 1 : 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_set_components: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
@@ -829,6 +833,23 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
                                        m_CellPixels.size() * sizeof(InputPixelType)) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_cell_pixels_download: " << cuberille_last_error(m_Context));
     }
+  m_PointComponents.clear();
+  m_CellComponents.clear();
+  m_ComponentCellCounts.clear();
+  if (m_GenerateComponents)                   // (the single context: a group has refused above)
+    {
+    uint64_t nComponents = 0;
+    if (cuberille_components_info(m_Context, &nComponents) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_components_info: " << cuberille_last_error(m_Context));
+    m_PointComponents.resize(static_cast<size_t>(res.n_points));
+    m_CellComponents.resize(static_cast<size_t>(res.n_cells));
+    m_ComponentCellCounts.resize(static_cast<size_t>(nComponents));
+    if (cuberille_components_download(m_Context, m_PointComponents.empty() ? 0 : &m_PointComponents[0],
+                                      m_CellComponents.empty() ? 0 : &m_CellComponents[0],
+                                      m_ComponentCellCounts.empty() ? 0 : &m_ComponentCellCounts[0],
+                                      m_ComponentCellCounts.size()) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_components_download: " << cuberille_last_error(m_Context));
+    }
   m_LastDownloadSeconds = cuberille_detail::WallSeconds() - downloadStart;
   struct FreeOnExit { void *p; ~FreeOnExit() { std::free(p); } } ownCells = {0};   // the host walk's triangles, when it makes them
 
@@ -854,6 +875,12 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
         {
         m_CellPixels.resize(static_cast<size_t>(res.n_cells));
         for (size_t q = m_CellPixels.size() / 2; q-- > 0;) m_CellPixels[2 * q] = m_CellPixels[2 * q + 1] = m_CellPixels[q];
+        }
+      if (m_GenerateComponents)               // likewise: both triangles are of their quad's component (they share its diagonal)
+        {
+        m_CellComponents.resize(static_cast<size_t>(res.n_cells));
+        for (size_t q = m_CellComponents.size() / 2; q-- > 0;) m_CellComponents[2 * q] = m_CellComponents[2 * q + 1] = m_CellComponents[q];
+        for (size_t k = 0; k < m_ComponentCellCounts.size(); k++) m_ComponentCellCounts[k] *= 2;
         }
       }
     }
