@@ -6,7 +6,7 @@ a GPU box, its summary committed under profiles/:
 
 Every case is a pure function of (seed, case): draw_case() draws a RECIPE from np.random.default_rng([seed, case]) -- no GPU,
 no oracle; the recipe survives JSON and holds all that is needed to build the voxels again --, expected() asks the references
-for the mesh (and the normals), run_case() asks the library.  A recipe a run printed replays alone:
+for the mesh (and the normals, the cell pixels, the components), run_case() asks the library.  A recipe a run printed replays alone:
 
     python tests/fuzz_campaign.py --seed 1 --case 4711          (or --replay '<the recipe>' / --replay recipe.json)
 
@@ -28,17 +28,32 @@ flip as direction matrix, a start index), the filter's eight parameters, a proje
           bspline cuberille_set_interpolator, 32 / 64 bits: host, device, stream;
                                          reference: the oracle's lattice points walked by the drop-in's host walk (a subprocess)
   normals cuberille_set_point_normals on;   reference: normals_ref.normals on the frame image at the REFERENCE's points
-  repeat  the case three times on the context, the third mesh compared (the blind launch sized by its own history)
+  cell_pixels  cuberille_set_cell_pixels on, on every route of one whole volume (the held gradient too, not the slabs), every
+          kind, with or without normals;   reference: cell_pixels_ref.cell_pixels on the view's frame BEFORE the band mapping
+          (the caller's raw pixel; the ring's constant where the ring is inside), compared as bytes
+  components   cuberille_set_components on, the same routes and kinds (frames of up to COMPONENTS_MAX_VOXELS voxels: the
+          reference's time);   reference: components_ref.components on the REFERENCE's cells -- three rows as bytes, K, and the
+          definition's properties (test_components.check_properties)
+  emit_offset  count + emit: the id offset handed to cuberille_emit -- 0, below 10^6, or 2^32 and more --, taken off the cells
+          before the comparison; labels and pixels never carry it
+  repeat  the case three times on the context, the third mesh compared (the blind launch sized by its own history); the first
+          of the three runs with cell pixels and components OFF, and its points, cells and counters are the bytes of the third
   refusal one call the header lists as refused, made first: CUBERILLE_ERR_ARGUMENT with that refusal's words, and the case
-          itself still equal
+          itself still equal; refusal_slab (whole volumes): with cell pixels or components on, cuberille_count of a slab that
+          is not the whole volume, likewise
 
 and every case runs on the context the cases before it used, whatever they left there: the settings of a case are taken back
-behind it, the workspace and its history stay, and so does the normals row of a normals case unless its recipe drops it -- the
-next normals case then finds a row sized by another mesh (counted in the summary).  Comparisons are exact: ids, cell order,
+behind it, the workspace and its history stay, and so do the normals row of a normals case, the pixel row of a cell-pixel case
+and the rows of a components case unless the recipe drops them -- the next case with that setting then finds rows sized by
+another mesh, of another view, pixel width or cell count (counted in the summary).  Comparisons are exact: ids, cell order,
 the float bits of every coordinate (conftest.assert_same_mesh), the bits of every normal (normals_ref.same_normals), the walk's
-counters.  TEST INFRASTRUCTURE: the oracle is the checker here, never the thing measured or shipped.
+counters, the bytes of every cell pixel and label.  TEST INFRASTRUCTURE: the oracle is the checker here, never the thing
+measured or shipped.
+What was drawn before cell pixels and components existed comes from the stream it came from, draw for draw; the keys above that
+are new come from a second one (draw_case; tests/golden/campaign_recipe_digests.json): the cases of the committed logs replay.
 Prints one progress line every ~20 s; exit code 1 with the failing case's recipe if a mesh ever differs."""
 import argparse
+import copy
 import json
 import os
 import subprocess
@@ -74,15 +89,28 @@ NORMALS_ROUTES = ("host", "host_chunked", "device", "stream", "count_emit", "swi
 # normals_ref.gradient_image calls the oracle once per voxel from Python (about 2 us each): a frame of this many voxels takes
 # well under a second; a larger case is drawn without normals
 NORMALS_MAX_VOXELS = 40000
+# the routes on which cuberille_set_cell_pixels and cuberille_set_components are offered: every route of one whole volume -- the
+# held gradient too: the header lists no refusal of either with it --, not the slabs
+CELLDATA_ROUTES = ("host", "host_chunked", "device", "stream", "count_emit", "switch", "held")
+# components_ref.components propagates minima through numpy until nothing moves: measured on the largest cases of seed 1 at
+# --max-voxels 900000 (frames of 350 000 to 480 000 voxels, noise meshes of up to 785 000 cells) it takes 0.2 to 2.3 s, at most
+# 5 us per voxel of the frame -- a frame of this many voxels stays below 0.75 s, a larger case is drawn without components.
+# cell_pixels_ref took at most 0.05 s on the same cases: no cap.
+COMPONENTS_MAX_VOXELS = 150000
 # one subprocess per B-spline case, and ITK's class evaluates 64 taps per step on one thread: small volumes only
 BSPLINE_MAX_VOXELS = 12000
 COUNTERS = ("proj_iterations", "proj_stop_threshold", "proj_stop_steps")
-REFUSALS = {"whole": ["normals_rg", "bspline_variant", "bspline_held"],
+REFUSALS = {"whole": ["normals_rg", "bspline_variant", "bspline_held", "cell_pixels_slab", "components_slab"],
             "bspline": ["normals_rg", "bspline_variant", "bspline_held"],
             "border": ["pair", "variant", "held", "rg"],
             "region": ["pair", "stream", "variant", "held", "rg"],
             "band": ["pair", "stream", "variant", "held", "rg"]}
-DEFAULT_OPTIONS = dict(max_voxels=900000, big=False, recursive_gaussian=False, kind=None, dtype=None, route=None, max_rows=None)
+# recipe["refusal"] is drawn among the first names only, as it was before the two slab refusals existed (the draws of the first
+# stream do not move: tests/golden/campaign_recipe_digests.json); those two are drawn from the second stream as recipe["refusal_slab"]
+REFUSALS_FIRST_STREAM = {"whole": 3}
+SLAB_REFUSALS = {"cell_pixels_slab": "cell_pixels", "components_slab": "components"}
+DEFAULT_OPTIONS = dict(max_voxels=900000, big=False, recursive_gaussian=False, kind=None, dtype=None, route=None, max_rows=None,
+                       cell_pixels=None, components=None)
 
 
 def draw_field(rng, shape, dt, big=True):
@@ -229,9 +257,9 @@ def _jnum(v):
 
 
 def inside_set(img, iso):
-    """pixel >= iso in the pixel type (a NaN pixel is outside)."""
-    dt = img.dtype
-    return img >= (dt.type(iso) if dt.kind == "f" else np.asarray(int(iso), dtype=dt))
+    """The sweep's predicate !(pixel < iso) in the pixel type (a NaN pixel is inside): cell_pixels_ref.inside_of."""
+    import cell_pixels_ref
+    return cell_pixels_ref.inside_of(img, iso if img.dtype.kind == "f" else int(iso))
 
 
 def has_q1_gap(img, iso):
@@ -243,8 +271,14 @@ def has_q1_gap(img, iso):
 # ---- 1. the recipe ---------------------------------------------------------------------------------------------------------
 def draw_case(seed, case, options=None):
     """The recipe of case `case` of seed `seed`: a dict of plain numbers, lists and strings.  options: DEFAULT_OPTIONS' keys
-    -- max_voxels, big (up to 120 rows and slices), recursive_gaussian, and kind / dtype / route to fix what a stratified
-    slice fixes (they are recorded, so the recipe alone still says everything).  Needs no GPU and no oracle."""
+    -- max_voxels, big (up to 120 rows and slices), recursive_gaussian, and kind / dtype / route / cell_pixels / components to
+    fix what a stratified slice fixes (they are recorded, so the recipe alone still says everything; cell_pixels / components
+    True: every case that can takes it).  Needs no GPU and no oracle.
+
+    Two streams: np.random.default_rng([seed, case]) draws everything the campaign drew before cell pixels and components
+    existed, in the order it drew it then -- no draw of it may move, tests/golden/campaign_recipe_digests.json pins them --, and
+    np.random.default_rng([seed, case, 3]) draws cell_pixels, components, drop_cell_rows, emit_offset and refusal_slab
+    ([seed, case, 1] is the field's stream, [seed, case, 2] that of a held case's first volume)."""
     opt = dict(DEFAULT_OPTIONS)
     opt.update(options or {})
     rng = np.random.default_rng([int(seed), int(case)])
@@ -329,13 +363,32 @@ def draw_case(seed, case, options=None):
     recipe["repeat"] = 3 if rng.random() < 0.12 and recipe["route"] not in ("slabs", "thin_slabs", "held") else 1
     pick = rng.random() < 0.15, int(rng.integers(0, 8))
     if pick[0] and recipe["route"] not in ("slabs", "thin_slabs", "held"):
-        names = REFUSALS[kind]
+        names = REFUSALS[kind][:REFUSALS_FIRST_STREAM.get(kind)]
         recipe["refusal"] = names[pick[1] % len(names)]
         if recipe["refusal"] == "rg" and min(recipe["field"]["shape"]) < 4:
             recipe["refusal"] = "variant"       # (shorter lines are refused for their length, not for the view)
     # behind a normals case the setting stays on -- its row, sized by this mesh, is there for the next case -- or is switched off
     recipe["drop_normals_row"] = bool(rng.random() < 0.25)
+    _draw_cell_data(np.random.default_rng([int(seed), int(case), 3]), recipe, opt, img.size)
     return recipe
+
+
+def _draw_cell_data(rng, recipe, opt, frame_voxels):
+    """The second stream: cell pixels, components (independent of each other, of normals and of the kind: neither pass depends
+    on the interpolator), whether their rows stay behind the case, the id offset of a count + emit, a refused slab."""
+    offered = {"cell_pixels": recipe["route"] in CELLDATA_ROUTES,
+               "components": recipe["route"] in CELLDATA_ROUTES and frame_voxels <= COMPONENTS_MAX_VOXELS}
+    draws = {"cell_pixels": bool(rng.random() < 0.35), "components": bool(rng.random() < 0.35)}
+    for key in ("cell_pixels", "components"):
+        recipe[key] = bool(offered[key] and (draws[key] if opt[key] is None else opt[key]))
+    # behind the case the two settings are switched off, which frees their rows, or left on for the next case
+    recipe["drop_cell_rows"] = bool(rng.random() < 0.25) or recipe["route"] == "held"      # (held: a context of its own)
+    u, small, high = rng.random(), int(rng.integers(1, 10 ** 6)), bool(rng.random() < 0.4)
+    if recipe["route"] == "count_emit":
+        recipe["emit_offset"] = 0 if u < 0.5 else (2 ** 32 + small if high else small)
+    name = ["cell_pixels_slab", "components_slab"][int(rng.integers(0, 2))]
+    if rng.random() < 0.08 and recipe["kind"] == "whole" and recipe["route"] not in ("slabs", "thin_slabs", "held"):
+        recipe["refusal_slab"] = name
 
 
 def _draw_border_value(rng, dt, iso):
@@ -426,7 +479,9 @@ def _oracle_kw(recipe):
 
 def expected(oracle, recipe, vox=None):
     """{"mesh": the reference mesh (with .info, the walk's counters, where the reference has them), "normals": the reference
-    normals or None}.  Never the library."""
+    normals or None, "cell_pixels": cell_pixels_ref's row or None, "components": components_ref's three rows ON THE REFERENCE'S
+    CELLS or None}.  Never the library."""
+    vox = voxels(recipe) if vox is None else vox
     img, start = frame(recipe, vox)
     okw = _oracle_kw(recipe)
     if recipe["kind"] == "bspline":
@@ -441,7 +496,31 @@ def expected(oracle, recipe, vox=None):
     if recipe.get("normals"):
         import normals_ref
         normals = normals_ref.normals(oracle, img, mesh.points, start, **_geo(recipe)) if len(mesh.points) else np.zeros((0, 3), dtype=np.float32)
-    return {"mesh": mesh, "normals": normals}
+    pixels = components = None
+    if recipe.get("cell_pixels"):
+        import cell_pixels_ref
+        pixels = cell_pixels_ref.cell_pixels(*cell_pixels_view(recipe, vox), bool(recipe["kw"]["triangles"]))
+    if recipe.get("components"):
+        import components_ref
+        components = components_ref.components(mesh.cells, len(mesh.points))
+    return {"mesh": mesh, "normals": normals, "cell_pixels": pixels, "components": components}
+
+
+def cell_pixels_view(recipe, vox):
+    """(frame, inside) of cell_pixels_ref's view constructors: the frame BEFORE the band mapping -- with a band the caller's raw
+    volume --, the ring's constant where the ring is inside."""
+    import cell_pixels_ref as cp
+    kind, iso = recipe["kind"], recipe["iso"]
+    iso = iso if vox.dtype.kind == "f" else int(iso)
+    if kind == "border":
+        c = recipe["border"]["value"]
+        return cp.border(vox, float(c) if vox.dtype.kind == "f" else int(c), iso)
+    if kind == "region":
+        return cp.region(vox, recipe["region"]["start"], recipe["region"]["size"], iso)
+    if kind == "band":
+        b = recipe["band"]
+        return cp.band(vox, _num(b["lower"]), _num(b["upper"]), _num(b["inside"]), _num(b["outside"]), iso)
+    return cp.whole(vox, iso)
 
 
 def _bspline_expected(oracle, recipe, img, start):
@@ -489,7 +568,8 @@ def close_contexts(contexts):
 REFUSAL_TEXT = {"pair": "together with", "stream": "cuberille_extract_stream", "variant": "default projection branch only",
                 "held": "holding a gradient", "rg": "central-difference gradient only", "normals_rg": "point normals",
                 "bspline_variant": "B-spline interpolator walks the default projection branch",
-                "bspline_held": "B-spline interpolator is not offered on a context holding a gradient"}
+                "bspline_held": "B-spline interpolator is not offered on a context holding a gradient",
+                "cell_pixels_slab": "cell pixels", "components_slab": "components"}
 
 
 def _refused(pkg, ex, recipe, vox, desc, normals_on=False):
@@ -542,6 +622,39 @@ def _refused(pkg, ex, recipe, vox, desc, normals_on=False):
         _clear_settings(pkg, ex)
 
 
+def _refused_slab(pkg, ex, recipe, vox, on):
+    """cell_pixels_slab / components_slab: with the setting on, cuberille_count of a slab that is not the whole volume --
+    CUBERILLE_ERR_ARGUMENT, the message names the setting.  on: {"normals", "cell_pixels", "components"} -> whether a case
+    before left that setting on; none of them is switched off here (that would free its row), and count_prepare asks them in
+    this order, so the message names the first that is on.  A setting switched on for the call is switched off behind it."""
+    import torch
+    A = pkg._abi
+    name = recipe["refusal_slab"]
+    mine = SLAB_REFUSALS[name]
+    nz, ny, nx = vox.shape
+    kw = dict(recipe["kw"], variant=0)
+    kw.pop("gradient", None)
+    now = dict(on, **{mine: True})
+    text = next(REFUSAL_TEXT[t] for k, t in (("normals", "normals_rg"), ("cell_pixels", "cell_pixels_slab"), ("components", "components_slab")) if now[k])
+    desc = pkg.make_desc(vox.dtype, (nx, ny, nz), tuple(recipe["spacing"]), tuple(recipe["origin"]), np.asarray(recipe["direction"], dtype=np.float64),
+                         tuple(recipe["index_start"]))
+    dev = to_device(torch, vox)
+    torch.cuda.synchronize()
+    setter = ex.set_cell_pixels if mine == "cell_pixels" else ex.set_components
+    setter(True)
+    try:
+        # the buffer's slices as the lower part of a volume one slice taller: consistent ranges, not the whole volume
+        ex.count(dev.data_ptr(), desc, pkg.make_params(recipe["iso"], **kw), A.Slab(nz + 1, 0, 0, nz, 0, 0))
+    except A.CuberilleError as e:
+        assert e.code == A.ERR_ARGUMENT, "refusal %s: code %d (%s), not CUBERILLE_ERR_ARGUMENT" % (name, e.code, e)
+        assert text in str(e), "refusal %s: refused for another reason: %s" % (name, e)
+    else:
+        raise AssertionError("refusal %s: the call was accepted" % name)
+    finally:
+        if not on[mine]:
+            setter(False)
+
+
 def _set_view(ex, recipe):
     kind = recipe["kind"]
     if kind == "border":
@@ -559,14 +672,20 @@ def _clear_settings(pkg, ex):
     ex.clear_band()
     ex.hold_gradient(False)
     ex.set_interpolator(pkg._abi.INTERP_LINEAR)
-    ex.debug_option("defaults", 0)         # (cuberille_set_point_normals is the case's to set: off would free the row)
+    # (cuberille_set_point_normals, cuberille_set_cell_pixels and cuberille_set_components are the case's to set: off would free
+    #  the rows)
+    ex.debug_option("defaults", 0)
 
 
 def run_case(pkg, contexts, recipe, vox=None, stats=None):
-    """{"mesh", "normals" (or None), "counters" (or None), "row_before"} of the library for the recipe, on the contexts as the
-    cases before left them (the settings a case makes are taken back behind it; the workspace, its sizes, its history and --
-    unless the recipe drops it -- the normals row of a normals case stay).  row_before: the points of the mesh whose normals row
-    the context still held when the case began, or None."""
+    """{"mesh", "normals" (or None), "counters" (or None), "cell_pixels" (or None), "components" (three rows, or None),
+    "n_components", "first_mesh" / "first_counters" (a case that repeats: its first repeat, run with cell pixels and components
+    off), "emit_offset", "row_before", "pixels_row_before", "components_row_before"} of the library for the recipe, on the
+    contexts as the cases before left them (the settings a case makes are taken back behind it; the workspace, its sizes, its
+    history and -- unless the recipe drops them -- the normals row of a normals case, the pixel row of a cell-pixel case and the
+    rows of a components case stay).  row_before: the points of the mesh whose normals row the context still held when the case
+    began, or None; pixels_row_before: (cells, bytes per pixel) of the mesh whose pixel row it held; components_row_before:
+    (points, cells) of the mesh whose component rows it held."""
     import torch
     vox = voxels(recipe) if vox is None else vox
     dt = vox.dtype
@@ -577,10 +696,21 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
     vol = pkg.Volume(vox, spacing=spacing, origin=origin, direction=direction, index_start=start)
     desc = pkg.make_desc(dt, (nx, ny, nz), spacing, origin, direction, start)
     prm = pkg.make_params(iso, **kw)
-    row_before = contexts.get("normals_row") if route != "held" else None
+    held = route == "held"
+    row_before = contexts.get("normals_row") if not held else None
+    pixels_row_before = contexts.get("pixels_row") if not held else None
+    components_row_before = contexts.get("components_row") if not held else None
     if recipe.get("refusal"):
         _refused(pkg, ex, recipe, vox, desc, row_before is not None)
-    mesh = normals = counters = None
+    if recipe.get("refusal_slab"):
+        # (the refusal normals_rg switches the normals on for its call and leaves them to the case, which sets them next)
+        _refused_slab(pkg, ex, recipe, vox, {"normals": row_before is not None or recipe.get("refusal") == "normals_rg",
+                                             "cell_pixels": pixels_row_before is not None,
+                                             "components": components_row_before is not None})
+    want_pixels, want_components = bool(recipe.get("cell_pixels")), bool(recipe.get("components"))
+    repeat = int(recipe.get("repeat", 1))
+    offset = int(recipe.get("emit_offset", 0))
+    mesh = normals = counters = pixels = components = n_components = first_mesh = first_counters = None
     try:
         _set_view(ex, recipe)
         if kind == "bspline":
@@ -590,7 +720,14 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
         if recipe.get("chunk_kib"):
             ex.debug_option("upload_chunk_kib", recipe["chunk_kib"])
         ex.set_point_normals(bool(recipe.get("normals")))
-        for _ in range(int(recipe.get("repeat", 1))):
+        for rep in range(repeat):
+            # a case that repeats runs its first repeat with the two settings OFF (which frees what rows there were): points,
+            # cells and counters are the bytes of the same extraction with the setting off -- compare() holds them to that
+            first_off = repeat > 1 and rep == 0
+            ex.set_cell_pixels(want_pixels and not first_off)
+            ex.set_components(want_components and not first_off)
+            if rep == 1:
+                first_mesh, first_counters = mesh, counters
             res = None
             if route in ("host", "host_chunked", "switch"):
                 res = ex.extract_host(vol, prm)
@@ -610,10 +747,10 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
                 dev = to_device(torch, vox)
                 torch.cuda.synchronize()
                 n_p, n_c = ex.count(dev.data_ptr(), desc, prm)
-                res = ex.emit(0)
+                res = ex.emit(offset)           # (with cell pixels on the emit reads the voxels: dev lives until here)
                 mesh = ex.download()
                 assert (n_p, n_c) == (mesh.points.shape[0], mesh.cells.shape[0])
-            elif route == "held":
+            elif held:
                 # quirk Q3: a first volume of its own (same pixel type), then this one along the first one's gradient
                 f = recipe["first"]
                 fvox = _field(f["field"])[0]
@@ -655,20 +792,57 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
                 counters = {k: int(getattr(res, k)) for k in COUNTERS}
             if recipe.get("normals"):
                 normals = ex.download_normals()
+        # (after the last repeat)
+        if want_pixels:
+            pixels = ex.download_cell_pixels()
+        if want_components:
+            components = ex.download_components()
+            n_components = ex.n_components()
     finally:
         _clear_settings(pkg, ex)
-        if route != "held":
-            contexts["normals_row"] = None
-    if route != "held":
-        contexts["normals_row"] = row_after(recipe, int(mesh.points.shape[0]))
-        if contexts["normals_row"] is None:
-            ex.set_point_normals(False)
-    return {"mesh": mesh, "normals": normals, "counters": counters, "row_before": row_before}
+        if not held:
+            contexts["normals_row"] = contexts["pixels_row"] = contexts["components_row"] = None
+    n_points, n_cells = int(mesh.points.shape[0]), int(mesh.cells.shape[0])
+    rows = {"normals_row": row_after(recipe, n_points), "pixels_row": pixels_row_after(recipe, n_cells),
+            "components_row": components_row_after(recipe, n_points, n_cells)}
+    for name, setter in (("normals_row", ex.set_point_normals), ("pixels_row", ex.set_cell_pixels), ("components_row", ex.set_components)):
+        if rows[name] is None:
+            setter(False)
+    if not held:
+        contexts.update(rows)
+    return {"mesh": mesh, "normals": normals, "counters": counters, "cell_pixels": pixels, "components": components,
+            "n_components": n_components, "first_mesh": first_mesh, "first_counters": first_counters, "emit_offset": offset, "row_before": row_before,
+            "pixels_row_before": pixels_row_before, "components_row_before": components_row_before}
 
 
 def row_after(recipe, n_points):
     """The points of the mesh whose normals row a case leaves on its context (None: no row -- no normals, or dropped)."""
     return n_points if recipe.get("normals") and not recipe.get("drop_normals_row") else None
+
+
+def pixels_row_after(recipe, n_cells):
+    """(cells, bytes per pixel) of the mesh whose cell-pixel row a case leaves on its context (None: no row)."""
+    keep = recipe.get("cell_pixels") and not recipe.get("drop_cell_rows") and recipe["route"] != "held"
+    return (int(n_cells), np.dtype(recipe["dtype"]).itemsize) if keep else None
+
+
+def components_row_after(recipe, n_points, n_cells):
+    """(points, cells) of the mesh whose component rows a case leaves on its context (None: no rows)."""
+    keep = recipe.get("components") and not recipe.get("drop_cell_rows") and recipe["route"] != "held"
+    return (int(n_points), int(n_cells)) if keep else None
+
+
+def meets_pixels_row_of_another_size(row_before, recipe, n_cells):
+    """A cell-pixel case on a context that still holds the row of a mesh of another cell count or pixel width.  (A case that
+    repeats frees the row in its first repeat, which runs with the setting off: it meets none.)"""
+    return bool(recipe.get("cell_pixels") and recipe.get("repeat", 1) == 1 and row_before is not None
+                and tuple(row_before) != (int(n_cells), np.dtype(recipe["dtype"]).itemsize))
+
+
+def meets_components_row_of_another_size(row_before, recipe, n_points, n_cells):
+    """A components case on a context that still holds the rows of a mesh of other point or cell counts."""
+    return bool(recipe.get("components") and recipe.get("repeat", 1) == 1 and row_before is not None
+                and tuple(row_before) != (int(n_points), int(n_cells)))
 
 
 def meets_row_of_another_size(row_before, recipe, n_points):
@@ -677,15 +851,45 @@ def meets_row_of_another_size(row_before, recipe, n_points):
 
 
 def compare(got, want):
-    """The first difference as an AssertionError: mesh, then counters, then normals."""
+    """The first difference as an AssertionError: mesh (the id offset of a count + emit taken off its cells; the first repeat's
+    mesh, extracted with cell pixels and components off, byte for byte the last one's), then counters, normals, cell pixels
+    (as bytes: a NaN's payload and the sign of a zero count), components (three rows as bytes, K, the definition's properties)."""
     import normals_ref
-    assert_same_mesh(got["mesh"], want["mesh"])
+    mesh, offset = got["mesh"], int(got.get("emit_offset") or 0)
+    if offset:
+        if len(mesh.cells):
+            assert int(mesh.cells.min()) >= offset, ("a cell id below the id offset", int(mesh.cells.min()), offset)
+        mesh = copy.copy(mesh)
+        mesh.cells = mesh.cells - np.uint64(offset)
+    assert_same_mesh(mesh, want["mesh"])
+    first = got.get("first_mesh")
+    if first is not None:
+        for name in ("points", "cells"):
+            a, b = getattr(first, name), getattr(got["mesh"], name)
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), \
+                "%s with cell pixels and components off differ from those with the settings on" % name
     info = getattr(want["mesh"], "info", None)
     if got["counters"] is not None and info is not None:
         assert got["counters"] == {k: info[k] for k in COUNTERS}, ("counters", got["counters"], {k: info[k] for k in COUNTERS})
+    if first is not None:
+        assert got.get("first_counters") == got["counters"], ("counters with cell pixels and components off", got.get("first_counters"), got["counters"])
     if want["normals"] is not None:
         assert got["normals"] is not None, "no normals came back"
         normals_ref.same_normals(got["normals"], want["normals"], "normals")
+    if want.get("cell_pixels") is not None:
+        g, w = got.get("cell_pixels"), want["cell_pixels"]
+        assert g is not None, "no cell pixels came back"
+        assert g.dtype == w.dtype and g.shape == w.shape == (len(want["mesh"].cells),), ("cell pixels", g.dtype, g.shape, w.dtype, w.shape)
+        if g.tobytes() != w.tobytes():
+            at = int(np.argmax((g.view(np.uint8) != w.view(np.uint8)).reshape(len(g), -1).any(axis=1)))
+            raise AssertionError("cell pixels: first difference at cell %d: %r, reference %r" % (at, g[at], w[at]))
+    if want.get("components") is not None:
+        import test_components as cases
+        g, w = got.get("components"), want["components"]
+        assert g is not None, "no components came back"
+        cases.same(g, w, "components")
+        assert got.get("n_components") == len(w[2]), ("K", got.get("n_components"), len(w[2]))
+        cases.check_properties(want["mesh"].cells, len(want["mesh"].points), g, "components")
 
 
 def tally(stats, recipe, got, want):
@@ -700,16 +904,31 @@ def tally(stats, recipe, got, want):
     stats["normals_on_a_row_of_another_size"] += int(meets_row_of_another_size(got.get("row_before"), recipe, int(mesh.points.shape[0])))
     stats["nan_normals"] += int(np.isnan(want["normals"]).any(axis=1).sum()) if want["normals"] is not None and want["normals"].size else 0
     stats["repeats"] += int(recipe.get("repeat", 1) > 1)
-    stats["after_refusal"] += int(bool(recipe.get("refusal")))
+    stats["after_refusal"] += int(bool(recipe.get("refusal")) or bool(recipe.get("refusal_slab")))
     stats["with_switch"] += int(bool(recipe.get("switch")) or bool(recipe.get("chunk_kib")))
-    if recipe.get("refusal"):
-        key = "%s:%s" % (recipe["kind"], recipe["refusal"])
-        stats["refusals"][key] = stats["refusals"].get(key, 0) + 1
+    for name in (recipe.get("refusal"), recipe.get("refusal_slab")):
+        if name:
+            key = "%s:%s" % (recipe["kind"], name)
+            stats["refusals"][key] = stats["refusals"].get(key, 0) + 1
+    n_points, n_cells = int(mesh.points.shape[0]), int(mesh.cells.shape[0])
+    pix, comp = bool(recipe.get("cell_pixels")), bool(recipe.get("components"))
+    stats["with_cell_pixels"] += int(pix)
+    stats["with_components"] += int(comp)
+    stats["with_normals_cell_pixels_and_components"] += int(pix and comp and bool(recipe.get("normals")))
+    if comp:
+        stats["components_found"] += len(want["components"][2])
+        stats["with_two_components_or_more"] += int(len(want["components"][2]) >= 2)
+    stats["cell_pixels_on_a_row_of_another_size"] += int(meets_pixels_row_of_another_size(got.get("pixels_row_before"), recipe, n_cells))
+    stats["components_on_rows_of_another_size"] += int(meets_components_row_of_another_size(got.get("components_row_before"), recipe, n_points, n_cells))
+    stats["nonzero_id_offsets"] += int(bool(recipe.get("emit_offset")))
 
 
 def new_stats():
     return {"cases": 0, "points": 0, "cells": 0, "routes": {}, "dtypes": {}, "kinds": {}, "with_normals": 0, "normals_on_a_row_of_another_size": 0, "nan_normals": 0, "repeats": 0,
-            "after_refusal": 0, "refusals": {}, "with_switch": 0, "refused_slab_alias": 0, "nan_points": 0}
+            "after_refusal": 0, "refusals": {}, "with_switch": 0, "refused_slab_alias": 0, "nan_points": 0,
+            "with_cell_pixels": 0, "with_components": 0, "with_normals_cell_pixels_and_components": 0, "components_found": 0,
+            "with_two_components_or_more": 0, "cell_pixels_on_a_row_of_another_size": 0, "components_on_rows_of_another_size": 0,
+            "nonzero_id_offsets": 0}
 
 
 def one_case(pkg, oracle, contexts, recipe, stats=None):
@@ -729,34 +948,54 @@ SLICE = {"whole": (54, 24), "border": (4, 20), "region": (1, 20), "band": (1, 20
 
 
 def slice_recipes(kind, seed=None, n=None):
+    """Cell pixels and components are fixed by a RULE OF THE CASE NUMBER i, not by a seed: cell pixels on where
+    (i + i // 10) % 2 == 0 -- the pixel type is DTYPES[i % 10], so the parity alternates from one decade to the next and all ten
+    types take it --, components on where i % 3 != 2 -- the empty meshes of the region and band slices (cases 10; 1 and 16) are
+    among them -- and both on every route that offers them.  Everything else of the second stream (the rows kept or dropped,
+    the id offset, a refused slab) is drawn."""
     seed = SLICE[kind][0] if seed is None else seed
     n = SLICE[kind][1] if n is None else n
     return [draw_case(seed, i, dict(SLICE_OPTIONS, kind=kind, dtype=np.dtype(DTYPES[i % len(DTYPES)]).name,
-                                    route=ROUTES[kind][i % len(ROUTES[kind])])) for i in range(n)]
+                                    route=ROUTES[kind][i % len(ROUTES[kind])], cell_pixels=(i + i // 10) % 2 == 0,
+                                    components=i % 3 != 2)) for i in range(n)]
 
 
-def slice_facts(recipe, want, row_before=None):
-    """What one executed case of the slice contributes to the conditions, from the recipe and the reference alone.  row_before:
-    what row_after() gave for the case before it on the context (slice_sequence_facts follows it through a kind's cases)."""
+def slice_facts(recipe, want, row_before=None, pixels_row_before=None, components_row_before=None):
+    """What one executed case of the slice contributes to the conditions, from the recipe and the reference alone.  row_before,
+    pixels_row_before, components_row_before: what row_after(), pixels_row_after(), components_row_after() gave for the case
+    before it on the context (slice_sequence_facts follows them through a kind's cases)."""
     img, _ = frame(recipe)
     pts, nrm = want["mesh"].points, want["normals"]
+    n_cells = len(want["mesh"].cells)
+    pix, comp = want.get("cell_pixels"), want.get("components")
     return dict(walks=bool(recipe["kw"]["project"]) and recipe["kw"]["max_steps"] > 0 and len(pts) > 0,
                 other_row=meets_row_of_another_size(row_before, recipe, len(pts)),
+                cell_pixels=pix is not None, components=comp is not None, K=len(comp[2]) if comp is not None else None,
+                offset=int(recipe.get("emit_offset", 0)), switch=bool(recipe.get("switch")),
+                # a border case with cell pixels whose constant is not below the iso value: the ring is inside
+                ring_inside=pix is not None and recipe["kind"] == "border" and bool(cell_pixels_view(recipe, voxels(recipe))[1][0, 0, 0]),
+                # a band case with cell pixels whose cells carry at least two distinct raw pixels
+                raw_values=pix is not None and recipe["kind"] == "band" and len(pix) > 0
+                and len(np.unique(pix.view(np.uint8).reshape(len(pix), -1), axis=0)) >= 2,
+                other_pixels_row=meets_pixels_row_of_another_size(pixels_row_before, recipe, n_cells),
+                other_components_row=meets_components_row_of_another_size(components_row_before, recipe, len(pts), n_cells),
                 kind=recipe["kind"], dtype=recipe["dtype"], route=recipe["route"], triangles=bool(recipe["kw"]["triangles"]),
                 project=bool(recipe["kw"]["project"]), form=geometry_form(recipe), moved=any(int(v) for v in recipe["index_start"]),
                 q1=bool(has_q1_gap(img, recipe["iso"])), empty=len(pts) == 0, nan_points=bool(np.isnan(pts).any()),
                 normals=nrm is not None and len(nrm) > 0, nan_normals=nrm is not None and bool(np.isnan(nrm).any()),
-                repeat=recipe.get("repeat", 1) > 1, refusal=recipe.get("refusal"))
+                repeat=recipe.get("repeat", 1) > 1, refusal=recipe.get("refusal"),
+                refused=bool(recipe.get("refusal") or recipe.get("refusal_slab")))
 
 
 def slice_sequence_facts(recipes, wants):
     """slice_facts of a kind's cases in the order they run on their one context."""
-    facts, row = [], None
+    facts, rows = [], (None, None, None)
     for recipe, want in zip(recipes, wants):
-        held = recipe["route"] == "held"                      # (a context of its own, never with normals)
-        facts.append(slice_facts(recipe, want, None if held else row))
+        held = recipe["route"] == "held"                      # (a context of its own, never with normals, its rows always dropped)
+        facts.append(slice_facts(recipe, want, *((None, None, None) if held else rows)))
         if not held:
-            row = row_after(recipe, len(want["mesh"].points))
+            n_points, n_cells = len(want["mesh"].points), len(want["mesh"].cells)
+            rows = (row_after(recipe, n_points), pixels_row_after(recipe, n_cells), components_row_after(recipe, n_points, n_cells))
     return facts
 
 
@@ -779,6 +1018,15 @@ def slice_conditions(kind, facts):
     if kind in ("border", "region", "band"):
         need(any(f["refusal"] for f in facts), "a case behind a refused call")
     need(4 * sum(f["empty"] for f in facts) <= len(facts), "at most a quarter of the cases with an empty reference mesh")
+    for key, name in (("cell_pixels", "cell pixels"), ("components", "components")):
+        mine = [f for f in facts if f[key]]
+        need(len(mine) >= 5, "at least 5 cases with %s" % name)
+        need({f["triangles"] for f in mine} == {True, False}, "quads and triangles with %s" % name)
+        need(4 * sum(f["empty"] for f in mine) <= len(mine), "at most a quarter of the cases with %s with an empty reference mesh" % name)
+    if kind != "bspline":
+        need(any(f["components"] and f["K"] == 1 for f in facts), "a components case with K = 1")
+        need(any(f["components"] and f["K"] >= 2 for f in facts), "a components case with K >= 2")
+    need(any(f["cell_pixels"] and f["components"] for f in facts), "a case with cell pixels and components")
     return missing
 
 
@@ -797,6 +1045,22 @@ def slice_conditions_overall(facts):
     need({f["kind"] for f in facts} == set(KINDS), "the cases of every kind")
     for k in ("border", "region", "band"):
         need(any(f["kind"] == k and f["refusal"] for f in facts), "a refusal case of kind %s" % k)
+    pix, comp = [f for f in facts if f["cell_pixels"]], [f for f in facts if f["components"]]
+    need({f["dtype"] for f in pix} == {np.dtype(d).name for d in DTYPES}, "cell pixels of all ten pixel types")
+    need(any(f["normals"] and f["cell_pixels"] and f["components"] for f in facts), "a case with normals, cell pixels and components together")
+    need(any(f["empty"] and f["K"] == 0 for f in comp), "a components case with an empty mesh (K = 0, null rows)")
+    need(any(f["q1"] and not f["empty"] for f in comp), "a components case on a mesh with a Q1 gap")
+    need(any(f["K"] > 64 for f in comp), "a components case with K > 64")
+    need(any(f["ring_inside"] for f in facts), "a border case with cell pixels whose ring is inside")
+    need(any(f["raw_values"] for f in facts), "a band case whose cell pixels carry two distinct raw values")
+    for mine, name in ((pix, "cell pixels"), (comp, "components")):
+        need(any(f["repeat"] for f in mine), "a repeat case with %s" % name)
+        need(any(f["refused"] for f in mine), "a case with %s behind a refused call" % name)
+        need(any(f["switch"] for f in mine), "a case with %s under a development switch" % name)
+    need(any(f["route"] == "count_emit" and f["offset"] > 0 for f in comp), "a count + emit components case with a non-zero id offset")
+    need(any(f["route"] == "count_emit" and f["offset"] >= 2 ** 32 for f in comp), "a count + emit components case with an id offset of at least 2^32")
+    need(any(f["other_pixels_row"] for f in facts), "a cell-pixel case on a context whose previous case left a row of another size")
+    need(any(f["other_components_row"] for f in facts), "a components case on a context whose previous case left rows of another size")
     return missing
 
 
@@ -806,6 +1070,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-voxels", type=int, default=900000)
     ap.add_argument("--recursive-gaussian", action="store_true", help="every case that can takes the recursive-Gaussian gradient (h:21)")
+    ap.add_argument("--cell-pixels", action="store_true", help="every case that can takes cuberille_set_cell_pixels")
+    ap.add_argument("--components", action="store_true", help="every case that can takes cuberille_set_components")
     ap.add_argument("--big", action="store_true", help="up to 120 rows and slices (fewer, larger cases: set --max-voxels too)")
     ap.add_argument("--kind", choices=KINDS, default=None, help="draw this kind only")
     ap.add_argument("--dtype", default=None, help="draw this pixel type only (a numpy name)")
@@ -815,7 +1081,8 @@ def main():
     ap.add_argument("--replay", default=None, help="run one recipe: its JSON, or a file that holds it (a FAILED line is accepted as it is)")
     args = ap.parse_args()
     options = dict(max_voxels=args.max_voxels, big=args.big, recursive_gaussian=args.recursive_gaussian, kind=args.kind,
-                   dtype=args.dtype, route=args.route, max_rows=args.max_rows)
+                   dtype=args.dtype, route=args.route, max_rows=args.max_rows, cell_pixels=args.cell_pixels or None,
+                   components=args.components or None)
     pkg = graft.load_package()
     oracle = graft.load_oracle()
     oracle.build()
@@ -850,7 +1117,13 @@ def main():
             tally(stats, recipe, got, want)
             if time.time() - last > 20:
                 last = time.time()
-                print("t %.0f s: %d cases, %d points, %d cells, all identical" % (last - t0, stats["cases"], stats["points"], stats["cells"]), flush=True)
+                print("t %.0f s: %d cases, %d points, %d cells, %d with cell pixels (%d on a row of another size), %d with components "
+                      "(%d on rows of another size, %d components, %d cases with two or more), %d with normals and both, %d id offsets, "
+                      "all identical" % (last - t0, stats["cases"], stats["points"], stats["cells"], stats["with_cell_pixels"],
+                                         stats["cell_pixels_on_a_row_of_another_size"], stats["with_components"],
+                                         stats["components_on_rows_of_another_size"], stats["components_found"],
+                                         stats["with_two_components_or_more"], stats["with_normals_cell_pixels_and_components"],
+                                         stats["nonzero_id_offsets"]), flush=True)
     finally:
         close_contexts(contexts)
     stats["seconds"] = round(time.time() - t0, 1)

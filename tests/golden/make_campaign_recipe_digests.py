@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Regenerate tests/golden/campaign_recipe_digests.json: what tests/fuzz_campaign.py's draw_case drew BEFORE cell pixels,
+components and the emit offset entered the recipe -- to be run on a checkout of that commit (61de589), never on a later one:
+
+    python tests/golden/make_campaign_recipe_digests.py --tests /path/to/parent/checkout/tests
+
+  keys     the keys a recipe of that commit can hold (the union over every recipe digested)
+  seeds    for seeds 1 and 11, cases 0 .. 299, default options: sha256 of json.dumps(recipe, sort_keys=True)
+  slices   the same for the five slice_recipes(kind) lists
+
+The seeds of the slice were chosen for what they produce, and the cases logged in profiles/fuzz_views_seed*.log and
+profiles/r5_fuzz_campaign_*.log replay from --seed S --case N: tests/test_campaign_scripts.py recomputes every digest from the
+draw_case of the day, restricted to `keys`, and requires equality -- a new key is drawn from a stream of its own.
+Needs no GPU and no oracle."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SEEDS = (1, 11)
+CASES = 300
+
+
+def digest(recipe, keys=None):
+    """sha256 of the recipe's JSON with sorted keys; keys: the top-level keys that count (None: all)."""
+    if keys is not None:
+        recipe = {k: v for k, v in recipe.items() if k in keys}
+    return hashlib.sha256(json.dumps(recipe, sort_keys=True).encode()).hexdigest()
+
+
+def collect(fz, keys=None):
+    """(seeds, slices, recipes): the digests in the fixture's layout, and every recipe they were taken from."""
+    by_seed = {str(s): [fz.draw_case(s, c) for c in range(CASES)] for s in SEEDS}
+    by_kind = {kind: fz.slice_recipes(kind) for kind in fz.KINDS}
+    recipes = [r for rs in list(by_seed.values()) + list(by_kind.values()) for r in rs]
+    return ({s: [digest(r, keys) for r in rs] for s, rs in by_seed.items()},
+            {k: [digest(r, keys) for r in rs] for k, rs in by_kind.items()}, recipes)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tests", default=os.path.dirname(HERE), help="the tests/ directory of the checkout whose draw_case is recorded")
+    args = ap.parse_args()
+    tests = os.path.abspath(args.tests)
+    sys.path.insert(0, os.path.dirname(tests))
+    sys.path.insert(0, tests)
+    import fuzz_campaign as fz
+    assert os.path.dirname(os.path.abspath(fz.__file__)) == tests, fz.__file__
+    seeds, slices, recipes = collect(fz)
+    keys = sorted({k for r in recipes for k in r})
+    with open(os.path.join(HERE, "campaign_recipe_digests.json"), "w") as f:
+        json.dump(dict(keys=keys, cases=CASES, seeds=seeds, slices=slices), f, indent=1)
+        f.write("\n")
+    print(len(keys), "keys,", len(recipes), "recipes")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,11 +1,25 @@
 """A seeded slice of the differential campaign (tests/fuzz_campaign.py) in the GPU suite: one test per kind -- the whole volume
 (with normals and repeats), cuberille_set_border, cuberille_set_region, cuberille_set_band, the B-spline walk -- each a fixed list
 of (seed, case) pairs run in order on ONE context of the test's own, so that every case meets what the cases before it left
-there: the launch sizes of another frame, a workspace sized for a padded grid or a box, a normals row that exists or not.
+there: the launch sizes of another frame, a workspace sized for a padded grid or a box, a normals row that exists or not, the
+pixel row and the component rows of a mesh of another view, pixel width or cell count.
 
 The references are never the library: the oracle on the volume, on the padded copy, on the crop, on test_band.band_image; the
 oracle's lattice points walked by the drop-in's host walk through ITK's B-spline class; normals_ref.normals at the reference's
-points.  Comparisons are exact (conftest.assert_same_mesh, normals_ref.same_normals, the walk's counters equal).
+points; cell_pixels_ref.cell_pixels on the view's frame before the band mapping; components_ref.components on the REFERENCE's
+cells.  Comparisons are exact (conftest.assert_same_mesh, normals_ref.same_normals, the walk's counters equal, cell pixels and
+the three component rows as bytes, K; a case that repeats runs its first repeat with cell pixels and components off, and that
+mesh is byte for byte the last repeat's).
+
+Cell pixels (cuberille_set_cell_pixels) are on where (i + i // 10) % 2 == 0, components (cuberille_set_components) where
+i % 3 != 2, on every route that offers them (not the slabs); a count + emit case hands cuberille_emit the id offset its recipe
+drew.  Per kind: at least 5 cases with each setting, quads and triangles with each, a case with both, at most a quarter of the
+cases of each with an empty reference mesh, and (all but the B-spline) a components case with K = 1 and one with K >= 2.  Over
+the whole slice: cell pixels of all ten pixel types; normals, cell pixels and components together; components on an empty mesh
+(K = 0, null rows), on a mesh with a Q1 gap, with K > 64 (the slice reaches K = 311); a border whose ring is inside, a band
+whose cells carry two raw values; a repeat, a refused call ahead and a development switch with each setting; a count + emit
+components case with a non-zero id offset and one of 2^32 or more; a cell-pixel case and a components case on a context that
+still holds the rows of a mesh of another size -- the rows the run met are held to the rows the recipes foretell.
 
 Case i of a kind takes pixel type DTYPES[i % 10] and the kind's routes in turn; everything else is drawn, and the seeds
 (fuzz_campaign.SLICE) are the first for which the oracle alone shows the conditions of fuzz_campaign.slice_conditions: all ten pixel
@@ -21,8 +35,8 @@ Volumes: the XS row lengths; a volume (of a region case: its box) has at most 12
 region case's buffer is larger than its box by up to 16 + 8 voxels along x (up to 63 more where the buffer's rows are made
 whole words round a ragged box) and 3 + 3 (one more below a box that spans x and y) along y and z: at most 19 rows and slices,
 60 000 voxels.  Wall time of each test on an MI355X box (16 host
-threads, the references included), pytest's own figures: whole volume 1.9 s (24 cases in 0.14 s; the rest is the first context of
-the process loading the code objects), border 0.24 s, region 0.14 s, band 0.12 s, B-spline 0.36 s (20 cases each, the B-spline's
+threads, the references included), pytest's own figures: whole volume 2.0 s (24 cases in 0.35 s; the rest is the first context of
+the process loading the code objects), border 0.15 s, region 0.07 s, band 0.12 s, B-spline 0.31 s (20 cases each, the B-spline's
 with one subprocess per projecting case).
 """
 import time
@@ -52,13 +66,18 @@ def _run_slice(pkg, oracle, kind):
             except AssertionError as e:
                 raise AssertionError("seed %d case %d (%s %s %s): %s" % (recipe["seed"], recipe["case"], kind, recipe["dtype"], recipe["route"], e)) from e
             wants.append(want)
-            rows.append(fz.meets_row_of_another_size(got["row_before"], recipe, len(got["mesh"].points)))
+            n_points, n_cells = len(got["mesh"].points), len(got["mesh"].cells)
+            rows.append((fz.meets_row_of_another_size(got["row_before"], recipe, n_points),
+                         fz.meets_pixels_row_of_another_size(got["pixels_row_before"], recipe, n_cells),
+                         fz.meets_components_row_of_another_size(got["components_row_before"], recipe, n_points, n_cells)))
+            assert (got["cell_pixels"] is not None) == recipe["cell_pixels"] and (got["components"] is not None) == recipe["components"]
     finally:
         fz.close_contexts(contexts)
     print("%s: %d cases in %.2f s" % (kind, len(wants), time.time() - t0))
     assert len(wants) == len(recipes) == fz.SLICE[kind][1]                 # no case is skipped
     facts = fz.slice_sequence_facts(recipes, wants)
-    assert [f["other_row"] for f in facts] == rows                         # the rows the run met are the rows the recipes foretell
+    # the rows the run met -- normals, cell pixels, components -- are the rows the recipes foretell
+    assert [(f["other_row"], f["other_pixels_row"], f["other_components_row"]) for f in facts] == rows
     assert fz.slice_conditions(kind, facts) == []
     _FACTS[kind] = facts
     return facts
