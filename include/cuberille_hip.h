@@ -570,6 +570,38 @@ int cuberille_components_device(cuberille_ctx *ctx, const uint32_t **d_point_com
                                 const uint64_t **d_component_cells);
 int cuberille_components_download(cuberille_ctx *ctx, uint32_t *point_component, uint32_t *cell_component,
                                   uint64_t *component_cells, size_t capacity_components);
+/* Keep the largest surface, or drop the specks (new symbols within ABI 13, no struct changed): the last mesh of ctx -- one that
+ * came with components -- is replaced on the device by the part of it that lies in the kept components, order preserved.
+ *   CUBERILLE_KEEP_LARGEST    the one component with the most cells; a tie goes to the smaller component number; K = 0 keeps
+ *                             nothing.  n, host_mask and mask_len are ignored.
+ *   CUBERILLE_KEEP_MIN_CELLS  every component with component_cells[k] >= n (cells as component_cells counts them: with
+ *                             generate_triangles a quad is two).  n = 0 keeps everything, components of zero cells included.
+ *   CUBERILLE_KEEP_MASK       component k is kept when host_mask[k] != 0: host memory of exactly K bytes (mask_len != K, or a null
+ *                             mask with K > 0: CUBERILLE_ERR_ARGUMENT).  The "specified regions" case; a top-n selection is the
+ *                             caller's, from component_cells (K values).
+ * With keepK[k] the decision, kp = keepK[point_component], kc = keepK[cell_component], new_index = cumsum(kp) - 1 and
+ * new_number = cumsum(keepK) - 1:
+ *   points' = points[kp], normals' = normals[kp]; cells' = new_index[cells[kc] - offset] + offset (the offset of cuberille_emit
+ *   stays in the ids); cell pixels' = cell pixels[kc], bit for bit; point_component' = new_number[point_component[kp]],
+ *   cell_component' = new_number[cell_component[kc]]; component_cells' = component_cells[keepK]; K' = the kept.
+ * Every point of a kept component is kept and the compaction is stable, so the new rows are exactly the components of the new
+ * mesh, numbered by smallest point index: a second call on the result is legal and composes, LARGEST behind LARGEST changes
+ * nothing.  Afterwards cuberille_mesh_device / _download / _host / _write_vtk, cuberille_normals_*, cuberille_cell_pixels_* and
+ * cuberille_components_* speak of the kept mesh (pointers handed out before the call are void).  *n_points, *n_cells and
+ * *n_components receive the new sizes, *ms the device time of the call from one event pair; each pointer may be null.  The walk
+ * counters and the ms_* fields of the extraction's cuberille_result, cuberille_slice_counts, cuberille_debug_bits and the sizes
+ * that steer the next blind launch stay the extraction's; the next extraction on the context gives what a fresh context gives.
+ * On the device: the decision per component, three exclusive scans (components, points, cells) whose totals reach the host in
+ * one read, and a scatter out of place into spare rows sized by the kept counts -- buffers of the context, reserved by this call
+ * alone and freed by cuberille_set_components(ctx, 0) -- after which the buffers change places.  When everything is kept no byte
+ * moves; when nothing is kept the mesh is empty (null component pointers, empty downloads, K = 0).
+ * Refused, the context left usable and the mesh as it was: CUBERILLE_ERR_STATE with a message that says "components" when
+ * there is no mesh, the last extraction ran with components off, the mesh is a slab's, or a step is open; CUBERILLE_ERR_ARGUMENT
+ * for an unknown rule or the mask errors above; CUBERILLE_ERR_LIMIT with 2^32 cells or more (the cell positions are 32-bit
+ * sums); CUBERILLE_ERR_HIP when a row cannot be reserved -- every row is reserved before the first scatter. */
+enum { CUBERILLE_KEEP_LARGEST = 0, CUBERILLE_KEEP_MIN_CELLS = 1, CUBERILLE_KEEP_MASK = 2 };
+int cuberille_keep_components(cuberille_ctx *ctx, int rule, uint64_t n, const uint8_t *host_mask, size_t mask_len,
+                              uint64_t *n_points, uint64_t *n_cells, uint64_t *n_components, float *ms);
 /* Test aid (new symbol): the coefficient image of the last B-spline extraction on ctx (one that projected at least one
  * vertex), x fastest, coefficient_bits wide.  CUBERILLE_ERR_STATE when there is none, CUBERILLE_ERR_ARGUMENT when
  * capacity_bytes is smaller than the image. */

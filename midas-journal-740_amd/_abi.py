@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("CUBERILLE_LIB") or os.path.join(CSRC, "libcuberille_h
 OK, ERR_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_HALO, ERR_LIMIT, ERR_SOURCE, RETRY = range(9)
 SLAB_THIN_HALO = 1
 INTERP_LINEAR, INTERP_BSPLINE = 0, 1   # cuberille_set_interpolator
+KEEP_LARGEST, KEEP_MIN_CELLS, KEEP_MASK = 0, 1, 2   # cuberille_keep_components: the rule
 ESCAPED_OVERFLOW = 1 << 62          # Extractor.escaped_count(): more walks escaped than the library's list holds
 
 # every symbol include/cuberille_hip.h declares (tests check the built library exports them all)
@@ -39,6 +40,7 @@ EXPORTS = [
     "cuberille_set_point_normals", "cuberille_normals_device", "cuberille_normals_download", "cuberille_debug_device_bytes",
     "cuberille_set_cell_pixels", "cuberille_cell_pixels_device", "cuberille_cell_pixels_download",
     "cuberille_set_components", "cuberille_components_info", "cuberille_components_device", "cuberille_components_download",
+    "cuberille_keep_components",
 ]
 GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
@@ -156,6 +158,8 @@ def lib():
     L.cuberille_components_info.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cuberille_components_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.cuberille_components_download.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    L.cuberille_keep_components.argtypes = [vp, C.c_int, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

@@ -147,6 +147,11 @@ struct cuberille_ctx {
   bool countComponents = false;          // ... the setting as the running count/emit pair found it
   bool haveComponents = false;           // ... and whether the last mesh came with them
   u64 nComponents = 0;                   // ... K of the last mesh
+  // cuberille_keep_components: the decision and the scans' rows, and the spare rows the kept mesh is written to before the
+  // buffers change places (reserved by that call alone, sized by the kept counts; freed with the component rows) ...
+  DevBuf keepSel, keepScan, sparePoints, spareCells, spareNormals, spareCellPix, spareCompPoint, spareCompCell, spareCompCount;
+  u64 *hostKeep = nullptr;               // ... K', n_points', n_cells' on their way to the host (pinned; allocated by the first call)
+  hipEvent_t keepEv[2] = {};             // ... and the call's one event pair (created by the first call)
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
   Totals *hostTotals = nullptr;          // pinned
@@ -214,7 +219,9 @@ std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
   return {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
           &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
           &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals, &c->cellPix,
-          &c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan};
+          &c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan,
+          &c->keepSel, &c->keepScan, &c->sparePoints, &c->spareCells, &c->spareNormals, &c->spareCellPix, &c->spareCompPoint,
+          &c->spareCompCell, &c->spareCompCount};
 }
 
 // cuberille_set_components: the rows as their kernels take them
@@ -495,6 +502,8 @@ void cuberille_destroy(cuberille_ctx *c) {
   if (c->hostOcc) (void)hipHostFree(c->hostOcc);
   if (c->hostRows) (void)hipHostFree(c->hostRows);
   if (c->hostK) (void)hipHostFree(c->hostK);
+  if (c->hostKeep) (void)hipHostFree(c->hostKeep);
+  for (int i = 0; i < 2; i++) if (c->keepEv[i]) (void)hipEventDestroy(c->keepEv[i]);
   for (int i = 0; i < 2; i++) {
     if (c->stage[i]) (void)hipHostFree(c->stage[i]);
     if (c->stageFree[i]) (void)hipEventDestroy(c->stageFree[i]);
@@ -893,6 +902,14 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->aliasBelowBuffer = false;
   c->aliasMustResolve = false;
   c->aliasZ = -1;
+  // (cuberille_keep_components let the mesh's rows change places with spare rows sized by the kept counts: the mesh is gone now,
+  //  and the larger buffer of each pair is the one the extraction was sized for -- back in its place, nothing is reserved again)
+  for (auto pair : {std::make_pair(&c->points, &c->sparePoints), std::make_pair(&c->cells, &c->spareCells),
+                    std::make_pair(&c->normals, c->pointNormals ? &c->spareNormals : &c->normals),
+                    std::make_pair(&c->cellPix, c->cellPixels ? &c->spareCellPix : &c->cellPix),
+                    std::make_pair(&c->compPoint, &c->spareCompPoint), std::make_pair(&c->compCell, &c->spareCompCell),
+                    std::make_pair(&c->compCount, &c->spareCompCount)})
+    if (pair.second->cap > pair.first->cap) std::swap(*pair.first, *pair.second);
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
@@ -2356,11 +2373,32 @@ int cuberille_set_components(cuberille_ctx *c, int on) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
   c->components = on != 0;
-  if (!on && (c->compScan.p || c->compParent.p)) {
+  if (!on && (c->compScan.p || c->compParent.p || c->keepSel.p)) {
     // off: the context holds what one that never heard of the setting holds (the last mesh stays, its components go)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
     for (DevBuf *b : {&c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan}) b->release();
+    // (... and what cuberille_keep_components reserved: its scratch and the spare rows.  Where a kept mesh lives in a row sized
+    //  by the kept counts, it moves back into the buffer the extraction was sized for -- one copy of the kept size -- so that the
+    //  context holds the buffers it held before the setting was on, and the next extraction reserves nothing again)
+    if (c->haveMesh) {
+      const size_t pb = (size_t)c->res.n_points * 3 * sizeof(float), cb = (size_t)c->res.n_cells * c->res.verts_per_cell * sizeof(u64);
+      const size_t xb = c->haveCellPixels ? (size_t)c->res.n_cells * pixel_size(c->pixel_type) : 0;
+      struct { DevBuf *row, *spare; size_t bytes; } rows[] = {{&c->points, &c->sparePoints, pb}, {&c->cells, &c->spareCells, cb},
+                                                              {&c->normals, &c->spareNormals, c->haveNormals ? pb : 0},
+                                                              {&c->cellPix, &c->spareCellPix, xb}};
+      for (auto &r : rows) {
+        if (r.spare->cap <= r.row->cap || !r.row->p) continue;
+        if (r.bytes) HIP_TRY(c, hipMemcpyAsync(r.spare->p, r.row->p, r.bytes, hipMemcpyDeviceToDevice, c->stream));
+        std::swap(*r.row, *r.spare);
+      }
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      c->w.points = (float *)c->points.p;
+      c->w.cells = (u64 *)c->cells.p;
+    }
+    for (DevBuf *b : {&c->keepSel, &c->keepScan, &c->sparePoints, &c->spareCells, &c->spareNormals, &c->spareCellPix,
+                      &c->spareCompPoint, &c->spareCompCell, &c->spareCompCount})
+      b->release();
     c->haveComponents = false;
     c->countComponents = false;
     c->nComponents = 0;
@@ -2411,6 +2449,111 @@ int cuberille_components_download(cuberille_ctx *c, uint32_t *point_component, u
     if (const int rc = download_pipelined(c, cell_component, c->compCell.p, (size_t)c->res.n_cells * sizeof(uint32_t))) return rc;
   if (component_cells && c->nComponents)
     if (const int rc = download_pipelined(c, component_cells, c->compCount.p, (size_t)c->nComponents * sizeof(uint64_t))) return rc;
+  return CUBERILLE_OK;
+}
+
+int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint8_t *host_mask, size_t mask_len,
+                              uint64_t *n_points, uint64_t *n_cells, uint64_t *n_components, float *ms) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (rule != CUBERILLE_KEEP_LARGEST && rule != CUBERILLE_KEEP_MIN_CELLS && rule != CUBERILLE_KEEP_MASK)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, "cuberille_keep_components: unknown rule " + std::to_string(rule));
+  if (c->stepMode != 0)
+    return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: a step is open on this context, its mesh and components are not complete");
+  if (!c->haveMesh)
+    return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: no mesh, so no components: call cuberille_extract_* or cuberille_emit first");
+  if (c->slabMode)
+    return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: a slab's mesh has no components (a component does not stop at a slab's face)");
+  if (!c->haveComponents)
+    return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: no components: the last extraction ran with the setting off (cuberille_set_components)");
+  const u64 K = c->nComponents, nP = c->res.n_points, nC = c->res.n_cells;
+  if (rule == CUBERILLE_KEEP_MASK) {
+    if (mask_len != K)
+      return fail(c, CUBERILLE_ERR_ARGUMENT, "cuberille_keep_components: the mesh has " + std::to_string(K) + " components, the mask " +
+                                             std::to_string(mask_len) + " bytes");
+    if (K && !host_mask) return fail(c, CUBERILLE_ERR_ARGUMENT, "cuberille_keep_components: null mask");
+  }
+  // (the cells' positions are 32-bit sums like the labels)
+  if (nC >= 0x100000000ULL)
+    return fail(c, CUBERILLE_ERR_LIMIT, "cuberille_keep_components: cell positions are 32-bit: not offered with 2^32 cells or more");
+  auto report = [&]() {
+    if (n_points) *n_points = c->res.n_points;
+    if (n_cells) *n_cells = c->res.n_cells;
+    if (n_components) *n_components = c->nComponents;
+  };
+  if (ms) *ms = 0.0f;
+  if (!K || !nP) { report(); return CUBERILLE_OK; }          // an empty mesh: all of nothing is kept
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  if (!c->hostKeep) HIP_TRY(c, hipHostMalloc((void **)&c->hostKeep, 3 * sizeof(u64), hipHostMallocDefault));
+  for (int i = 0; i < 2; i++)
+    if (!c->keepEv[i]) HIP_TRY(c, hipEventCreate(&c->keepEv[i]));
+  // decide and number: keep[K], new_number[K], the mask's bytes; the three totals ahead of the scans' levels
+  HIP_TRY(c, c->keepSel.reserve((size_t)K * (2 * sizeof(u32) + 1)));
+  HIP_TRY(c, c->keepScan.reserve(keep_scan_bytes(K, nP, nC)));
+  KeepRows k{};
+  k.keep = (u32 *)c->keepSel.p;
+  k.number = k.keep + K;
+  k.mask = (const uint8_t *)(k.number + K);
+  k.totals = (u64 *)c->keepScan.p;
+  k.scanK = (u32 *)(k.totals + 3);
+  k.scanP = k.scanK + comp_scan_plan(K).entries;
+  k.scanC = k.scanP + comp_scan_plan(nP).entries;
+  const CompRows r = comp_rows(c);
+  HIP_TRY(c, hipEventRecord(c->keepEv[0], s));
+  if (rule == CUBERILLE_KEEP_MASK)
+    HIP_TRY(c, hipMemcpyAsync((void *)k.mask, host_mask, (size_t)K, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, launch_keep_count(c->w, r, k, rule, n, K, nP, nC, s));
+  HIP_TRY(c, hipMemcpyAsync(c->hostKeep, k.totals, 3 * sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));                       // the one read: K', n_points', n_cells'
+  const u64 K2 = c->hostKeep[0], nP2 = c->hostKeep[1], nC2 = c->hostKeep[2];
+  if (K2 > K || nP2 > nP || nC2 > nC) return fail(c, CUBERILLE_ERR_STATE, "internal: cuberille_keep_components kept more than there is");
+  if (K2 != K && K2 != 0) {
+    // decided: the spare rows by the kept counts, every one of them before the first scatter (a failure leaves the mesh as it is)
+    const size_t nv = (size_t)c->res.verts_per_cell, pix = c->haveCellPixels ? pixel_size(c->pixel_type) : 0;
+    HIP_TRY(c, c->sparePoints.reserve((size_t)nP2 * 3 * sizeof(float)));
+    HIP_TRY(c, c->spareCells.reserve((size_t)(nC2 ? nC2 : 1) * nv * sizeof(u64)));
+    if (c->haveNormals) HIP_TRY(c, c->spareNormals.reserve((size_t)nP2 * 3 * sizeof(float)));
+    if (pix) HIP_TRY(c, c->spareCellPix.reserve((size_t)(nC2 ? nC2 : 1) * pix));
+    HIP_TRY(c, c->spareCompPoint.reserve((size_t)nP2 * sizeof(u32)));
+    HIP_TRY(c, c->spareCompCell.reserve((size_t)(nC2 ? nC2 : 1) * sizeof(u32)));
+    HIP_TRY(c, c->spareCompCount.reserve((size_t)K2 * sizeof(u64)));
+    KeepOut o{};
+    o.points = (float *)c->sparePoints.p;
+    o.normals = c->haveNormals ? (float *)c->spareNormals.p : nullptr;
+    o.cells = (u64 *)c->spareCells.p;
+    o.cellPix = pix ? c->spareCellPix.p : nullptr;
+    o.pointComp = (u32 *)c->spareCompPoint.p;
+    o.cellComp = (u32 *)c->spareCompCell.p;
+    o.compCells = (u64 *)c->spareCompCount.p;
+    Workspace w = c->w;
+    w.points = (float *)c->points.p;
+    w.cells = (u64 *)c->cells.p;
+    HIP_TRY(c, launch_keep_scatter(w, r, k, o, c->haveNormals ? (const float *)c->normals.p : nullptr, pix ? c->cellPix.p : nullptr,
+                                   (int)pix, c->prm.triangles, c->pointOffset, K, nP, nC, s));
+  }
+  HIP_TRY(c, hipEventRecord(c->keepEv[1], s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->keepEv[0], c->keepEv[1]));
+  if (K2 != K) {
+    if (K2) {
+      // the kept mesh is complete in the spare rows: the buffers change places (the earlier ones are the next call's spare rows)
+      std::swap(c->points, c->sparePoints);
+      std::swap(c->cells, c->spareCells);
+      if (c->haveNormals) std::swap(c->normals, c->spareNormals);
+      if (c->haveCellPixels) std::swap(c->cellPix, c->spareCellPix);
+      std::swap(c->compPoint, c->spareCompPoint);
+      std::swap(c->compCell, c->spareCompCell);
+      std::swap(c->compCount, c->spareCompCount);
+      c->w.points = (float *)c->points.p;
+      c->w.cells = (u64 *)c->cells.p;
+    }
+    // (the walk counters, the ms_* fields, the count's tables and the sizes of the next blind launch stay the extraction's)
+    c->res.n_points = nP2;
+    c->res.n_cells = nC2;
+    c->nComponents = K2;
+    c->hostMeshValid = false;
+  }
+  report();
   return CUBERILLE_OK;
 }
 

@@ -298,5 +298,37 @@ struct CompRows {
 hipError_t launch_components(const Workspace &w, const CompRows &r, int triangles, u64 pointOffset, u64 nP, u64 nQ, int dyn,
                              hipStream_t s);
 
+// cuberille_keep_components: what the compaction by component works through, buffers of the context reserved by that call alone.
+// Three exclusive scans with the numbering's block plan (one per COMP_SCAN_B entries, comp_scan_plan): over keep[k], over
+// keep[point_component[p]] and over keep[cell_component[c]]; their totals lie side by side for the one read.
+struct KeepRows {
+  u32 *keep;             // [K] 0 / 1: the decision per component
+  u32 *number;           // [K] new_number: the exclusive scan of keep
+  const uint8_t *mask;   // [K] CUBERILLE_KEEP_MASK: the caller's bytes as uploaded (else unused)
+  u64 *totals;           // [3] K', n_points', n_cells'
+  u32 *scanK, *scanP, *scanC;   // the levels of block sums of the three scans (comp_scan_plan of K, n_points, n_cells entries each)
+};
+inline size_t keep_scan_bytes(u64 K, u64 nP, u64 nC) {
+  return 3 * sizeof(u64) + (comp_scan_plan(K).entries + comp_scan_plan(nP).entries + comp_scan_plan(nC).entries) * sizeof(u32);
+}
+// the kept mesh's rows: spare buffers sized by the kept counts (normals / cellPix: null where the mesh has none)
+struct KeepOut {
+  float *points, *normals;
+  u64 *cells;
+  void *cellPix;
+  u32 *pointComp, *cellComp;
+  u64 *compCells;
+};
+// Decide (rule: CUBERILLE_KEEP_*, n: the MIN_CELLS bound) and number: k.keep, and the three scans as far as their totals.  Reads
+// r.compCells, r.pointComp, r.cellComp; writes nothing of the mesh.  K, nP >= 1; nC: cells (two per quad with triangles).
+hipError_t launch_keep_count(const Workspace &w, const CompRows &r, const KeepRows &k, int rule, u64 n, u64 K, u64 nP, u64 nC,
+                             hipStream_t s);
+// Scatter, out of place and stable: every row of the mesh in w.points / w.cells (normalsIn, cellPixIn: null where there are
+// none; pixBytes: the size of a cell pixel) into `o`, ids through new_index (left in r.parent) with pointOffset taken off and put
+// back, labels through k.number.  Behind launch_keep_count on `s`.
+hipError_t launch_keep_scatter(const Workspace &w, const CompRows &r, const KeepRows &k, const KeepOut &o, const float *normalsIn,
+                               const void *cellPixIn, int pixBytes, int triangles, u64 pointOffset, u64 K, u64 nP, u64 nC,
+                               hipStream_t s);
+
 }  // namespace cuberille
 #endif

@@ -4292,6 +4292,145 @@ __global__ __launch_bounds__(256) void k_comp_relabel_cells(const u64 *__restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// K3d: compaction by component (cuberille_keep_components), on the rows the component pass left.
+//   k_keep_largest, k_keep_min_cells, k_keep_mask
+//                     keep[k] = 0 / 1: the one component with the most cells (a tie goes to the smaller number: one block strides
+//                     over K, every thread keeps the first maximum of its ascending stride, the block's reduction prefers the
+//                     smaller number among equals), component_cells[k] >= n, or the caller's byte
+//   k_keep_sums       level 0 of a scan's sums: the kept among each block of COMP_SCAN_B components (label == null), points or
+//                     cells (keep[label[i]]); the levels above and the scan downwards are k_comp_sums and k_comp_scan as the
+//                     numbering runs them, the top block leaving the total
+//   k_keep_scatter_components, k_keep_scatter_points, k_keep_scatter_cells
+//                     each entry's position is its block's prefix (level 0, scanned) plus its rank among the kept of the block --
+//                     ascending with the index, so the compaction is stable.  Out of place: a block reads the old rows and
+//                     writes the spare ones, no block reads what another writes.  new_number[k] and new_index[p] are left for
+//                     every entry (number, newIndex = the free parent row): the cells' ids and both label rows go through them
+// A label at or beyond K, or an id at or beyond n_points, is held by no row the component pass wrote: such an entry is not kept
+// (an id is copied as it stands), and nothing outside the rows is ever addressed.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_largest(const u64 *__restrict__ compCells, u32 *__restrict__ keep, u64 K) {
+  __shared__ u64 bestN[COMP_SCAN_B];
+  __shared__ u64 bestK[COMP_SCAN_B];
+  u64 n = 0, at = ~0ull;                       // (~0: no component seen)
+  for (u64 k = threadIdx.x; k < K; k += COMP_SCAN_B) {
+    const u64 v = compCells[k];
+    if (at == ~0ull || v > n) { n = v; at = k; }
+  }
+  bestN[threadIdx.x] = n;
+  bestK[threadIdx.x] = at;
+  __syncthreads();
+  for (int d = COMP_SCAN_B / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) {
+      const u64 n2 = bestN[threadIdx.x + d], k2 = bestK[threadIdx.x + d], n1 = bestN[threadIdx.x], k1 = bestK[threadIdx.x];
+      if (k2 != ~0ull && (k1 == ~0ull || n2 > n1 || (n2 == n1 && k2 < k1))) {
+        bestN[threadIdx.x] = n2;
+        bestK[threadIdx.x] = k2;
+      }
+    }
+    __syncthreads();
+  }
+  const u64 winner = bestK[0];
+  for (u64 k = threadIdx.x; k < K; k += COMP_SCAN_B) keep[k] = k == winner ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_keep_min_cells(const u64 *__restrict__ compCells, u32 *__restrict__ keep, u64 K, u64 n) {
+  const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < K) keep[k] = compCells[k] >= n ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_keep_mask(const uint8_t *__restrict__ mask, u32 *__restrict__ keep, u64 K) {
+  const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < K) keep[k] = mask[k] != 0 ? 1u : 0u;
+}
+
+// keep of entry i of a scan: the component's own flag (label == null), or that of the entry's component
+__device__ __forceinline__ u32 keep_flag(const u32 *__restrict__ keep, const u32 *__restrict__ label, u64 i, u64 n, u64 K, u32 &k) {
+  k = 0;
+  if (i >= n) return 0u;
+  k = label ? label[i] : (u32)i;
+  return k < K ? keep[k] : 0u;
+}
+
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_sums(const u32 *__restrict__ keep, const u32 *__restrict__ label,
+                                                           u32 *__restrict__ sums, u64 n, u64 K) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  const u64 i = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  u32 k, total;
+  (void)comp_block_scan(keep_flag(keep, label, i, n, K, k), waveSum, total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_scatter_components(const u32 *__restrict__ keep, const u32 *__restrict__ base,
+                                                                         const u64 *__restrict__ compCells, u32 *__restrict__ number,
+                                                                         u64 *__restrict__ compCellsOut, u64 K) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  const u64 i = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  u32 k, total;
+  const u32 f = keep_flag(keep, nullptr, i, K, K, k);
+  const u32 at = comp_block_scan(f, waveSum, total) + base[blockIdx.x];
+  if (i < K) number[i] = at;
+  if (f) compCellsOut[at] = compCells[i];
+}
+
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_scatter_points(const float *__restrict__ points, const float *__restrict__ normals,
+                                                                     const u32 *__restrict__ pointComp, const u32 *__restrict__ keep,
+                                                                     const u32 *__restrict__ number, const u32 *__restrict__ base,
+                                                                     u32 *__restrict__ newIndex, float *__restrict__ pointsOut,
+                                                                     float *__restrict__ normalsOut, u32 *__restrict__ pointCompOut,
+                                                                     u64 nP, u64 K) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  const u64 p = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  u32 k, total;
+  const u32 f = keep_flag(keep, pointComp, p, nP, K, k);
+  const u32 at = comp_block_scan(f, waveSum, total) + base[blockIdx.x];
+  if (p < nP) newIndex[p] = at;
+  if (!f) return;
+  const float x = points[3 * p], y = points[3 * p + 1], z = points[3 * p + 2];
+  pointsOut[3 * (u64)at] = x;
+  pointsOut[3 * (u64)at + 1] = y;
+  pointsOut[3 * (u64)at + 2] = z;
+  if (normals) {
+    const float nx = normals[3 * p], ny = normals[3 * p + 1], nz = normals[3 * p + 2];
+    normalsOut[3 * (u64)at] = nx;
+    normalsOut[3 * (u64)at + 1] = ny;
+    normalsOut[3 * (u64)at + 2] = nz;
+  }
+  pointCompOut[at] = number[k];
+}
+
+template <int NV>
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_scatter_cells(const u64 *__restrict__ cells, const u32 *__restrict__ cellComp,
+                                                                    const u32 *__restrict__ keep, const u32 *__restrict__ number,
+                                                                    const u32 *__restrict__ newIndex, const u32 *__restrict__ base,
+                                                                    const void *__restrict__ pixIn, u64 *__restrict__ cellsOut,
+                                                                    u32 *__restrict__ cellCompOut, void *__restrict__ pixOut,
+                                                                    int pixBytes, u64 nP, u64 nC, u64 K, u64 pointOffset) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  const u64 c = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  u32 k, total;
+  const u32 f = keep_flag(keep, cellComp, c, nC, K, k);
+  const u32 at = comp_block_scan(f, waveSum, total) + base[blockIdx.x];
+  if (!f) return;
+  // the wave's id loads are 64 consecutive cells whose points are near each other: the gathers as they fall
+  u64 id[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) id[i] = cells[c * NV + i];
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    const u64 old = id[i] - pointOffset;
+    if (old < nP) id[i] = (u64)newIndex[old] + pointOffset;
+  }
+#pragma unroll
+  for (int i = 0; i < NV; i++) cellsOut[(u64)at * NV + i] = id[i];
+  cellCompOut[at] = number[k];
+  // the cell's pixel in its own width, bit for bit (pixBytes is the same in every lane)
+  if (pixBytes == 1) ((uint8_t *)pixOut)[at] = ((const uint8_t *)pixIn)[c];
+  else if (pixBytes == 2) ((uint16_t *)pixOut)[at] = ((const uint16_t *)pixIn)[c];
+  else if (pixBytes == 4) ((u32 *)pixOut)[at] = ((const u32 *)pixIn)[c];
+  else if (pixBytes == 8) ((u64 *)pixOut)[at] = ((const u64 *)pixIn)[c];
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <class F>
@@ -5091,6 +5230,59 @@ hipError_t launch_components(const Workspace &w, const CompRows &r, int triangle
     else
       hipLaunchKernelGGL(k_comp_relabel_cells<4>, perSpan, block, 0, s, w.cells, r.pointComp, r.cellComp, r.compCells, tot, dyn, nP, nQ,
                          pointOffset);
+  }
+  return hipGetLastError();
+}
+
+// One exclusive scan of cuberille_keep_components as far as its total: the kept per block (k_keep_sums), the sums up the levels,
+// the top level scanned by one block (its total to *total), the levels below scanned downwards -- level 0 is then every block's
+// prefix, which the scatter kernels add their rank to.
+static void keep_scan(const u32 *keep, const u32 *label, u32 *levels, u64 *total, u64 n, u64 K, const Totals *tot, hipStream_t s) {
+  const CompScanPlan plan = comp_scan_plan(n);
+  const dim3 scanBlock(COMP_SCAN_B);
+  hipLaunchKernelGGL(k_keep_sums, dim3((unsigned)plan.len[0]), scanBlock, 0, s, keep, label, levels + plan.off[0], n, K);
+  for (int l = 1; l < plan.levels; l++)
+    hipLaunchKernelGGL(k_comp_sums, dim3((unsigned)plan.len[l]), scanBlock, 0, s, levels + plan.off[l - 1], levels + plan.off[l], l,
+                       tot, 0, n);
+  for (int l = plan.levels - 1; l >= 0; l--) {
+    const bool top = l == plan.levels - 1;
+    hipLaunchKernelGGL(k_comp_scan, dim3(top ? 1u : grid_for(plan.len[l], COMP_SCAN_B, 0)), scanBlock, 0, s, levels + plan.off[l],
+                       top ? (const u32 *)nullptr : levels + plan.off[l + 1], top ? total : (u64 *)nullptr, l, tot, 0, n);
+  }
+}
+
+hipError_t launch_keep_count(const Workspace &w, const CompRows &r, const KeepRows &k, int rule, u64 n, u64 K, u64 nP, u64 nC,
+                             hipStream_t s) {
+  if (!K || !nP) return hipErrorInvalidValue;
+  const dim3 block(256), perComponent(grid_for(K, 256, 0));
+  if (rule == CUBERILLE_KEEP_LARGEST) hipLaunchKernelGGL(k_keep_largest, dim3(1), dim3(COMP_SCAN_B), 0, s, r.compCells, k.keep, K);
+  else if (rule == CUBERILLE_KEEP_MIN_CELLS) hipLaunchKernelGGL(k_keep_min_cells, perComponent, block, 0, s, r.compCells, k.keep, K, n);
+  else if (rule == CUBERILLE_KEEP_MASK) hipLaunchKernelGGL(k_keep_mask, perComponent, block, 0, s, k.mask, k.keep, K);
+  else return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(k.totals, 0, 3 * sizeof(u64), s);     // (a mesh without cells runs no cell scan)
+  if (e != hipSuccess) return e;
+  keep_scan(k.keep, nullptr, k.scanK, k.totals, K, K, w.totals, s);
+  keep_scan(k.keep, r.pointComp, k.scanP, k.totals + 1, nP, K, w.totals, s);
+  if (nC) keep_scan(k.keep, r.cellComp, k.scanC, k.totals + 2, nC, K, w.totals, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_keep_scatter(const Workspace &w, const CompRows &r, const KeepRows &k, const KeepOut &o, const float *normalsIn,
+                               const void *cellPixIn, int pixBytes, int triangles, u64 pointOffset, u64 K, u64 nP, u64 nC,
+                               hipStream_t s) {
+  const dim3 scanBlock(COMP_SCAN_B);
+  hipLaunchKernelGGL(k_keep_scatter_components, dim3((unsigned)comp_scan_plan(K).len[0]), scanBlock, 0, s, k.keep, k.scanK, r.compCells,
+                     k.number, o.compCells, K);
+  hipLaunchKernelGGL(k_keep_scatter_points, dim3((unsigned)comp_scan_plan(nP).len[0]), scanBlock, 0, s, w.points, normalsIn, r.pointComp,
+                     k.keep, k.number, k.scanP, r.parent, o.points, o.normals, o.pointComp, nP, K);
+  if (nC) {
+    const dim3 perCell((unsigned)comp_scan_plan(nC).len[0]);
+    if (triangles)
+      hipLaunchKernelGGL(k_keep_scatter_cells<3>, perCell, scanBlock, 0, s, w.cells, r.cellComp, k.keep, k.number, r.parent, k.scanC,
+                         cellPixIn, o.cells, o.cellComp, o.cellPix, cellPixIn ? pixBytes : 0, nP, nC, K, pointOffset);
+    else
+      hipLaunchKernelGGL(k_keep_scatter_cells<4>, perCell, scanBlock, 0, s, w.cells, r.cellComp, k.keep, k.number, r.parent, k.scanC,
+                         cellPixIn, o.cells, o.cellComp, o.cellPix, cellPixIn ? pixBytes : 0, nP, nC, K, pointOffset);
   }
   return hipGetLastError();
 }

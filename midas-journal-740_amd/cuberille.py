@@ -552,6 +552,32 @@ class Extractor:
             self._ctx, C.c_void_p(pc.ctypes.data), C.c_void_p(cc.ctypes.data), C.c_void_p(counts.ctypes.data), k))
         return pc, cc, counts
 
+    _KEEP_RULES = {"largest": _abi.KEEP_LARGEST, "min_cells": _abi.KEEP_MIN_CELLS, "mask": _abi.KEEP_MASK}
+
+    def keep_components(self, rule, n=0, mask=None):
+        """Compact the last mesh by component on the device (cuberille_keep_components): rule "largest" (the one component
+        with the most cells, a tie to the smaller number), "min_cells" (every component of at least n cells) or "mask"
+        (component k is kept when mask[k] is non-zero: K entries), or the _abi.KEEP_* constants.  The mesh must have come
+        with components (set_components).  download(), mesh_host(), download_normals(), download_cell_pixels(),
+        download_components(), n_components() and write_vtk() then speak of the kept mesh; self.result becomes a copy with
+        the new n_points and n_cells, its counters and times those of the extraction.  Returns
+        (n_points, n_cells, n_components, ms)."""
+        rule = self._KEEP_RULES.get(rule, rule) if isinstance(rule, str) else int(rule)
+        if isinstance(rule, str):
+            raise _abi.CuberilleError(_abi.ERR_ARGUMENT, "keep_components: unknown rule %r" % (rule,))
+        m, ptr, length = None, None, 0
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            ptr, length = C.c_void_p(m.ctypes.data), int(m.size)
+        npnt, ncell, k, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _abi.check(self._ctx, self._lib.cuberille_keep_components(self._ctx, rule, int(n), ptr, length, C.byref(npnt), C.byref(ncell),
+                                                                  C.byref(k), C.byref(ms)))
+        if self.result is not None:
+            res = type(self.result).from_buffer_copy(self.result)      # (the caller's result of the extraction stays as it was)
+            res.n_points, res.n_cells = npnt.value, ncell.value
+            self.result = res
+        return int(npnt.value), int(ncell.value), int(k.value), float(ms.value)
+
     def device_bytes(self):
         """Bytes of device memory the context's workspace holds at this moment (cuberille_debug_device_bytes)."""
         n = C.c_size_t()
@@ -827,6 +853,8 @@ class CuberilleImageToMeshFilter:
     _normals = False       # SetGeneratePointNormals: off (class level for the same reason)
     _cell_pixels_on = False   # SetSavePixelAsCellData: off (likewise)
     _components_on = False    # SetGenerateComponents: off (likewise)
+    _keep_largest = False     # SetKeepLargestComponent: off (likewise)
+    _min_component_cells = 0  # SetMinimumComponentCells: none (likewise)
 
     _NOT_IN_A_GROUP = (
         ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
@@ -834,7 +862,9 @@ class CuberilleImageToMeshFilter:
         ("_band_on", False, "a band (InsideBandOn / cuberille_set_band)", "the binary image belongs to one context's whole volume"),
         ("_normals", False, "point normals (SetGeneratePointNormals / cuberille_set_point_normals)", "they belong to one context's whole volume"),
         ("_cell_pixels_on", False, "cell pixels (SetSavePixelAsCellData / cuberille_set_cell_pixels)", "they belong to one context's whole volume"),
-        ("_components_on", False, "components (SetGenerateComponents / cuberille_set_components)", "a component does not stop at a slab's face"))
+        ("_components_on", False, "components (SetGenerateComponents / cuberille_set_components)", "a component does not stop at a slab's face"),
+        ("_keep_largest", False, "the largest component (SetKeepLargestComponent / cuberille_keep_components)", "a component does not stop at a slab's face"),
+        ("_min_component_cells", 0, "a minimum of cells per component (SetMinimumComponentCells / cuberille_keep_components)", "a component does not stop at a slab's face"))
 
     def __init__(self, device=0, devices=None):
         self._device = device
@@ -869,6 +899,8 @@ class CuberilleImageToMeshFilter:
         self._cell_pixels = None                  # GetCellPixels(): one pixel per cell of the last Update(), or None
         self._components_on = False               # SetGenerateComponents: off
         self._components = None                   # (point_component, cell_component, component_cells) of the last Update(), or None
+        self._keep_largest = False                # SetKeepLargestComponent: off
+        self._min_component_cells = 0             # SetMinimumComponentCells: none
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -1146,6 +1178,33 @@ class CuberilleImageToMeshFilter:
         """K of the last Update() with the switch on; 0 with it off."""
         return 0 if self._components is None else int(self._components[2].shape[0])
 
+    def SetKeepLargestComponent(self, b):
+        """Not in the reference.  On: Update() keeps the one connected surface with the most cells and drops the rest, on the
+        device behind the extraction (cuberille_keep_components, LARGEST; a tie goes to the component with the smaller first
+        point).  Turns the components on for that extraction by itself; the output, the normals, the cell pixels and the
+        component getters describe the kept mesh.  Default off."""
+        self._keep_largest = bool(b)
+
+    def GetKeepLargestComponent(self):
+        return self._keep_largest
+
+    def KeepLargestComponentOn(self):
+        self.SetKeepLargestComponent(True)
+
+    def KeepLargestComponentOff(self):
+        self.SetKeepLargestComponent(False)
+
+    def SetMinimumComponentCells(self, n):
+        """Not in the reference.  n > 0: Update() drops every connected surface of fewer than n cells (cuberille_keep_components,
+        MIN_CELLS; with triangles a quad is two cells), behind the largest-component selection where both are set.  Turns the
+        components on for that extraction by itself.  Default 0: nothing is dropped."""
+        if int(n) < 0:
+            raise ValueError("SetMinimumComponentCells: a count of cells, got %r" % (n,))
+        self._min_component_cells = int(n)
+
+    def GetMinimumComponentCells(self):
+        return self._min_component_cells
+
     def SetLinearInterpolator(self):
         """Back to the default interpolator (LinearInterpolateImageFunction<TImage, double>)."""
         self._bspline = None
@@ -1198,15 +1257,21 @@ class CuberilleImageToMeshFilter:
         self._point_normals = None
         self._extractor.set_cell_pixels(self._cell_pixels_on)
         self._cell_pixels = None
-        self._extractor.set_components(self._components_on)
+        keep = self._keep_largest or self._min_component_cells > 0
+        self._extractor.set_components(self._components_on or keep)
         self._components = None
         self.last_result = self._extractor.extract_host(vol, prm)
+        # (the mesh is compacted on the device before anything of it comes to the host)
+        if self._keep_largest:
+            self._extractor.keep_components(_abi.KEEP_LARGEST)
+        if self._min_component_cells > 0:
+            self._extractor.keep_components(_abi.KEEP_MIN_CELLS, self._min_component_cells)
         self._output = self._extractor.download()
         if self._normals:
             self._point_normals = self._extractor.download_normals()
         if self._cell_pixels_on:
             self._cell_pixels = self._extractor.download_cell_pixels()
-        if self._components_on:
+        if self._components_on or keep:
             self._components = self._extractor.download_components()
         self.last_number_of_slabs = 1
 

@@ -317,6 +317,21 @@ public:
   const std::vector<uint64_t> &GetComponentCellCounts() const { return m_ComponentCellCounts; }
   size_t GetNumberOfComponents() const { return m_ComponentCellCounts.size(); }
 
+  /** Not in the reference: what a caller of itk::ConnectedRegionsMeshFilter does behind the filter -- keep the largest surface,
+   *  drop the specks -- on the device, before the output mesh is filled (cuberille_keep_components).
+   *  KeepLargestComponentOn(): Update() keeps the one connected surface with the most cells (a tie goes to the component with
+   *  the smaller first point id) and drops every other.  SetMinimumComponentCells(n), n > 0: Update() drops every surface of
+   *  fewer than n cells (with GenerateTriangleFaces a quad is two cells); behind the largest-component selection where both are
+   *  set.  Either one turns the components on for that Update() by itself.  The output mesh, its cell data, GetPointNormals(),
+   *  GetCellPixels(), Get*Components() and GetNumberOfComponents() all describe the kept mesh, whose points and cells keep their
+   *  order and are numbered anew; a bound above every component yields an empty mesh.  Not offered with SetDevices of more than
+   *  one device or with an interpolator that takes the host walk.  Default: off, 0. */
+  itkGetMacro(KeepLargestComponent, bool);
+  itkSetMacro(KeepLargestComponent, bool);
+  itkBooleanMacro(KeepLargestComponent);
+  itkGetMacro(MinimumComponentCells, unsigned long long);
+  itkSetMacro(MinimumComponentCells, unsigned long long);
+
   /** Not in the reference.  More than one device id -- ids may repeat: several contexts on one GPU -- makes Update() cut
    *  the volume into z-slabs of equal thickness, one per member of a context group (cuberille_group_extract_host): each
    *  slab and its halo go from the input's buffer straight to its own device, and one mesh comes back, the same ids, cell
@@ -364,6 +379,8 @@ private:
   bool m_SavePixelAsCellData;
   std::vector<InputPixelType> m_CellPixels;   // GetCellPixels(): filled by Update() with the switch on, else empty
   bool m_GenerateComponents;
+  bool m_KeepLargestComponent;
+  unsigned long long m_MinimumComponentCells;
   std::vector<uint32_t> m_PointComponents, m_CellComponents;   // filled by Update() with the switch on, else empty
   std::vector<uint64_t> m_ComponentCellCounts;
   bool m_InsideBand;

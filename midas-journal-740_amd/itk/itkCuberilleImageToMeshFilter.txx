@@ -503,6 +503,8 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_GeneratePointNormals = false;
   m_SavePixelAsCellData = false;
   m_GenerateComponents = false;
+  m_KeepLargestComponent = false;
+  m_MinimumComponentCells = 0;
   m_InsideBand = false;
   m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
   m_BandInside = NumericTraits<InputPixelType>::One;
@@ -759,6 +761,12 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   const bool grouped = m_Devices.size() > 1 && !deviceBSpline && !m_ReproduceStaleGradient &&
                        !(prm.project_vertices && prm.gradient_variant == CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN);
   m_LastUpdateGrouped = false;
+  // KeepLargestComponentOn() / SetMinimumComponentCells(n): either one turns the components on for this extraction by itself
+  const bool keepComponents = m_KeepLargestComponent || m_MinimumComponentCells > 0;
+  const bool components = m_GenerateComponents || keepComponents;
+  if (keepComponents && hostWalk)
+    itkExceptionMacro(<< "keeping components (KeepLargestComponentOn / SetMinimumComponentCells / cuberille_keep_components) is not "
+                         "offered with an interpolator that takes the host walk: its triangles are made on the host");
   cuberille_result res;
   double extractStart;
   if (grouped)
@@ -772,7 +780,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       // (point normals on the members: the group's extraction refuses them likewise)
       (void)cuberille_set_point_normals(cuberille_group_context(m_Group, i), m_GeneratePointNormals ? 1 : 0);
       (void)cuberille_set_cell_pixels(cuberille_group_context(m_Group, i), m_SavePixelAsCellData ? 1 : 0);
-      (void)cuberille_set_components(cuberille_group_context(m_Group, i), m_GenerateComponents ? 1 : 0);
+      (void)cuberille_set_components(cuberille_group_context(m_Group, i), components ? 1 : 0);
       }
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_group_extract_host(m_Group, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
@@ -796,11 +804,19 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< "cuberille_set_point_normals: " << cuberille_last_error(m_Context));
     if (cuberille_set_cell_pixels(m_Context, m_SavePixelAsCellData ? 1 : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_cell_pixels: " << cuberille_last_error(m_Context));
-    if (cuberille_set_components(m_Context, m_GenerateComponents ? 1 : 0) != CUBERILLE_OK)
+    if (cuberille_set_components(m_Context, components ? 1 : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_components: " << cuberille_last_error(m_Context));
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
+    // the mesh is compacted on the device before anything of it comes to the host: everything below describes the kept mesh
+    if (m_KeepLargestComponent &&
+        cuberille_keep_components(m_Context, CUBERILLE_KEEP_LARGEST, 0, 0, 0, &res.n_points, &res.n_cells, 0, 0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_keep_components: " << cuberille_last_error(m_Context));
+    if (m_MinimumComponentCells > 0 &&
+        cuberille_keep_components(m_Context, CUBERILLE_KEEP_MIN_CELLS, m_MinimumComponentCells, 0, 0, &res.n_points, &res.n_cells, 0,
+                                  0) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_keep_components: " << cuberille_last_error(m_Context));
     m_LastNumberOfSlabs = 1;
     }
   m_LastDeviceSeconds = 1e-3 * res.ms_total;
@@ -836,7 +852,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   m_PointComponents.clear();
   m_CellComponents.clear();
   m_ComponentCellCounts.clear();
-  if (m_GenerateComponents)                   // (the single context: a group has refused above)
+  if (components)                             // (the single context: a group has refused above)
     {
     uint64_t nComponents = 0;
     if (cuberille_components_info(m_Context, &nComponents) != CUBERILLE_OK)
@@ -876,7 +892,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
         m_CellPixels.resize(static_cast<size_t>(res.n_cells));
         for (size_t q = m_CellPixels.size() / 2; q-- > 0;) m_CellPixels[2 * q] = m_CellPixels[2 * q + 1] = m_CellPixels[q];
         }
-      if (m_GenerateComponents)               // likewise: both triangles are of their quad's component (they share its diagonal)
+      if (components)                         // likewise: both triangles are of their quad's component (they share its diagonal)
         {
         m_CellComponents.resize(static_cast<size_t>(res.n_cells));
         for (size_t q = m_CellComponents.size() / 2; q-- > 0;) m_CellComponents[2 * q] = m_CellComponents[2 * q + 1] = m_CellComponents[q];

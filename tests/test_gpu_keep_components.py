@@ -1,0 +1,395 @@
+"""Compaction by component on the GPU (cuberille_keep_components): every row the library hands out after the call against the numpy
+reference of tests/keep_ref.py -- held to the components' definition by tests/test_keep_components.py -- applied to what the
+library itself handed out before the call, compared as bytes.  No tolerance anywhere.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import components_ref as cref
+import keep_ref
+import test_components as cases
+from conftest import ROOT
+from test_cell_pixels import label_volume
+from test_gpu_components import counters, device_copy, params
+
+pytestmark = pytest.mark.gpu
+
+ARG, HIP, STATE = 1, 3, 4
+
+
+@pytest.fixture()
+def ex(pkg):
+    e = pkg.Extractor(0)
+    e.set_components(True)
+    yield e
+    e.close()
+
+
+def snapshot(ex, normals=False, pixels=False, offset=0):
+    """What the library hands out of its present mesh: the arguments of keep_ref.keep."""
+    mesh = ex.download()
+    pc, cc, counts = ex.download_components()
+    assert ex.n_components() == len(counts)
+    return dict(points=mesh.points, cells=mesh.cells, point_component=pc, cell_component=cc, component_cells=counts, offset=offset,
+                normals=ex.download_normals() if normals else None, cell_pixels=ex.download_cell_pixels() if pixels else None)
+
+
+def same(snap, want, what):
+    for name in ("points", "cells", "point_component", "cell_component", "component_cells", "normals", "cell_pixels"):
+        g, w = snap[name], getattr(want, name)
+        assert (g is None) == (w is None), (what, name)
+        if g is not None:
+            assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, g.shape, w.dtype, w.shape)
+            assert g.tobytes() == w.tobytes(), (what, name, "first difference at %d" % int(np.argmax(g.reshape(-1) != w.reshape(-1))))
+
+
+def keep_held(ex, before, rule, n=0, mask=None, what=""):
+    """One keep on the context, held to the reference on `before` -> the snapshot after it."""
+    want = keep_ref.apply(rule, before["points"], before["cells"], before["point_component"], before["cell_component"],
+                          before["component_cells"], n=n, mask=mask, offset=before["offset"], normals=before["normals"],
+                          cell_pixels=before["cell_pixels"])
+    got = ex.keep_components(rule, n, mask)
+    assert got[:3] == (len(want.points), len(want.cells), len(want.component_cells)), (what, got)
+    assert got[3] >= 0.0 and (int(ex.result.n_points), int(ex.result.n_cells)) == got[:2]
+    after = snapshot(ex, before["normals"] is not None, before["cell_pixels"] is not None, before["offset"])
+    same(after, want, what)
+    ptrs = ex.components_device()
+    assert [bool(p) for p in ptrs] == [got[0] > 0, got[1] > 0, got[2] > 0], (what, ptrs)
+    # closure: the rows are the components of the kept mesh
+    cases.same((after["point_component"], after["cell_component"], after["component_cells"]),
+               cref.components(after["cells"], len(after["points"]), before["offset"]), (what, "closure"))
+    return after
+
+
+def rules_of(counts):
+    """Every rule on a mesh with these component counts: (rule, n, mask)."""
+    k = len(counts)
+    low = int(counts.min()) if k else 0
+    out = [("largest", 0, None), ("min_cells", 0, None), ("min_cells", low, None), ("min_cells", low + 1, None),
+           (keep_ref.MASK, 0, np.ones(k, dtype=np.uint8)), ("mask", 0, np.zeros(k, dtype=np.uint8))]
+    if k > 1:
+        first, last = np.zeros(k, dtype=np.uint8), np.zeros(k, dtype=np.uint8)
+        first[0], last[-1] = 1, 7
+        out += [("mask", 0, first), ("mask", 0, last)]
+    return out
+
+
+def test_one_voxel_pairs_and_the_empty_mesh(pkg, ex):
+    for triangles in (0, 1):
+        prm = params(pkg, project=0, triangles=triangles)
+        for name, vox, k in (("one voxel", cases.one_voxel(), 1), ("corner", cases.pair(1, 1, 1), 1), ("edge", cases.pair(0, 1, 1), 1),
+                             ("separated", cases.pair(0, 0, 2), 2)):
+            ex.extract_host(pkg.Volume(vox), prm)
+            counts = ex.download_components()[2]
+            assert len(counts) == k
+            for rule, n, mask in rules_of(counts):
+                ex.extract_host(pkg.Volume(vox), prm)
+                after = keep_held(ex, snapshot(ex), rule, n, mask, (name, triangles, rule, n))
+                if rule == "largest":
+                    # (separated: a tie, component 0 -- the first voxel's cube)
+                    assert len(after["component_cells"]) == 1 and (k == 1 or len(after["points"]) == 8)
+                if mask is not None and not mask.any():
+                    # nothing kept: the accessors of an empty mesh
+                    assert ex.components_device() == (None, None, None) and ex.n_components() == 0
+                    assert len(ex.download().points) == 0 and len(ex.download().cells) == 0
+                    assert ex.keep_components("largest")[:3] == (0, 0, 0)                        # (and a keep on it is legal)
+        # an empty mesh, all outside and all inside: every rule keeps all of nothing
+        for value in (0, 1):
+            ex.extract_host(pkg.Volume(np.full((9, 10, 11), value, dtype=np.uint8)), prm)
+            for rule, n, mask in rules_of(np.zeros(0, dtype=np.uint64)):
+                keep_held(ex, snapshot(ex), rule, n, mask, ("empty", value, rule))
+                assert ex.components_device() == (None, None, None)
+            with pytest.raises(pkg._abi.CuberilleError) as e:
+                ex.keep_components("mask", mask=[1])
+            assert e.value.code == ARG
+
+
+def test_isolated_voxels(pkg, ex):
+    """16 384 cubes that touch nothing, 8 points and 6 quads each with quirk Q1 off: about 131 072 points and 98 304 quads (the mesh
+    is the library's: its exact sizes are not this test's to pin) -- the point scan and the cell scan both take two blocks at
+    their second level."""
+    vol = pkg.Volume(cases.isolated_voxels())
+    prm = params(pkg, project=0, triangles=0, q1=False)
+    ex.extract_host(vol, prm)
+    whole = snapshot(ex)
+    counts = whole["component_cells"]
+    k = len(counts)
+    assert len(whole["points"]) > 256 * 256 + 256 and len(whole["cells"]) > 256 * 256 + 256 and k > 8192 and int(np.median(counts)) == 6
+    last = np.zeros(k, dtype=np.uint8)
+    last[-1] = 1
+    for rule, n, mask in (("mask", 0, (np.arange(k) % 2 == 0)), ("mask", 0, last), ("largest", 0, None), ("min_cells", 6, None),
+                          ("min_cells", 7, None)):
+        ex.extract_host(vol, prm)
+        after = keep_held(ex, whole, rule, n, mask, ("isolated voxels", rule, n))
+        kept = len(after["component_cells"])
+        if rule == "mask":
+            assert kept == int(mask.sum()) and len(after["cells"]) == int(counts[mask != 0].sum())
+        elif rule == "largest":
+            # (all counts equal: a tie, component 0 -- 8 points and 6 quads)
+            assert kept == 1 and int(after["component_cells"][0]) == int(counts.max())
+            winner = int(np.argmax(counts))
+            assert after["points"].tobytes() == whole["points"][whole["point_component"] == winner].tobytes()
+            assert winner == 0 or int(counts[0]) < int(counts[winner])
+        else:
+            # (the cubes at the image's lower faces have fewer quads: 6 and 7 both cut through the counts)
+            assert kept == int((counts >= n).sum()) and 0 <= kept < k
+
+
+def parse_counts(path):
+    tok = open(path, "rb").read().split()
+    return {key.decode(): int(tok[tok.index(key) + 1]) for key in (b"POINTS", b"POLYGONS", b"POINT_DATA", b"CELL_DATA")}
+
+
+@pytest.mark.parametrize("dtype,triangles", ((np.uint8, 1), (np.float32, 0)))
+def test_noise_with_normals_and_cell_pixels(pkg, ex, tmp_path, dtype, triangles):
+    vox = cases.gradient_noise()
+    isos = cases.noise_isos(vox)
+    vol = pkg.Volume(vox.astype(dtype))
+    ex.set_point_normals(True)
+    ex.set_cell_pixels(True)
+    f = 2 if triangles else 1
+    for iso in isos:
+        prm = params(pkg, iso, project=1, triangles=triangles)
+        ex.extract_host(vol, prm)
+        host = ex.mesh_host()
+        assert len(host.points) == int(ex.result.n_points)
+        whole = snapshot(ex, True, True)
+        assert whole["cell_pixels"].dtype == dtype and host.cells.tobytes() == whole["cells"].tobytes()
+        largest = keep_held(ex, whole, "largest", what=("noise", dtype, iso, "largest"))
+        # something is dropped and something is kept: the comparison never runs where nothing happens
+        assert 0 < len(largest["cells"]) < len(whole["cells"]) and 0 < len(largest["points"]) < len(whole["points"])
+        assert len(largest["component_cells"]) == 1 < len(whole["component_cells"])
+        host = ex.mesh_host()                                                   # (taken before the keep: the kept mesh now)
+        assert host.points.tobytes() == largest["points"].tobytes() and host.cells.tobytes() == largest["cells"].tobytes()
+        path = str(tmp_path / "kept.vtk")
+        ex.write_vtk(path)
+        assert parse_counts(path) == {"POINTS": len(largest["points"]), "POLYGONS": len(largest["cells"]),
+                                      "POINT_DATA": len(largest["points"]), "CELL_DATA": len(largest["cells"])}
+        # LARGEST behind LARGEST changes nothing
+        again = keep_held(ex, largest, "largest", what=("noise", iso, "largest twice"))
+        same(again, keep_ref.Kept(**{k: v for k, v in largest.items() if k != "offset"}), "idempotence")
+        # MIN_CELLS, and LARGEST behind it
+        ex.extract_host(vol, prm)
+        specks = keep_held(ex, whole, "min_cells", 1000 * f, what=("noise", dtype, iso, "min_cells"))
+        assert 1 <= len(specks["component_cells"]) < len(whole["component_cells"]) and 0 < len(specks["cells"]) < len(whole["cells"])
+        behind = keep_held(ex, specks, "largest", what=("noise", dtype, iso, "largest behind min_cells"))
+        same(behind, keep_ref.Kept(**{k: v for k, v in largest.items() if k != "offset"}), "composition")
+    if dtype == np.uint8:
+        # iso 160: the winner is component 2, and a quarter of the cells goes
+        counts = whole["component_cells"]
+        assert isos[2] == 160 and int(np.argmax(counts)) == 2 and int(counts[2]) == 29224 * f and len(whole["cells"]) == 38514 * f
+
+
+def test_border_region_and_band(pkg, ex):
+    kw = dict(project=1, triangles=1)
+    labels = label_volume((9, 11, 37), 8)
+    ex.set_border(1, 0)
+    ex.extract_host(pkg.Volume(labels), params(pkg, 2, **kw))
+    whole = snapshot(ex)
+    assert len(whole["component_cells"]) >= 2
+    keep_held(ex, whole, "largest", what="border")
+    ex.set_border(0, 0)
+    vox, start, size = cases.two_pieces_in_a_box()
+    ex.set_region(start, size)
+    ex.extract_host(pkg.Volume(vox), params(pkg, 1, **kw))
+    whole = snapshot(ex)
+    assert len(whole["component_cells"]) == 2
+    after = keep_held(ex, whole, "mask", mask=[0, 1], what="region")
+    assert 0 < len(after["cells"]) < len(whole["cells"])
+    ex.clear_region()
+    ex.set_band(1, 255, 1, 0)
+    ex.set_cell_pixels(True)
+    ex.set_point_normals(True)
+    ex.extract_host(pkg.Volume(labels), params(pkg, 1, **kw))
+    whole = snapshot(ex, True, True)
+    counts = whole["component_cells"]
+    assert len(counts) >= 2
+    after = keep_held(ex, whole, "min_cells", int(np.sort(counts)[-2]) + 1, what="band")
+    assert 0 < len(after["cells"]) < len(whole["cells"])
+
+
+def test_count_emit_with_an_offset(pkg, ex):
+    vox = cases.gradient_noise((20, 22, 70), seed=9)
+    iso = cases.noise_isos(vox)[1]
+    dev = device_copy(vox)
+    desc = pkg.make_desc(vox.dtype, pkg.Volume(vox).dims)
+    prm = params(pkg, iso, project=1, triangles=1)
+    for offset in (0, 1000, 2 ** 32 + 5):
+        ex.count(dev.data_ptr(), desc, prm)
+        ex.emit(offset)
+        whole = snapshot(ex, offset=offset)
+        k = len(whole["component_cells"])
+        assert k >= 3 and int(whole["cells"].min()) >= offset
+        after = keep_held(ex, whole, "mask", mask=(np.arange(k) != int(np.argmax(whole["component_cells"]))), what=("offset", offset))
+        assert 0 < len(after["cells"]) < len(whole["cells"]) and int(after["cells"].min()) >= offset        # (the offset stays in the ids)
+        assert int(after["cells"].max()) < offset + len(after["points"])
+        keep_held(ex, after, "largest", what=("offset", offset, "second keep"))
+
+
+def test_the_next_extraction_and_memory(pkg):
+    """After a keep the context's next extraction -- sized by a host read, and launched blindly from the extraction's sizes -- gives
+    the bytes and counters a fresh context gives; with the setting off again the context holds what it held before it was on."""
+    vox = cases.gradient_noise((24, 30, 70), seed=3)
+    iso = cases.noise_isos(vox)[1]
+    dev = device_copy(vox)
+    desc = pkg.make_desc(vox.dtype, pkg.Volume(vox).dims)
+    prm = params(pkg, iso, project=1, triangles=1)
+    fresh, e = pkg.Extractor(0), pkg.Extractor(0)
+    try:
+        want = []
+        for _ in range(5):                                                      # (all but the first are launched blindly)
+            res = fresh.extract_device(dev.data_ptr(), desc, prm)
+            want.append((fresh.download(), counters(res)))
+        res = e.extract_device(dev.data_ptr(), desc, prm)
+        bytes_before = e.device_bytes()
+        slices = e.slice_counts(vox.shape[0])
+        e.set_components(True)
+        for i in range(3):
+            res = e.extract_device(dev.data_ptr(), desc, prm)
+            mesh = e.download()
+            assert mesh.points.tobytes() == want[i + 1][0].points.tobytes() and mesh.cells.tobytes() == want[i + 1][0].cells.tobytes(), i
+            assert counters(res) == want[i + 1][1], i
+            whole = snapshot(e)
+            assert len(whole["component_cells"]) >= 2
+            after = keep_held(e, whole, "largest" if i != 1 else "min_cells", int(whole["component_cells"].max()), what=("series", i))
+            assert len(after["cells"]) < len(whole["cells"])
+            # the walk counters and the times are history, and the count's tables still describe the extraction
+            assert {k: v for k, v in counters(e.result).items() if k not in ("n_points", "n_cells")} == \
+                   {k: v for k, v in want[i + 1][1].items() if k not in ("n_points", "n_cells")}
+            assert e.result.ms_total == res.ms_total and int(res.n_points) == len(whole["points"])
+            assert [a.tolist() for a in e.slice_counts(vox.shape[0])] == [a.tolist() for a in slices]
+        assert e.device_bytes() > bytes_before
+        kept = e.download()
+        e.set_components(False)
+        # (the kept mesh stays, in the buffers the context held before the setting was on)
+        assert e.device_bytes() == fresh.device_bytes()
+        back = e.download()
+        assert back.points.tobytes() == kept.points.tobytes() and back.cells.tobytes() == kept.cells.tobytes()
+        res = e.extract_device(dev.data_ptr(), desc, prm)
+        assert e.download().cells.tobytes() == want[4][0].cells.tobytes() and counters(res) == want[4][1]
+        # (the same five extractions on a context that never heard of either call)
+        assert e.device_bytes() == fresh.device_bytes() and e.device_bytes() >= bytes_before
+    finally:
+        fresh.close()
+        e.close()
+
+
+def test_refusals_and_the_allocation_drill(pkg, ex):
+    vox = cases.gradient_noise((20, 22, 70), seed=9)
+    iso = cases.noise_isos(vox)[1]
+    vol, dev = pkg.Volume(vox), device_copy(vox)
+    desc = pkg.make_desc(vox.dtype, vol.dims)
+    prm = params(pkg, iso, project=1, triangles=1)
+
+    def refused(code, fn, word="components"):
+        with pytest.raises(pkg._abi.CuberilleError) as e:
+            fn()
+        assert e.value.code == code and word in str(e.value), (e.value.code, str(e.value))
+
+    # no mesh; an unknown rule
+    refused(STATE, lambda: ex.keep_components("largest"))
+    refused(ARG, lambda: ex.keep_components(3), "rule")
+    refused(ARG, lambda: ex.keep_components("biggest"), "rule")
+    # the last extraction ran with components off
+    ex.set_components(False)
+    ex.extract_host(vol, prm)
+    refused(STATE, lambda: ex.keep_components("largest"))
+    plain = ex.download()
+    # a slab's mesh
+    slab = pkg._abi.Slab(global_nz=40, z_begin=0, own_z0=0, own_z1=16)       # (the buffer: the lower 20 slices of 40)
+    ex.extract_device(dev.data_ptr(), desc, params(pkg, iso, project=0, triangles=1), slab)
+    refused(STATE, lambda: ex.keep_components("largest"))
+    # between cuberille_step_begin and cuberille_step_end
+    ptr, _ = ex.step_begin(dev.data_ptr(), desc, prm)
+    refused(STATE, lambda: ex.keep_components("min_cells", 1))
+    ex.step_end(ptr, 1, 0)
+    assert ex.download().cells.tobytes() == plain.cells.tobytes()               # (the context went on)
+    # the mask's errors: the mesh stays as it was
+    ex.set_components(True)
+    ex.extract_host(vol, prm)
+    whole = snapshot(ex)
+    k = len(whole["component_cells"])
+    assert k >= 3
+    lib = pkg._abi.lib()
+    refused(ARG, lambda: ex.keep_components("mask", mask=np.ones(k - 1)), "mask")
+    refused(ARG, lambda: ex.keep_components("mask", mask=np.ones(k + 1)), "mask")
+    assert lib.cuberille_keep_components(ex._ctx, keep_ref.MASK, 0, None, k, None, None, None, None) == ARG
+    assert lib.cuberille_keep_components(ex._ctx, 17, 0, None, 0, None, None, None, None) == ARG
+    same(snapshot(ex), keep_ref.Kept(**{n: v for n, v in whole.items() if n != "offset"}), "after the refusals")
+    # the allocation drill: whichever row cannot be reserved, the call fails with ERR_HIP, the mesh is byte for byte what it was,
+    # and a later call succeeds
+    failed = 0
+    for at in range(32):
+        ex.debug_option("fail_alloc_at", at)
+        try:
+            got = ex.keep_components("min_cells", int(np.sort(whole["component_cells"])[-2]))
+        except pkg._abi.CuberilleError as e:
+            assert e.code == HIP, (at, e.code, str(e))
+            failed += 1
+            same(snapshot(ex), keep_ref.Kept(**{n: v for n, v in whole.items() if n != "offset"}), ("drill", at))
+            continue
+        break
+    ex.debug_option("fail_alloc_at", -1)
+    assert failed >= 3 and got[2] == 2, (failed, got)
+    want = keep_ref.apply("min_cells", *[whole[n] for n in ("points", "cells", "point_component", "cell_component", "component_cells")],
+                          n=int(np.sort(whole["component_cells"])[-2]))
+    same(snapshot(ex), want, "after the drill")
+    # (the limit of 2^32 cells needs a mesh no test can afford: it is one comparison ahead of the first launch, left to review)
+
+
+def test_python_filter_mirror(pkg, ex):
+    vox = cases.gradient_noise()
+    iso = cases.noise_isos(vox)[2]
+    vol = pkg.Volume(vox)
+    f = pkg.CuberilleImageToMeshFilter(device=0)
+    f.SetInput(vol)
+    f.SetIsoSurfaceValue(iso)
+    f.GeneratePointNormalsOn()
+    f.SavePixelAsCellDataOn()
+    f.Update()
+    n_all = len(f.GetOutput().cells)
+    assert f.GetPointComponents() is None
+    prm = pkg.make_params(iso, triangles=True, project=True, step=max(vol.spacing) * 0.25)
+    ex.set_point_normals(True)
+    ex.set_cell_pixels(True)
+
+    def held(what, *keeps):
+        ex.extract_host(vol, prm)
+        for rule, n in keeps:
+            ex.keep_components(rule, n)
+        want = snapshot(ex, True, True)
+        f.Update()
+        got = dict(points=f.GetOutput().points, cells=f.GetOutput().cells, point_component=f.GetPointComponents(),
+                   cell_component=f.GetCellComponents(), component_cells=f.GetComponentCellCounts(), normals=f.GetPointNormals(),
+                   cell_pixels=f.GetCellPixels())
+        same(got, keep_ref.Kept(**{k: v for k, v in want.items() if k != "offset"}), what)
+        assert f.GetNumberOfComponents() == len(want["component_cells"])
+        return len(got["cells"])
+
+    f.KeepLargestComponentOn()
+    assert 0 < held("KeepLargestComponentOn", ("largest", 0)) < n_all
+    f.SetMinimumComponentCells(2000)
+    held("both", ("largest", 0), ("min_cells", 2000))
+    f.KeepLargestComponentOff()
+    assert 0 < held("SetMinimumComponentCells", ("min_cells", 2000)) < n_all
+    f.SetMinimumComponentCells(10 ** 9)
+    assert held("above every component", ("min_cells", 10 ** 9)) == 0
+    f.SetMinimumComponentCells(0)
+    f.Update()
+    assert len(f.GetOutput().cells) == n_all and f.GetPointComponents() is None
+
+
+def test_drop_in_filter_keep_update():
+    """itk/tests/keep_update.cxx: two balls of different size -- KeepLargestComponentOn() and a minimum between the two sizes yield
+    exactly the mesh of the image with the small ball erased (points, cells, cell data), a minimum above both an empty mesh --
+    the program exits non-zero on a difference."""
+    exe = os.path.join(ROOT, "midas-journal-740_amd", "itk", "build", "keep_update")
+    if not os.path.exists(exe):
+        pytest.fail("itk/build/keep_update is missing: __graft_entry__.build() makes it")
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(run.stdout.strip(), run.stderr.strip())
+    assert run.returncode == 0 and "keep_update ok" in run.stdout and "DIFFERENT" not in run.stdout
+    assert run.stdout.count("the largest is component 1: yes") == 2
