@@ -2291,11 +2291,13 @@ int cuberille_set_point_normals(cuberille_ctx *c, int on) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
   c->pointNormals = on != 0;
-  if (!on && c->normals.p) {
-    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its normals go)
+  if (!on && (c->normals.p || c->spareNormals.p)) {
+    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its normals go -- and behind a
+    // cuberille_keep_components the row's partner, whichever of the two the extraction was sized for)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
     c->normals.release();
+    c->spareNormals.release();
     c->haveNormals = false;
     c->countNormals = false;
   }
@@ -2330,11 +2332,13 @@ int cuberille_set_cell_pixels(cuberille_ctx *c, int on) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
   c->cellPixels = on != 0;
-  if (!on && c->cellPix.p) {
-    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its cell pixels go)
+  if (!on && (c->cellPix.p || c->spareCellPix.p)) {
+    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its cell pixels go -- and
+    // behind a cuberille_keep_components the row's partner, whichever of the two the extraction was sized for)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
     c->cellPix.release();
+    c->spareCellPix.release();
     c->haveCellPixels = false;
     c->countCellPixels = false;
   }

@@ -34,6 +34,15 @@ flip as direction matrix, a start index), the filter's eight parameters, a proje
   components   cuberille_set_components on, the same routes and kinds (frames of up to COMPONENTS_MAX_VOXELS voxels: the
           reference's time);   reference: components_ref.components on the REFERENCE's cells -- three rows as bytes, K, and the
           definition's properties (test_components.check_properties)
+  keep    (with components) cuberille_keep_components behind the last extraction, one stage or two -- largest, a minimum of
+          cells picked among 0, max + 1 and the sorted counts' quantiles, a mask drawn from a stream of its own, kept bytes of
+          2 .. 255 among them; every argument resolved on the REFERENCE's counts (keep_arguments) --, and behind every repeat that
+          runs with components on.  After each stage everything the library says of its mesh is taken again: counts, points and
+          cells through the route's own accessor, normals, cell pixels, the three rows, K, the device pointers, the counters;
+                                         reference: keep_ref.keep on the reference mesh, components_ref's rows, normals_ref's
+          normals and cell_pixels_ref's pixels -- the kept mesh is held to the oracle's own mesh, never to rows the library
+          handed out.  The context stays as the keep left it: rows sized by the kept counts in place, the extraction's as spare
+          rows -- the next case toggles settings, changes the pixel width, or launches blindly on that (counted: behind_keep)
   emit_offset  count + emit: the id offset handed to cuberille_emit -- 0, below 10^6, or 2^32 and more --, taken off the cells
           before the comparison; labels and pixels never carry it
   repeat  the case three times on the context, the third mesh compared (the blind launch sized by its own history); the first
@@ -50,7 +59,8 @@ the float bits of every coordinate (conftest.assert_same_mesh), the bits of ever
 counters, the bytes of every cell pixel and label.  TEST INFRASTRUCTURE: the oracle is the checker here, never the thing
 measured or shipped.
 What was drawn before cell pixels and components existed comes from the stream it came from, draw for draw; the keys above that
-are new come from a second one (draw_case; tests/golden/campaign_recipe_digests.json): the cases of the committed logs replay.
+are new come from a second one, the keep from a third (draw_case; tests/golden/campaign_recipe_digests.json and
+campaign_celldata_recipe_digests.json): the cases of the committed logs replay.
 Prints one progress line every ~20 s; exit code 1 with the failing case's recipe if a mesh ever differs."""
 import argparse
 import copy
@@ -110,7 +120,8 @@ REFUSALS = {"whole": ["normals_rg", "bspline_variant", "bspline_held", "cell_pix
 REFUSALS_FIRST_STREAM = {"whole": 3}
 SLAB_REFUSALS = {"cell_pixels_slab": "cell_pixels", "components_slab": "components"}
 DEFAULT_OPTIONS = dict(max_voxels=900000, big=False, recursive_gaussian=False, kind=None, dtype=None, route=None, max_rows=None,
-                       cell_pixels=None, components=None)
+                       cell_pixels=None, components=None, keep=None)
+KEEP_RULES = ("largest", "min_cells", "mask")
 
 
 def draw_field(rng, shape, dt, big=True):
@@ -271,14 +282,15 @@ def has_q1_gap(img, iso):
 # ---- 1. the recipe ---------------------------------------------------------------------------------------------------------
 def draw_case(seed, case, options=None):
     """The recipe of case `case` of seed `seed`: a dict of plain numbers, lists and strings.  options: DEFAULT_OPTIONS' keys
-    -- max_voxels, big (up to 120 rows and slices), recursive_gaussian, and kind / dtype / route / cell_pixels / components to
-    fix what a stratified slice fixes (they are recorded, so the recipe alone still says everything; cell_pixels / components
-    True: every case that can takes it).  Needs no GPU and no oracle.
+    -- max_voxels, big (up to 120 rows and slices), recursive_gaussian, and kind / dtype / route / cell_pixels / components /
+    keep to fix what a stratified slice fixes (they are recorded, so the recipe alone still says everything; cell_pixels /
+    components / keep True: every case that can takes it; keep may name the rule).  Needs no GPU and no oracle.
 
     Two streams: np.random.default_rng([seed, case]) draws everything the campaign drew before cell pixels and components
     existed, in the order it drew it then -- no draw of it may move, tests/golden/campaign_recipe_digests.json pins them --, and
-    np.random.default_rng([seed, case, 3]) draws cell_pixels, components, drop_cell_rows, emit_offset and refusal_slab
-    ([seed, case, 1] is the field's stream, [seed, case, 2] that of a held case's first volume)."""
+    np.random.default_rng([seed, case, 3]) draws cell_pixels, components, drop_cell_rows, emit_offset and refusal_slab -- pinned in
+    turn by tests/golden/campaign_celldata_recipe_digests.json --, np.random.default_rng([seed, case, 4]) draws keep
+    ([seed, case, 1] is the field's stream, [seed, case, 2] that of a held case's first volume, [seed, case, 5] a keep's mask)."""
     opt = dict(DEFAULT_OPTIONS)
     opt.update(options or {})
     rng = np.random.default_rng([int(seed), int(case)])
@@ -370,6 +382,7 @@ def draw_case(seed, case, options=None):
     # behind a normals case the setting stays on -- its row, sized by this mesh, is there for the next case -- or is switched off
     recipe["drop_normals_row"] = bool(rng.random() < 0.25)
     _draw_cell_data(np.random.default_rng([int(seed), int(case), 3]), recipe, opt, img.size)
+    _draw_keep(np.random.default_rng([int(seed), int(case), 4]), recipe, opt)
     return recipe
 
 
@@ -389,6 +402,72 @@ def _draw_cell_data(rng, recipe, opt, frame_voxels):
     name = ["cell_pixels_slab", "components_slab"][int(rng.integers(0, 2))]
     if rng.random() < 0.08 and recipe["kind"] == "whole" and recipe["route"] not in ("slabs", "thin_slabs", "held"):
         recipe["refusal_slab"] = name
+
+
+def _draw_keep(rng, recipe, opt):
+    """The third stream: recipe["keep"], a cuberille_keep_components behind the case's last extraction (and behind every repeat
+    that runs with components on) -- None unless components are on.  The draw cannot know K, so it holds a rule and the means to
+    resolve its argument later (keep_arguments):
+
+      {"rule": "largest"}
+      {"rule": "min_cells", "pick": "zero" (keeps all) | "above_max" (max + 1: drops all) | "quantile", "quantile": q,
+       "plus_one": bool}                    quantile: counts[j] or counts[j] + 1 at j = floor(q K) of the sorted counts
+      {"rule": "mask", "stream": [seed, case, 5], "form": "random" | "all_but_largest", "p": the probability of a kept byte,
+       "odd_bytes": bool}                   odd_bytes: some kept bytes hold a value of 2 .. 255 (the ABI says non-zero)
+      "then": None, or a second stage ("largest" or "min_cells") resolved on the first keep's result
+
+    opt["keep"]: None (about half of the components cases), True / False (every case that can / none), or a rule's name (every
+    case that can, with that rule).  Every draw is made whatever the options and the rule are."""
+    wanted = bool(rng.random() < 0.5)
+    rule = KEEP_RULES[int(rng.integers(0, 3))]
+
+    def min_cells():
+        u, q, plus = rng.random(), float(rng.random()), bool(rng.integers(0, 2))
+        pick = "zero" if u < 0.1 else ("above_max" if u < 0.2 else "quantile")
+        return dict(rule="min_cells", pick=pick, quantile=round(q, 6), plus_one=plus)
+    stages = {"largest": dict(rule="largest"), "min_cells": min_cells(),
+              "mask": dict(rule="mask", stream=[recipe["seed"], recipe["case"], 5],
+                           form="all_but_largest" if rng.random() < 0.2 else "random",
+                           p=float(rng.choice([0.0, 0.1, 0.5, 0.5, 0.9, 1.0])), odd_bytes=bool(rng.random() < 0.4))}
+    second = [None, dict(rule="largest"), min_cells()][int(rng.choice([0, 0, 0, 0, 1, 2, 2]))]
+    if isinstance(opt["keep"], str):
+        assert opt["keep"] in KEEP_RULES, opt["keep"]
+        wanted, rule = True, opt["keep"]
+    elif opt["keep"] is not None:
+        wanted = bool(opt["keep"])
+    recipe["keep"] = dict(stages[rule], then=second) if wanted and recipe["components"] else None
+
+
+def keep_stages(keep):
+    """The stages of a recipe's keep in the order they run: one, or two with `then`."""
+    if not keep:
+        return []
+    first = {k: v for k, v in keep.items() if k != "then"}
+    return [first] + ([keep["then"]] if keep.get("then") else [])
+
+
+def keep_arguments(stage, component_cells):
+    """(rule, n, mask) of cuberille_keep_components for one stage on a mesh with these component counts -- the REFERENCE's, never
+    the library's.  Pure: the mask's bytes come from the stage's own stream."""
+    counts = np.asarray(component_cells, dtype=np.uint64)
+    k = len(counts)
+    rule = stage["rule"]
+    if rule == "largest":
+        return "largest", 0, None
+    if rule == "min_cells":
+        if stage["pick"] == "zero":
+            return "min_cells", 0, None
+        if stage["pick"] == "above_max":
+            return "min_cells", (int(counts.max()) if k else 0) + 1, None
+        at = int(np.sort(counts)[min(int(stage["quantile"] * k), k - 1)]) if k else 0
+        return "min_cells", at + int(bool(stage["plus_one"])), None
+    assert rule == "mask", rule
+    rng = np.random.default_rng(stage["stream"])
+    kept, odd, values = rng.random(k) < stage["p"], rng.random(k) < 0.3, rng.integers(2, 256, size=k)
+    if stage["form"] == "all_but_largest":
+        kept = np.arange(k) != (int(np.argmax(counts)) if k else -1)
+    mask = np.where(kept, np.where(odd & bool(stage["odd_bytes"]), values, 1), 0).astype(np.uint8)
+    return "mask", 0, mask
 
 
 def _draw_border_value(rng, dt, iso):
@@ -480,7 +559,8 @@ def _oracle_kw(recipe):
 def expected(oracle, recipe, vox=None):
     """{"mesh": the reference mesh (with .info, the walk's counters, where the reference has them), "normals": the reference
     normals or None, "cell_pixels": cell_pixels_ref's row or None, "components": components_ref's three rows ON THE REFERENCE'S
-    CELLS or None}.  Never the library."""
+    CELLS or None, "kept": one keep_ref.Kept per stage of the recipe's keep, "keep_args": the (rule, n, mask) of each stage
+    (kept_expected)}.  Never the library."""
     vox = voxels(recipe) if vox is None else vox
     img, start = frame(recipe, vox)
     okw = _oracle_kw(recipe)
@@ -503,7 +583,25 @@ def expected(oracle, recipe, vox=None):
     if recipe.get("components"):
         import components_ref
         components = components_ref.components(mesh.cells, len(mesh.points))
-    return {"mesh": mesh, "normals": normals, "cell_pixels": pixels, "components": components}
+    kept, keep_args = kept_expected(recipe, mesh, normals, pixels, components)
+    return {"mesh": mesh, "normals": normals, "cell_pixels": pixels, "components": components, "kept": kept, "keep_args": keep_args}
+
+
+def kept_expected(recipe, mesh, normals, pixels, components):
+    """(one keep_ref.Kept per stage of recipe["keep"], the (rule, n, mask) each stage resolves to): keep_ref.keep on the
+    reference mesh, components_ref's rows, normals_ref's normals and cell_pixels_ref's pixels -- a stage behind another on the
+    first one's result.  Offset 0: the reference's cells carry none."""
+    import keep_ref
+    kept, args = [], []
+    if recipe.get("keep"):
+        now = keep_ref.Kept(mesh.points, np.asarray(mesh.cells, dtype=np.uint64), components[0], components[1], components[2], normals, pixels)
+        for stage in keep_stages(recipe["keep"]):
+            rule, n, mask = keep_arguments(stage, now.component_cells)
+            now = keep_ref.keep(keep_ref.decide(rule, now.component_cells, n, mask), now.points, now.cells, now.point_component,
+                                now.cell_component, now.component_cells, offset=0, normals=now.normals, cell_pixels=now.cell_pixels)
+            kept.append(now)
+            args.append((rule, n, mask))
+    return kept, args
 
 
 def cell_pixels_view(recipe, vox):
@@ -677,8 +775,53 @@ def _clear_settings(pkg, ex):
     ex.debug_option("defaults", 0)
 
 
-def run_case(pkg, contexts, recipe, vox=None, stats=None):
-    """{"mesh", "normals" (or None), "counters" (or None), "cell_pixels" (or None), "components" (three rows, or None),
+def _keep(pkg, ex, rule, n, mask):
+    """ex.keep_components -- but a mask that holds bytes other than 0 and 1 goes to the C ABI as it is (the Python wrapper hands
+    the library `mask != 0`: through it the library would never see such a byte), and ex.result is renewed the way the wrapper
+    renews it."""
+    if mask is None or not (np.asarray(mask) > 1).any():
+        return ex.keep_components(rule, n, mask)
+    import ctypes as C
+    A = pkg._abi
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    npnt, ncell, k, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+    A.check(ex._ctx, A.lib().cuberille_keep_components(ex._ctx, A.KEEP_MASK, 0, C.c_void_p(m.ctypes.data), int(m.size), C.byref(npnt),
+                                                       C.byref(ncell), C.byref(k), C.byref(ms)))
+    res = type(ex.result).from_buffer_copy(ex.result)
+    res.n_points, res.n_cells = npnt.value, ncell.value
+    ex.result = res
+    return int(npnt.value), int(ncell.value), int(k.value), float(ms.value)
+
+
+def _keep_stage(pkg, ex, recipe, args):
+    """One cuberille_keep_components on the context and everything the library then says of its mesh."""
+    before = {k: int(getattr(ex.result, k)) for k in COUNTERS}
+    k_before = ex.n_components()
+    returned = _keep(pkg, ex, *args)
+    if recipe["route"] == "device":
+        host = ex.mesh_host()                              # (taken before the keep too: it must be fetched again)
+        mesh = pkg.Mesh(host.points.copy(), host.cells.copy())
+    else:
+        mesh = ex.download()
+    return {"returned": tuple(returned[:3]), "ms": returned[3], "result": (int(ex.result.n_points), int(ex.result.n_cells)), "mesh": mesh,
+            "normals": ex.download_normals() if recipe.get("normals") else None,
+            "cell_pixels": ex.download_cell_pixels() if recipe.get("cell_pixels") else None,
+            "components": ex.download_components(), "n_components": ex.n_components(),
+            "null": tuple(p is None or p == 0 for p in ex.components_device()),
+            "counters_before": before, "counters": {k: int(getattr(ex.result, k)) for k in COUNTERS}, "k_before": k_before}
+
+
+def moved_by_keep(stages):
+    """Whether a stage of a case's keeps kept some but not all -- 0 < K' < K: the mesh's rows then changed places with spare rows
+    sized by the kept counts, and the context is left that way.  stages: (K before, K') per stage."""
+    return any(0 < int(k2) < int(k) for k, k2 in stages)
+
+
+def run_case(pkg, contexts, recipe, vox=None, stats=None, keeps=()):
+    """keeps: the (rule, n, mask) of every stage of recipe["keep"], resolved on the REFERENCE's counts (expected()["keep_args"]);
+    "kept": what _keep_stage recorded behind each; "keep_before": whether the case before on the context left it behind a keep
+    that moved the rows (moved_by_keep).
+    {"mesh", "normals" (or None), "counters" (or None), "cell_pixels" (or None), "components" (three rows, or None),
     "n_components", "first_mesh" / "first_counters" (a case that repeats: its first repeat, run with cell pixels and components
     off), "emit_offset", "row_before", "pixels_row_before", "components_row_before"} of the library for the recipe, on the
     contexts as the cases before left them (the settings a case makes are taken back behind it; the workspace, its sizes, its
@@ -700,6 +843,8 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
     row_before = contexts.get("normals_row") if not held else None
     pixels_row_before = contexts.get("pixels_row") if not held else None
     components_row_before = contexts.get("components_row") if not held else None
+    keep_before = bool(contexts.get("behind_keep")) if not held else False
+    kept = []
     if recipe.get("refusal"):
         _refused(pkg, ex, recipe, vox, desc, row_before is not None)
     if recipe.get("refusal_slab"):
@@ -792,16 +937,23 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
                 counters = {k: int(getattr(res, k)) for k in COUNTERS}
             if recipe.get("normals"):
                 normals = ex.download_normals()
+            if keeps and want_components and not first_off and rep + 1 < repeat:
+                # every repeat that runs with components on keeps too: the next extraction is launched behind a keep
+                for args in keeps:
+                    _keep(pkg, ex, *args)
         # (after the last repeat)
         if want_pixels:
             pixels = ex.download_cell_pixels()
         if want_components:
             components = ex.download_components()
             n_components = ex.n_components()
+        for args in keeps:
+            kept.append(_keep_stage(pkg, ex, recipe, args))
     finally:
         _clear_settings(pkg, ex)
         if not held:
             contexts["normals_row"] = contexts["pixels_row"] = contexts["components_row"] = None
+            contexts["behind_keep"] = False
     n_points, n_cells = int(mesh.points.shape[0]), int(mesh.cells.shape[0])
     rows = {"normals_row": row_after(recipe, n_points), "pixels_row": pixels_row_after(recipe, n_cells),
             "components_row": components_row_after(recipe, n_points, n_cells)}
@@ -810,7 +962,8 @@ def run_case(pkg, contexts, recipe, vox=None, stats=None):
             setter(False)
     if not held:
         contexts.update(rows)
-    return {"mesh": mesh, "normals": normals, "counters": counters, "cell_pixels": pixels, "components": components,
+        contexts["behind_keep"] = moved_by_keep([(g["k_before"], g["returned"][2]) for g in kept])
+    return {"kept": kept, "keep_before": keep_before, "mesh": mesh, "normals": normals, "counters": counters, "cell_pixels": pixels, "components": components,
             "n_components": n_components, "first_mesh": first_mesh, "first_counters": first_counters, "emit_offset": offset, "row_before": row_before,
             "pixels_row_before": pixels_row_before, "components_row_before": components_row_before}
 
@@ -848,6 +1001,56 @@ def meets_components_row_of_another_size(row_before, recipe, n_points, n_cells):
 def meets_row_of_another_size(row_before, recipe, n_points):
     """A normals case on a context that still holds the row of a mesh of another size."""
     return bool(recipe.get("normals")) and row_before is not None and row_before != n_points
+
+
+def behind_keep(keep_before, rows_before, recipe):
+    """The settings -- among "normals", "cell_pixels", "components" -- that the case has on, whose row the case before left on
+    the context, that case having run a keep with 0 < K' < K: the row the case finds is one sized by the kept counts, its
+    extraction-sized partner a spare row.  rows_before: (normals row, pixels row, components row) as the *_row_after functions
+    gave them.  (A case that repeats switches cell pixels and components off in its first repeat: it meets the normals row only.)"""
+    if not keep_before:
+        return ()
+    once = recipe.get("repeat", 1) == 1
+    on = (bool(recipe.get("normals")), bool(recipe.get("cell_pixels")) and once, bool(recipe.get("components")) and once)
+    return tuple(name for name, mine, row in zip(("normals", "cell_pixels", "components"), on, rows_before) if mine and row is not None)
+
+
+def compare_kept(got, want, offset=0):
+    """The stages of a case's keep, each exact: points and cells (the id offset taken off: every id is >= offset and below offset
+    + kept points), normals, cell pixels and the three rows as bytes, the returned counts, ex.result's counts and K the
+    reference's, the device pointers null exactly where a count is 0, the walk's counters those before the keep, the
+    definition's properties on the kept rows."""
+    import normals_ref
+    import test_components as cases
+    stages, kept = got.get("kept") or [], want.get("kept") or []
+    assert len(stages) == len(kept), "%d keep stages ran, the recipe holds %d" % (len(stages), len(kept))
+    for i, (g, w) in enumerate(zip(stages, kept)):
+        what = "keep stage %d" % i
+        n_points, n_cells, k = len(w.points), len(w.cells), len(w.component_cells)
+        mesh = copy.copy(g["mesh"])
+        if len(mesh.cells):
+            assert int(mesh.cells.min()) >= offset and int(mesh.cells.max()) < offset + n_points, \
+                (what, "a kept cell id outside [offset, offset + kept points)", int(mesh.cells.min()), int(mesh.cells.max()), offset, n_points)
+        mesh.cells = mesh.cells - np.uint64(offset)
+        try:
+            assert_same_mesh(mesh, w)
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (what, e)) from e
+        assert tuple(g["returned"]) == (n_points, n_cells, k), (what, "returned counts", g["returned"], (n_points, n_cells, k))
+        assert tuple(g["result"]) == (n_points, n_cells), (what, "result counts", g["result"], (n_points, n_cells))
+        assert g["n_components"] == k, (what, "K", g["n_components"], k)
+        if w.normals is not None:
+            assert g["normals"] is not None, (what, "no normals came back")
+            normals_ref.same_normals(g["normals"], w.normals, what + ": normals")
+        if w.cell_pixels is not None:
+            p = g["cell_pixels"]
+            assert p is not None, (what, "no cell pixels came back")
+            assert p.dtype == w.cell_pixels.dtype and p.shape == w.cell_pixels.shape and p.tobytes() == w.cell_pixels.tobytes(), (what, "cell pixels")
+        rows = (w.point_component, w.cell_component, w.component_cells)
+        cases.same(g["components"], rows, what + ": components")
+        assert tuple(g["null"]) == (n_points == 0, n_cells == 0, k == 0), (what, "null device pointers", g["null"], (n_points, n_cells, k))
+        assert g["counters"] == g["counters_before"], (what, "counters changed by the keep", g["counters_before"], g["counters"])
+        cases.check_properties(w.cells, n_points, g["components"], what + ": components")
 
 
 def compare(got, want):
@@ -890,6 +1093,7 @@ def compare(got, want):
         cases.same(g, w, "components")
         assert got.get("n_components") == len(w[2]), ("K", got.get("n_components"), len(w[2]))
         cases.check_properties(want["mesh"].cells, len(want["mesh"].points), g, "components")
+    compare_kept(got, want, offset)
 
 
 def tally(stats, recipe, got, want):
@@ -921,6 +1125,16 @@ def tally(stats, recipe, got, want):
     stats["cell_pixels_on_a_row_of_another_size"] += int(meets_pixels_row_of_another_size(got.get("pixels_row_before"), recipe, n_cells))
     stats["components_on_rows_of_another_size"] += int(meets_components_row_of_another_size(got.get("components_row_before"), recipe, n_points, n_cells))
     stats["nonzero_id_offsets"] += int(bool(recipe.get("emit_offset")))
+    if recipe.get("keep"):
+        ks = [len(want["components"][2])] + [len(w.component_cells) for w in want["kept"]]
+        stats["keeps"][recipe["keep"]["rule"]] = stats["keeps"].get(recipe["keep"]["rule"], 0) + 1
+        stats["keeps_that_dropped"] += int(any(b < a for a, b in zip(ks, ks[1:])))
+        stats["keeps_some_of_several"] += int(moved_by_keep(list(zip(ks, ks[1:]))))
+        stats["keeps_to_nothing"] += int(ks[0] > 0 and ks[-1] == 0)
+        stats["chained_keeps"] += int(len(ks) > 2)
+        stats["keeps_on_mask_bytes_other_than_0_and_1"] += int(any(m is not None and (m > 1).any() for _, _, m in want["keep_args"]))
+    stats["behind_keep"] += int(bool(behind_keep(got.get("keep_before"), (got.get("row_before"), got.get("pixels_row_before"),
+                                                                          got.get("components_row_before")), recipe)))
 
 
 def new_stats():
@@ -928,14 +1142,15 @@ def new_stats():
             "after_refusal": 0, "refusals": {}, "with_switch": 0, "refused_slab_alias": 0, "nan_points": 0,
             "with_cell_pixels": 0, "with_components": 0, "with_normals_cell_pixels_and_components": 0, "components_found": 0,
             "with_two_components_or_more": 0, "cell_pixels_on_a_row_of_another_size": 0, "components_on_rows_of_another_size": 0,
-            "nonzero_id_offsets": 0}
+            "nonzero_id_offsets": 0, "keeps": {}, "keeps_that_dropped": 0, "keeps_some_of_several": 0, "keeps_to_nothing": 0,
+            "chained_keeps": 0, "keeps_on_mask_bytes_other_than_0_and_1": 0, "behind_keep": 0}
 
 
 def one_case(pkg, oracle, contexts, recipe, stats=None):
     """Run and compare one recipe; returns (got, want).  Raises at the first difference."""
     vox = voxels(recipe)
     want = expected(oracle, recipe, vox)
-    got = run_case(pkg, contexts, recipe, vox, stats)
+    got = run_case(pkg, contexts, recipe, vox, stats, want["keep_args"])
     compare(got, want)
     return got, want
 
@@ -952,18 +1167,28 @@ def slice_recipes(kind, seed=None, n=None):
     (i + i // 10) % 2 == 0 -- the pixel type is DTYPES[i % 10], so the parity alternates from one decade to the next and all ten
     types take it --, components on where i % 3 != 2 -- the empty meshes of the region and band slices (cases 10; 1 and 16) are
     among them -- and both on every route that offers them.  Everything else of the second stream (the rows kept or dropped,
-    the id offset, a refused slab) is drawn."""
+    the id offset, a refused slab) is drawn.  Every components case keeps (recipe["keep"]), by the rule
+    KEEP_RULES[(i // 2) % 3]; the pick, the mask and a second stage are drawn from the third stream."""
     seed = SLICE[kind][0] if seed is None else seed
     n = SLICE[kind][1] if n is None else n
     return [draw_case(seed, i, dict(SLICE_OPTIONS, kind=kind, dtype=np.dtype(DTYPES[i % len(DTYPES)]).name,
                                     route=ROUTES[kind][i % len(ROUTES[kind])], cell_pixels=(i + i // 10) % 2 == 0,
-                                    components=i % 3 != 2)) for i in range(n)]
+                                    components=i % 3 != 2, keep=KEEP_RULES[(i // 2) % 3])) for i in range(n)]
 
 
-def slice_facts(recipe, want, row_before=None, pixels_row_before=None, components_row_before=None):
+def slice_facts(recipe, want, row_before=None, pixels_row_before=None, components_row_before=None, keep_before=False):
     """What one executed case of the slice contributes to the conditions, from the recipe and the reference alone.  row_before,
     pixels_row_before, components_row_before: what row_after(), pixels_row_after(), components_row_after() gave for the case
-    before it on the context (slice_sequence_facts follows them through a kind's cases)."""
+    before it on the context, keep_before: whether that case ran a keep that kept some of several (slice_sequence_facts follows
+    them through a kind's cases).  keep: None, or the keep's facts -- its rule, `ks` (K before and behind every stage), whether
+    the kept part of any stage holds a NaN coordinate or normal, whether a mask holds a byte other than 0 and 1."""
+    keep = None
+    if recipe.get("keep"):
+        ks = [len(want["components"][2])] + [len(w.component_cells) for w in want["kept"]]
+        keep = dict(rule=recipe["keep"]["rule"], ks=ks, chained=len(ks) > 2, some=moved_by_keep(list(zip(ks, ks[1:]))),
+                    first_some=0 < ks[1] < ks[0],
+                    nan=any(bool(np.isnan(w.points).any()) or (w.normals is not None and bool(np.isnan(w.normals).any())) for w in want["kept"]),
+                    odd_mask=any(m is not None and bool((m > 1).any()) for _, _, m in want["keep_args"]))
     img, _ = frame(recipe)
     pts, nrm = want["mesh"].points, want["normals"]
     n_cells = len(want["mesh"].cells)
@@ -984,18 +1209,21 @@ def slice_facts(recipe, want, row_before=None, pixels_row_before=None, component
                 q1=bool(has_q1_gap(img, recipe["iso"])), empty=len(pts) == 0, nan_points=bool(np.isnan(pts).any()),
                 normals=nrm is not None and len(nrm) > 0, nan_normals=nrm is not None and bool(np.isnan(nrm).any()),
                 repeat=recipe.get("repeat", 1) > 1, refusal=recipe.get("refusal"),
-                refused=bool(recipe.get("refusal") or recipe.get("refusal_slab")))
+                refused=bool(recipe.get("refusal") or recipe.get("refusal_slab")), keep=keep,
+                behind_keep=behind_keep(keep_before, (row_before, pixels_row_before, components_row_before), recipe))
 
 
 def slice_sequence_facts(recipes, wants):
     """slice_facts of a kind's cases in the order they run on their one context."""
-    facts, rows = [], (None, None, None)
+    facts, rows = [], (None, None, None, False)
     for recipe, want in zip(recipes, wants):
         held = recipe["route"] == "held"                      # (a context of its own, never with normals, its rows always dropped)
-        facts.append(slice_facts(recipe, want, *((None, None, None) if held else rows)))
+        facts.append(slice_facts(recipe, want, *((None, None, None, False) if held else rows)))
         if not held:
             n_points, n_cells = len(want["mesh"].points), len(want["mesh"].cells)
-            rows = (row_after(recipe, n_points), pixels_row_after(recipe, n_cells), components_row_after(recipe, n_points, n_cells))
+            keep = facts[-1]["keep"]
+            rows = (row_after(recipe, n_points), pixels_row_after(recipe, n_cells), components_row_after(recipe, n_points, n_cells),
+                    bool(keep and keep["some"]))
     return facts
 
 
@@ -1027,6 +1255,10 @@ def slice_conditions(kind, facts):
         need(any(f["components"] and f["K"] == 1 for f in facts), "a components case with K = 1")
         need(any(f["components"] and f["K"] >= 2 for f in facts), "a components case with K >= 2")
     need(any(f["cell_pixels"] and f["components"] for f in facts), "a case with cell pixels and components")
+    keeps = [f for f in facts if f["keep"]]
+    need(len(keeps) >= 5, "at least 5 keep cases")
+    need({f["triangles"] for f in keeps} == {True, False}, "quads and triangles among the keep cases")
+    need(sum(f["keep"]["first_some"] for f in keeps) >= 4, "at least 4 keep cases with 0 < K' < K")
     return missing
 
 
@@ -1061,6 +1293,29 @@ def slice_conditions_overall(facts):
     need(any(f["route"] == "count_emit" and f["offset"] >= 2 ** 32 for f in comp), "a count + emit components case with an id offset of at least 2^32")
     need(any(f["other_pixels_row"] for f in facts), "a cell-pixel case on a context whose previous case left a row of another size")
     need(any(f["other_components_row"] for f in facts), "a components case on a context whose previous case left rows of another size")
+    keeps = [f for f in facts if f["keep"]]
+    first, last = (lambda f: f["keep"]["ks"][0]), (lambda f: f["keep"]["ks"][-1])
+    dropped = lambda f: any(b < a for a, b in zip(f["keep"]["ks"], f["keep"]["ks"][1:]))        # noqa: E731
+    for rule in KEEP_RULES:
+        need(sum(f["keep"]["rule"] == rule and f["keep"]["first_some"] for f in keeps) >= 3, "the keep rule %s at least 3 times with 0 < K' < K" % rule)
+    need(any(first(f) >= 1 and last(f) == 0 for f in keeps), "a keep with K' = 0 from K >= 1")
+    need(any(first(f) >= 2 and f["keep"]["ks"][1] == first(f) for f in keeps), "a keep with K' = K >= 2 (nothing moves)")
+    need(any(first(f) == 0 and f["empty"] for f in keeps), "a keep on an empty mesh (K = 0)")
+    need(any(f["normals"] and not f["cell_pixels"] for f in keeps), "a keep with normals")
+    need(any(f["cell_pixels"] and not f["normals"] for f in keeps), "a keep with cell pixels")
+    need(any(f["normals"] and f["cell_pixels"] for f in keeps), "a keep with normals and cell pixels")
+    need(any(f["keep"]["nan"] for f in keeps), "a keep with NaN coordinates or a NaN normal in the kept part")
+    need(any(first(f) > 64 for f in keeps), "a keep at K > 64")
+    need(any(f["route"] == "count_emit" and f["offset"] >= 2 ** 32 and dropped(f) for f in keeps),
+         "a count + emit keep with an id offset of at least 2^32 that drops something")
+    need(any(f["repeat"] for f in keeps), "a keep in a repeating case")
+    need(any(f["route"] == "held" for f in keeps), "a keep on the held route")
+    need(any(f["switch"] for f in keeps), "a keep under a development switch")
+    need(any(f["refused"] for f in keeps), "a keep behind a refused call")
+    need(any(f["keep"]["chained"] for f in keeps), "a chained keep")
+    need(any(f["keep"]["odd_mask"] for f in keeps), "a keep whose mask holds a byte other than 0 and 1")
+    for name, text in (("normals", "normals"), ("cell_pixels", "cell pixels"), ("components", "components")):
+        need(any(name in f["behind_keep"] for f in facts), "a case with %s behind a keep (behind_keep)" % text)
     return missing
 
 
@@ -1072,6 +1327,7 @@ def main():
     ap.add_argument("--recursive-gaussian", action="store_true", help="every case that can takes the recursive-Gaussian gradient (h:21)")
     ap.add_argument("--cell-pixels", action="store_true", help="every case that can takes cuberille_set_cell_pixels")
     ap.add_argument("--components", action="store_true", help="every case that can takes cuberille_set_components")
+    ap.add_argument("--keep", action="store_true", help="every case with components takes a cuberille_keep_components behind it")
     ap.add_argument("--big", action="store_true", help="up to 120 rows and slices (fewer, larger cases: set --max-voxels too)")
     ap.add_argument("--kind", choices=KINDS, default=None, help="draw this kind only")
     ap.add_argument("--dtype", default=None, help="draw this pixel type only (a numpy name)")
@@ -1082,7 +1338,7 @@ def main():
     args = ap.parse_args()
     options = dict(max_voxels=args.max_voxels, big=args.big, recursive_gaussian=args.recursive_gaussian, kind=args.kind,
                    dtype=args.dtype, route=args.route, max_rows=args.max_rows, cell_pixels=args.cell_pixels or None,
-                   components=args.components or None)
+                   components=args.components or None, keep=args.keep or None)
     pkg = graft.load_package()
     oracle = graft.load_oracle()
     oracle.build()
@@ -1119,11 +1375,13 @@ def main():
                 last = time.time()
                 print("t %.0f s: %d cases, %d points, %d cells, %d with cell pixels (%d on a row of another size), %d with components "
                       "(%d on rows of another size, %d components, %d cases with two or more), %d with normals and both, %d id offsets, "
+                      "keeps %s (%d dropped, %d to nothing, %d chained, %d cases behind one), "
                       "all identical" % (last - t0, stats["cases"], stats["points"], stats["cells"], stats["with_cell_pixels"],
                                          stats["cell_pixels_on_a_row_of_another_size"], stats["with_components"],
                                          stats["components_on_rows_of_another_size"], stats["components_found"],
                                          stats["with_two_components_or_more"], stats["with_normals_cell_pixels_and_components"],
-                                         stats["nonzero_id_offsets"]), flush=True)
+                                         stats["nonzero_id_offsets"], json.dumps(stats["keeps"], sort_keys=True), stats["keeps_that_dropped"],
+                                         stats["keeps_to_nothing"], stats["chained_keeps"], stats["behind_keep"]), flush=True)
     finally:
         close_contexts(contexts)
     stats["seconds"] = round(time.time() - t0, 1)

@@ -11,6 +11,9 @@ components and the emit offset entered the recipe -- to be run on a checkout of 
 The seeds of the slice were chosen for what they produce, and the cases logged in profiles/fuzz_views_seed*.log and
 profiles/r5_fuzz_campaign_*.log replay from --seed S --case N: tests/test_campaign_scripts.py recomputes every digest from the
 draw_case of the day, restricted to `keys`, and requires equality -- a new key is drawn from a stream of its own.
+--out names the fixture: campaign_celldata_recipe_digests.json is the same record taken on the commit before the keep entered the
+recipe (070778d) -- it holds the keys of the second stream too (cell_pixels, components, drop_cell_rows, emit_offset,
+refusal_slab), which the keep's third stream must not move.
 Needs no GPU and no oracle."""
 import argparse
 import hashlib
@@ -42,6 +45,7 @@ def collect(fz, keys=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tests", default=os.path.dirname(HERE), help="the tests/ directory of the checkout whose draw_case is recorded")
+    ap.add_argument("--out", default="campaign_recipe_digests.json", help="the fixture's file name in tests/golden/")
     args = ap.parse_args()
     tests = os.path.abspath(args.tests)
     sys.path.insert(0, os.path.dirname(tests))
@@ -50,7 +54,7 @@ def main():
     assert os.path.dirname(os.path.abspath(fz.__file__)) == tests, fz.__file__
     seeds, slices, recipes = collect(fz)
     keys = sorted({k for r in recipes for k in r})
-    with open(os.path.join(HERE, "campaign_recipe_digests.json"), "w") as f:
+    with open(os.path.join(HERE, os.path.basename(args.out)), "w") as f:
         json.dump(dict(keys=keys, cases=CASES, seeds=seeds, slices=slices), f, indent=1)
         f.write("\n")
     print(len(keys), "keys,", len(recipes), "recipes")

@@ -4,7 +4,10 @@ between the rounds in which somebody runs them on a GPU box.  The campaign's new
 and band passes its validator, every drawn recipe survives JSON, rebuilds the same bytes and runs through expected(); and the
 seeded slice of tests/test_gpu_campaign.py holds the conditions that keep it from hiding a failure, shown on the oracle alone.
 Cell pixels, components, their rows and the id offset come from a stream of their own: what the campaign drew before them is
-held, draw for draw, to a fixture recorded on the commit before (tests/golden/campaign_recipe_digests.json)."""
+held, draw for draw, to a fixture recorded on the commit before (tests/golden/campaign_recipe_digests.json); the keep comes from a
+third stream, and a second fixture (campaign_celldata_recipe_digests.json) holds the second stream the same way.  The keep's
+reference is keep_ref.keep on the oracle's mesh and the references' rows: its closure, its purity and compare()'s eye for one bit
+of a kept row are shown here on the oracle alone."""
 import glob
 import json
 import os
@@ -116,7 +119,9 @@ def test_the_first_stream_draws_what_it_drew():
     entered the recipe (tests/golden/make_campaign_recipe_digests.py): restricted to the keys a recipe had then, every recipe of
     seeds 1 and 11 (cases 0 .. 299, default options) and of the five slice lists is byte for byte the recipe of that commit --
     the slice's seeds keep what they were chosen for, the cases of the committed logs replay -- and what is new is drawn from a
-    stream of its own."""
+    stream of its own.  tests/golden/campaign_celldata_recipe_digests.json, recorded the same way on the commit before `keep`
+    entered the recipe, holds the second stream -- cell pixels, components, their rows, the id offset, the refused slab -- to what
+    it drew then: the only key beyond that fixture's is `keep`, from a third stream."""
     import sys
     import fuzz_campaign as fz
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -124,23 +129,28 @@ def test_the_first_stream_draws_what_it_drew():
         import make_campaign_recipe_digests as mk
     finally:
         sys.path.pop(0)
-    with open(os.path.join(ROOT, "tests", "golden", "campaign_recipe_digests.json")) as f:
-        fixture = json.load(f)
-    assert fixture["cases"] == mk.CASES == 300 and sorted(fixture["seeds"]) == ["1", "11"] and sorted(fixture["slices"]) == sorted(fz.KINDS)
-    assert "cell_pixels" not in fixture["keys"] and {"kind", "dtype", "route", "kw", "field", "refusal", "drop_normals_row"} <= set(fixture["keys"])
-    seeds, slices, recipes = mk.collect(fz, set(fixture["keys"]))
-    for name, got, want in [("seed " + s, seeds[s], fixture["seeds"][s]) for s in sorted(seeds)] + [(k, slices[k], fixture["slices"][k]) for k in fz.KINDS]:
-        assert len(got) == len(want)
-        moved = [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
-        assert moved == [], "%s: the earlier draws of cases %s moved" % (name, moved[:10])
-    # ... and the recipes of today hold the earlier keys and these, no others
-    new = {"cell_pixels", "components", "drop_cell_rows", "emit_offset", "refusal_slab"}
-    assert {k for r in recipes for k in r} == set(fixture["keys"]) | new
+    second = {"cell_pixels", "components", "drop_cell_rows", "emit_offset", "refusal_slab"}
+    for name, new in (("campaign_recipe_digests.json", second | {"keep"}), ("campaign_celldata_recipe_digests.json", {"keep"})):
+        with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+            fixture = json.load(f)
+        assert fixture["cases"] == mk.CASES == 300 and sorted(fixture["seeds"]) == ["1", "11"] and sorted(fixture["slices"]) == sorted(fz.KINDS)
+        assert {"kind", "dtype", "route", "kw", "field", "refusal", "drop_normals_row"} <= set(fixture["keys"]) and "keep" not in fixture["keys"]
+        assert ("cell_pixels" in fixture["keys"]) == (new == {"keep"}) == (second <= set(fixture["keys"]))
+        seeds, slices, recipes = mk.collect(fz, set(fixture["keys"]))
+        for what, got, want in [("seed " + s, seeds[s], fixture["seeds"][s]) for s in sorted(seeds)] + [(k, slices[k], fixture["slices"][k]) for k in fz.KINDS]:
+            assert len(got) == len(want)
+            moved = [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
+            assert moved == [], "%s, %s: the earlier draws of cases %s moved" % (name, what, moved[:10])
+        # ... and the recipes of today hold the earlier keys and these, no others
+        assert {k for r in recipes for k in r} == set(fixture["keys"]) | new
 
 
 def test_recipes_survive_json_and_run_through_the_references(oracle):
     """Every kind, route, normals, repeat and refusal the campaign draws: the recipe is plain data, its JSON round trip rebuilds
-    the same voxel bytes and the same expected mesh (and normals), and draw_case is a pure function of (seed, case)."""
+    the same voxel bytes and the same expected mesh (and normals), and draw_case is a pure function of (seed, case).  The keep
+    (recipe["keep"]): there only with components, resolved by a pure keep_arguments on the reference's counts, every stage's rows
+    the components of the kept reference mesh; the three rules, a second stage, K' = 0 and K' = K are all seen."""
+    import components_ref
     import fuzz_campaign as fz
     import test_components as cases
     from conftest import assert_same_mesh
@@ -148,6 +158,7 @@ def test_recipes_survive_json_and_run_through_the_references(oracle):
     seen = {"kinds": set(), "routes": set(), "normals": 0, "repeat": 0, "refusals": set(), "switch": 0, "beyond_2_53": 0}
     new = {"cell_pixels": 0, "components": 0, "all_three": 0, "drop_cell_rows": 0, "offset": 0, "offset_2_32": 0, "held": 0,
            "bspline": 0, "refusal_slab": set()}
+    keeps = {"largest": 0, "min_cells": 0, "mask": 0, "then": 0, "to_nothing": 0, "all_kept": 0, "some": 0, "odd_bytes": 0}
     recipes = _recipes(160)
     assert recipes == _recipes(160)
     for r in recipes:
@@ -203,6 +214,35 @@ def test_recipes_survive_json_and_run_through_the_references(oracle):
             assert r["refusal_slab"] in fz.SLAB_REFUSALS and r["refusal_slab"] in fz.REFUSALS["whole"] and r["refusal_slab"] in fz.REFUSAL_TEXT
             new["refusal_slab"].add(r["refusal_slab"])
         assert r.get("refusal") not in fz.SLAB_REFUSALS
+        # the keep: only with components; plain data (the round trip above); its stages resolved on the reference's counts
+        assert "keep" in r and (r["keep"] is None or r["components"])
+        stages = fz.keep_stages(r["keep"])
+        assert len(want["kept"]) == len(want["keep_args"]) == len(stages) and len(stages) == (0 if r["keep"] is None else 1 + bool(r["keep"]["then"]))
+        counts = want["components"][2] if r["components"] else None
+        for stage, kept, args, more in zip(stages, want["kept"], want["keep_args"], again["kept"]):
+            assert stage["rule"] in fz.KEEP_RULES and args[0] == stage["rule"]
+            held = counts.copy()
+            twice = fz.keep_arguments(stage, counts), fz.keep_arguments(json.loads(json.dumps(stage)), list(counts))
+            assert counts.tobytes() == held.tobytes()
+            for a in twice:
+                assert a[:2] == args[:2] and (a[2] is None) == (args[2] is None) == (stage["rule"] != "mask")
+                assert a[2] is None or (a[2].dtype == np.uint8 and a[2].shape == (len(counts),) and a[2].tobytes() == args[2].tobytes())
+            assert all(getattr(kept, n) is None if getattr(more, n) is None else getattr(kept, n).tobytes() == getattr(more, n).tobytes() for n in kept._fields)
+            assert (kept.normals is not None) == r["normals"] and (kept.cell_pixels is not None) == r["cell_pixels"]
+            # closure: the kept rows are the components of the kept mesh
+            rows = (kept.point_component, kept.cell_component, kept.component_cells)
+            cases.same(rows, components_ref.components(kept.cells, len(kept.points)), "closure")
+            cases.check_properties(kept.cells, len(kept.points), rows, "kept")
+            assert kept.cells.shape[1:] == want["mesh"].cells.shape[1:] and len(kept.component_cells) <= len(counts)
+            if stage is stages[0]:
+                keeps[stage["rule"]] += 1
+                keeps["all_kept"] += int(len(kept.component_cells) == len(counts) >= 2)
+                keeps["some"] += int(0 < len(kept.component_cells) < len(counts))
+            keeps["odd_bytes"] += int(args[2] is not None and bool((args[2] > 1).any()))
+            counts = kept.component_cells
+        if stages:
+            keeps["then"] += int(len(stages) == 2)
+            keeps["to_nothing"] += int(len(want["components"][2]) >= 1 and len(want["kept"][-1].component_cells) == 0)
         new["cell_pixels"] += int(r["cell_pixels"])
         new["components"] += int(r["components"])
         new["all_three"] += int(r["cell_pixels"] and r["components"] and r["normals"])
@@ -211,19 +251,28 @@ def test_recipes_survive_json_and_run_through_the_references(oracle):
         new["bspline"] += int(r["kind"] == "bspline" and (r["cell_pixels"] or r["components"]))
     assert min(v for k, v in new.items() if k != "refusal_slab") > 0 and new["refusal_slab"] == set(fz.SLAB_REFUSALS), new
     assert fz.REFUSAL_TEXT["cell_pixels_slab"] == "cell pixels" and fz.REFUSAL_TEXT["components_slab"] == "components"
+    assert min(keeps.values()) > 0, keeps
     # the options fix the two settings wherever the route offers them, and nothing else moves
     for on in (True, False):
         fixed = _recipes(160, cell_pixels=on, components=on)
         for r, f in zip(recipes, fixed):
             assert f["cell_pixels"] == f["components"] == (on and r["route"] in fz.CELLDATA_ROUTES)
-            assert {k: v for k, v in f.items() if k not in ("cell_pixels", "components")} == {k: v for k, v in r.items() if k not in ("cell_pixels", "components")}
+            # (the keep is drawn from a stream of its own and is there only with components)
+            assert f["keep"] is None or f["components"]
+            assert {k: v for k, v in f.items() if k not in ("cell_pixels", "components", "keep")} == {k: v for k, v in r.items() if k not in ("cell_pixels", "components", "keep")}
+        kept = _recipes(160, keep=on)
+        for r, f in zip(recipes, kept):
+            assert (f["keep"] is not None) == (on and r["components"])
+            assert r["keep"] is None or f["keep"] is None or f["keep"] == r["keep"]
+            assert {k: v for k, v in f.items() if k != "keep"} == {k: v for k, v in r.items() if k != "keep"}
     assert seen["kinds"] == set(fz.KINDS)
     assert seen["routes"] >= {"host", "device", "stream", "slabs", "thin_slabs", "count_emit", "held", "switch", "host_chunked"}
     assert len(seen["refusals"]) >= 5 and min(seen[k] for k in ("normals", "repeat", "switch", "beyond_2_53")) > 0, seen
 
 
 def test_gpu_slice_conditions_hold_on_the_oracle(oracle):
-    """The seeded slice of tests/test_gpu_campaign.py, from draw_case and the oracle alone: per kind and over the whole slice."""
+    """The seeded slice of tests/test_gpu_campaign.py, from draw_case and the oracle alone: per kind and over the whole slice --
+    the keep's conditions among them (fuzz_campaign.slice_conditions, slice_conditions_overall)."""
     import fuzz_campaign as fz
     facts = []
     for kind in fz.KINDS:
@@ -239,6 +288,9 @@ def test_gpu_slice_conditions_hold_on_the_oracle(oracle):
             # cell pixels and components by the rule of the case number, wherever the route offers them
             offered = r["route"] in fz.CELLDATA_ROUTES
             assert r["cell_pixels"] == (offered and (i + i // 10) % 2 == 0) and r["components"] == (offered and i % 3 != 2)
+            # every components case keeps, by the rule of the case number
+            assert (r["keep"] is not None) == r["components"]
+            assert r["keep"] is None or r["keep"]["rule"] == ("largest", "min_cells", "mask")[(i // 2) % 3]
         wants = [fz.expected(oracle, r) for r in recipes]
         mine = fz.slice_sequence_facts(recipes, wants)
         assert fz.slice_conditions(kind, mine) == []
@@ -248,6 +300,9 @@ def test_gpu_slice_conditions_hold_on_the_oracle(oracle):
                 assert len(w["cell_pixels"]) == len(w["mesh"].cells) and w["cell_pixels"].dtype == np.dtype(r["dtype"])
             if r["components"]:
                 assert f["K"] == len(w["components"][2]) and (f["K"] == 0) == f["empty"]
+                assert f["keep"]["ks"][0] == f["K"] and len(f["keep"]["ks"]) == 1 + len(w["kept"]) == 2 + bool(r["keep"]["then"])
+            else:
+                assert f["keep"] is None and w["kept"] == []
         facts += mine
     assert fz.slice_conditions_overall(facts) == []
     # the conditions see what they are there for: without its cases each is reported missing
@@ -255,7 +310,19 @@ def test_gpu_slice_conditions_hold_on_the_oracle(oracle):
     assert any("2^32" in m for m in fz.slice_conditions_overall([f for f in facts if f["offset"] < 2 ** 32]))
     assert any("pixel types" in m for m in fz.slice_conditions_overall([f for f in facts if not (f["cell_pixels"] and f["dtype"] == "float64")]))
     assert any("row of another size" in m for m in fz.slice_conditions_overall([f for f in facts if not f["other_pixels_row"]]))
+    # ... the keep's too: K' = 0, the id offset of 2^32 and more that drops something, each setting behind a keep, the rules
+    gone = fz.slice_conditions_overall([f for f in facts if not (f["keep"] and f["keep"]["ks"][0] >= 1 and f["keep"]["ks"][-1] == 0)])
+    assert any("K' = 0" in m for m in gone), gone
+    gone = fz.slice_conditions_overall([f for f in facts if not (f["keep"] and f["offset"] >= 2 ** 32 and f["keep"]["ks"][-1] < f["keep"]["ks"][0])])
+    assert any("2^32 that drops something" in m for m in gone), gone
+    for name, text in (("normals", "normals"), ("cell_pixels", "cell pixels"), ("components", "components")):
+        gone = fz.slice_conditions_overall([f for f in facts if name not in f["behind_keep"]])
+        assert any("%s behind a keep" % text in m for m in gone), gone
+    gone = fz.slice_conditions_overall([f for f in facts if not (f["keep"] and f["keep"]["rule"] == "mask" and f["keep"]["first_some"])])
+    assert any("rule mask" in m for m in gone), gone
+    assert any("K > 64" in m and "keep" in m for m in fz.slice_conditions_overall([f for f in facts if not (f["keep"] and f["K"] > 64)]))
     whole = [f for f in facts if f["kind"] == "whole"]
+    assert any("0 < K' < K" in m for m in fz.slice_conditions("whole", [f for f in whole if not (f["keep"] and f["keep"]["first_some"])]))
     assert any("K >= 2" in m for m in fz.slice_conditions("whole", [f for f in whole if not (f["components"] and f["K"] >= 2)]))
 
 
@@ -263,20 +330,36 @@ def test_compare_sees_one_bit(oracle):
     """compare() is the campaign's only judge: a mesh against itself passes, and one flipped bit of a coordinate, a swapped cell,
     a counter off by one or one flipped bit of a normal each fail; so do one flipped bit of a cell pixel, one label off by one in
     each of the three component rows, a K off by one, a missing row, a cell id below the id offset, and a first repeat (the
-    settings off) whose mesh differs from the last by one bit."""
+    settings off) whose mesh differs from the last by one bit.  The keep, on a recipe with normals, cell pixels, components and a
+    keep that drops something, the reference against itself: one flipped bit in a kept point, normal or cell pixel, one kept cell
+    id left un-renumbered, one label off by one in each kept row, K' or a returned count off by one, a counter changed by the
+    keep, a missing stage and a non-null pointer for an empty row each fail."""
     import copy
     import fuzz_campaign as fz
     import pytest
     r = next(r for r in _recipes(200, kind="border", cell_pixels=True, components=True) if r["normals"] and r["kw"]["project"])
-    assert r == next(dict(q, cell_pixels=True, components=True) for q in _recipes(200, kind="border") if q["normals"] and q["kw"]["project"])
+    # (the keep is drawn from a stream of its own: it is the one thing the options' recipe holds beyond the plain one's)
+    assert r == next(dict(q, cell_pixels=True, components=True, keep=r["keep"]) for q in _recipes(200, kind="border") if q["normals"] and q["kw"]["project"])
     want = fz.expected(oracle, r)
     assert len(want["mesh"].points) > 3 and len(want["mesh"].cells) > 1 and len(want["cell_pixels"]) == len(want["mesh"].cells)
 
-    def got():
+    def stage(w, k_before, counters):
+        """What run_case records behind one keep, from the reference's own Kept."""
+        mesh = copy.deepcopy(want["mesh"])
+        mesh.points, mesh.cells = w.points.copy(), w.cells.copy()
+        sizes = (len(w.points), len(w.cells), len(w.component_cells))
+        return {"returned": sizes, "ms": 0.0, "result": sizes[:2], "mesh": mesh, "normals": None if w.normals is None else w.normals.copy(),
+                "cell_pixels": None if w.cell_pixels is None else w.cell_pixels.copy(),
+                "components": (w.point_component.copy(), w.cell_component.copy(), w.component_cells.copy()), "n_components": sizes[2],
+                "null": tuple(n == 0 for n in sizes), "counters_before": dict(counters), "counters": dict(counters), "k_before": k_before}
+
+    def got(want=want):
         m = want["mesh"]
-        return {"mesh": copy.deepcopy(m), "normals": want["normals"].copy(), "counters": {k: m.info[k] for k in fz.COUNTERS},
+        counters = {k: m.info[k] for k in fz.COUNTERS}
+        ks = [len(want["components"][2])] + [len(w.component_cells) for w in want["kept"]]
+        return {"mesh": copy.deepcopy(m), "normals": want["normals"].copy(), "counters": counters,
                 "cell_pixels": want["cell_pixels"].copy(), "components": tuple(a.copy() for a in want["components"]),
-                "n_components": len(want["components"][2])}
+                "n_components": len(want["components"][2]), "kept": [stage(w, k, counters) for w, k in zip(want["kept"], ks)]}
     fz.compare(got(), want)
     g = got()
     g["mesh"].points.view(np.uint32)[2, 1] ^= 1
@@ -352,3 +435,66 @@ def test_compare_sees_one_bit(oracle):
     g["first_counters"]["proj_stop_steps"] += 1
     with pytest.raises(AssertionError, match="off"):
         fz.compare(g, want)
+
+    # ---- the keep: the reference against itself, stage by stage ----
+    for rk in _recipes(200, kind="border", cell_pixels=True, components=True, keep="min_cells"):
+        if not (rk["normals"] and rk["kw"]["project"] and rk["keep"]["pick"] == "quantile"):
+            continue
+        wk = fz.expected(oracle, rk)
+        first = wk["kept"][0]
+        # the cells of the mesh that the first stage keeps, with the ids they had before: some of them are renumbered
+        old = wk["mesh"].cells[np.isin(wk["components"][1], np.flatnonzero(np.isin(wk["components"][2], first.component_cells)))]
+        if 0 < len(first.component_cells) < len(wk["components"][2]) and len(first.cells) > 1 and old.shape == first.cells.shape \
+                and (old != first.cells).any() and np.isfinite(first.normals).any():
+            break
+    else:
+        raise AssertionError("no recipe with normals, cell pixels, components and a keep that drops something")
+    assert len(first.points) < len(wk["mesh"].points) and len(first.cells) < len(wk["mesh"].cells) and first.cell_pixels is not None
+    fz.compare(got(wk), wk)
+
+    def fails(change, match):
+        g = got(wk)
+        change(g["kept"][0], g)
+        with pytest.raises(AssertionError, match=match):
+            fz.compare(g, wk)
+
+    def flip(row, at):
+        row.view(np.uint8 if row.dtype.itemsize == 1 else np.uint32)[at] ^= 1
+    moved = tuple(np.argwhere(old != first.cells)[0])
+    finite = tuple(np.argwhere(np.isfinite(first.normals))[0])
+    fails(lambda k, g: flip(k["mesh"].points, (1, 2)), "keep stage 0")                              # one bit of a kept point
+    fails(lambda k, g: flip(k["normals"], finite), "keep stage 0: normals")                         # ... of a kept normal
+    fails(lambda k, g: flip(k["cell_pixels"].view(np.uint8), -1), "cell pixels")                    # ... of a kept cell pixel
+    fails(lambda k, g: k["mesh"].cells.__setitem__(moved, old[moved]), "keep stage 0")              # one id left un-renumbered
+    for row in range(3):
+        fails(lambda k, g: k["components"][row].__setitem__(-1, k["components"][row][-1] + 1), "component")
+    fails(lambda k, g: k.__setitem__("n_components", k["n_components"] + 1), "K")
+    for at in range(3):
+        fails(lambda k, g: k.__setitem__("returned", tuple(v + (i == at) for i, v in enumerate(k["returned"]))), "returned counts")
+    fails(lambda k, g: k.__setitem__("result", (k["result"][0], k["result"][1] - 1)), "result counts")
+    fails(lambda k, g: k["counters"].__setitem__("proj_iterations", k["counters"]["proj_iterations"] + 1), "counters changed by the keep")
+    fails(lambda k, g: g["kept"].pop(), "keep stages ran")                                          # a missing stage
+    fails(lambda k, g: g.__setitem__("kept", []), "keep stages ran")
+    fails(lambda k, g: k.__setitem__("null", (False, False, True)), "null device pointers")
+    # an id offset: carried by the kept cells, taken off; a kept id outside [offset, offset + kept points) fails
+    g = got(wk)
+    g["emit_offset"] = 2 ** 32 + 5
+    g["mesh"].cells = g["mesh"].cells + np.uint64(2 ** 32 + 5)
+    with pytest.raises(AssertionError, match="kept cell id outside"):
+        fz.compare(g, wk)
+    for k in g["kept"]:
+        k["mesh"].cells = k["mesh"].cells + np.uint64(2 ** 32 + 5)
+    fz.compare(g, wk)
+    g["kept"][0]["mesh"].cells[0, 0] = np.uint64(2 ** 32 + 5 + len(first.points))
+    with pytest.raises(AssertionError, match="kept cell id outside"):
+        fz.compare(g, wk)
+    # a keep to nothing: every pointer of an empty row is null, and a non-null one fails
+    nothing = dict(rk, keep=dict(rule="min_cells", pick="above_max", quantile=0.0, plus_one=False, then=None))
+    wn = fz.expected(oracle, nothing)
+    assert len(wn["kept"]) == 1 and len(wn["kept"][0].points) == len(wn["kept"][0].cells) == len(wn["kept"][0].component_cells) == 0
+    fz.compare(got(wn), wn)
+    for at in range(3):
+        g = got(wn)
+        g["kept"][0]["null"] = tuple(i != at for i in range(3))
+        with pytest.raises(AssertionError, match="null device pointers"):
+            fz.compare(g, wn)

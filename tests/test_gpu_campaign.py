@@ -21,6 +21,21 @@ whose cells carry two raw values; a repeat, a refused call ahead and a developme
 components case with a non-zero id offset and one of 2^32 or more; a cell-pixel case and a components case on a context that
 still holds the rows of a mesh of another size -- the rows the run met are held to the rows the recipes foretell.
 
+Every components case keeps (cuberille_keep_components, recipe["keep"]): the rule is KEEP_RULES[(i // 2) % 3] -- largest,
+min_cells, mask --, the pick, the mask's bytes and a second stage are drawn, every argument is resolved on the REFERENCE's counts,
+and after each stage the library's counts, mesh (mesh_host() on the device route, download() elsewhere), normals, cell pixels,
+rows, K, device pointers and counters are held to keep_ref.keep on the oracle's mesh and the references' rows -- nothing of it
+is the library's.  In a repeating case the second extraction keeps too, and the third, launched blindly behind that keep, is
+still the first one's mesh.  The context stays as the keep left it.  Per kind: at least 5 keep cases, quads and triangles among
+them, at least 4 whose first stage keeps some of several (0 < K' < K; the B-spline slice, checked on the oracle and the host walk, has 6).  Over the whole
+slice: each rule at least 3 times with 0 < K' < K; K' = 0 from K >= 1; K' = K >= 2 (nothing moves); a keep on an empty mesh;
+with normals, with cell pixels, with both; with NaN coordinates or a NaN normal in the kept part (the slice offers several: the
+border's cases 3, 4, 6, 10, 12, region 18, band 15); at K > 64 (K = 311, 110, 85 and 67); a count + emit keep with an id offset of 2^32
+and more that drops something (region, case 7); in a repeating case; on the held route; under a development switch; behind a
+refused call; chained; on a mask with bytes other than 0 and 1; and, for normals, cell pixels and components each, a case with
+the setting on whose predecessor on the context ran a keep with 0 < K' < K and left that setting's row (behind_keep) -- the
+cases that ran behind a keep, by what the library returned, are held to those the recipes foretell.
+
 Case i of a kind takes pixel type DTYPES[i % 10] and the kind's routes in turn; everything else is drawn, and the seeds
 (fuzz_campaign.SLICE) are the first for which the oracle alone shows the conditions of fuzz_campaign.slice_conditions: all ten pixel
 types, every route at least twice, quads and triangles, projection on and off, the three geometry forms, a start index other
@@ -37,7 +52,9 @@ whole words round a ragged box) and 3 + 3 (one more below a box that spans x and
 60 000 voxels.  Wall time of each test on an MI355X box (16 host
 threads, the references included), pytest's own figures: whole volume 2.0 s (24 cases in 0.35 s; the rest is the first context of
 the process loading the code objects), border 0.15 s, region 0.07 s, band 0.12 s, B-spline 0.31 s (20 cases each, the B-spline's
-with one subprocess per projecting case).
+with one subprocess per projecting case).  With the keeps -- one or two per components case, every row downloaded a second time,
+the numpy reference of a keep -- measured the same way: whole volume 2.06 s (24 cases in 0.34 s), border 0.15 s, region 0.07 s,
+band 0.12 s, B-spline 0.30 s: what a keep adds is below the figures' last digit.
 """
 import time
 
@@ -57,7 +74,7 @@ def _run_slice(pkg, oracle, kind):
         return _FACTS[kind]
     recipes = fz.slice_recipes(kind)
     contexts = fz.open_contexts(pkg)
-    wants, rows = [], []
+    wants, rows, behind = [], [], []
     t0 = time.time()
     try:
         for recipe in recipes:
@@ -71,6 +88,9 @@ def _run_slice(pkg, oracle, kind):
                          fz.meets_pixels_row_of_another_size(got["pixels_row_before"], recipe, n_cells),
                          fz.meets_components_row_of_another_size(got["components_row_before"], recipe, n_points, n_cells)))
             assert (got["cell_pixels"] is not None) == recipe["cell_pixels"] and (got["components"] is not None) == recipe["components"]
+            # every components case keeps, every stage ran, and the case knows whether it ran behind a keep that moved the rows
+            assert len(got["kept"]) == len(fz.keep_stages(recipe["keep"])) == len(want["kept"]) and bool(got["kept"]) == recipe["components"]
+            behind.append(fz.behind_keep(got["keep_before"], (got["row_before"], got["pixels_row_before"], got["components_row_before"]), recipe))
     finally:
         fz.close_contexts(contexts)
     print("%s: %d cases in %.2f s" % (kind, len(wants), time.time() - t0))
@@ -78,6 +98,8 @@ def _run_slice(pkg, oracle, kind):
     facts = fz.slice_sequence_facts(recipes, wants)
     # the rows the run met -- normals, cell pixels, components -- are the rows the recipes foretell
     assert [(f["other_row"], f["other_pixels_row"], f["other_components_row"]) for f in facts] == rows
+    # ... and so are the cases that ran behind a keep: what the library returned (K, K') against what the reference foretells
+    assert [f["behind_keep"] for f in facts] == behind
     assert fz.slice_conditions(kind, facts) == []
     _FACTS[kind] = facts
     return facts

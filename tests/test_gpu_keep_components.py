@@ -1,6 +1,9 @@
 """Compaction by component on the GPU (cuberille_keep_components): every row the library hands out after the call against the numpy
 reference of tests/keep_ref.py -- held to the components' definition by tests/test_keep_components.py -- applied to what the
-library itself handed out before the call, compared as bytes.  No tolerance anywhere.
+library itself handed out before the call, compared as bytes.  No tolerance anywhere.  (A kept mesh is held to a reference that
+owes nothing to the library by the campaign -- tests/fuzz_campaign.py, its slice in tests/test_gpu_campaign.py: keep_ref on the
+oracle's mesh.  Here are the cases the campaign cannot look at: the context's device memory with the settings switched off
+behind a keep, in either order, and cell pixels of another width and cell count left on across keeps.)
 """
 import os
 import subprocess
@@ -275,6 +278,106 @@ def test_the_next_extraction_and_memory(pkg):
     finally:
         fresh.close()
         e.close()
+
+
+def mesh_bytes(e, components=True):
+    """The mesh (and the three component rows) the context holds, as bytes."""
+    mesh = e.download()
+    return [a.tobytes() for a in (mesh.points, mesh.cells) + (tuple(e.download_components()) if components else ())]
+
+
+@pytest.mark.parametrize("order", ("normals and cell pixels off, components on", "components off first"))
+def test_settings_off_behind_a_keep(pkg, order):
+    """A keep lets every row of the mesh change places with a spare row sized by the kept counts -- the normals and the cell
+    pixels too.  Switched off behind the keep, cuberille_set_point_normals and cuberille_set_cell_pixels release BOTH rows of
+    their pair: context A, which extracted with normals and cell pixels on, kept the largest component and switched the two off,
+    holds byte for byte the device memory, the kept mesh and the component rows of context B, which never heard of the two
+    (before the fix the extraction-sized spare rows stayed until components were switched off).  The other order -- components
+    off first, which moves the kept mesh back into the buffers the extraction was sized for, then the two -- leaves what a
+    context holds that never heard of any of the three.  Either way the next extraction with everything on again, and its keep,
+    give the bytes a fresh context gives."""
+    vox = cases.gradient_noise((24, 30, 70), seed=3)
+    iso = cases.noise_isos(vox)[1]
+    vol = pkg.Volume(vox)
+    prm = params(pkg, iso, project=1, triangles=1)
+
+    def extract_and_keep(e, extras, what):
+        e.set_components(True)
+        e.set_point_normals(extras)
+        e.set_cell_pixels(extras)
+        res = e.extract_host(vol, prm)
+        whole = snapshot(e, extras, extras)
+        after = keep_held(e, whole, "largest", what=(order, what))
+        assert 0 < len(after["cells"]) < len(whole["cells"]) and 1 == len(after["component_cells"]) < len(whole["component_cells"])
+        return whole, after, counters(res)
+
+    a, b, fresh = pkg.Extractor(0), pkg.Extractor(0), pkg.Extractor(0)
+    try:
+        _, kept, _ = extract_and_keep(a, True, "A")
+        if order.startswith("normals"):
+            _, kept_b, _ = extract_and_keep(b, False, "B")
+            a.set_point_normals(False)
+            a.set_cell_pixels(False)
+            assert mesh_bytes(a) == mesh_bytes(b) == [kept[n].tobytes() for n in ("points", "cells", "point_component", "cell_component", "component_cells")]
+            assert a.components_device()[0] is not None and a.n_components() == 1
+            assert a.device_bytes() == b.device_bytes(), (a.device_bytes(), b.device_bytes())
+        else:
+            b.extract_host(vol, prm)                                            # (never heard of any of the three)
+            a.set_components(False)
+            # (the kept mesh stays, with its normals and cell pixels, in the buffers the extraction was sized for)
+            assert mesh_bytes(a, False) == [kept["points"].tobytes(), kept["cells"].tobytes()]
+            assert a.download_normals().tobytes() == kept["normals"].tobytes() and a.download_cell_pixels().tobytes() == kept["cell_pixels"].tobytes()
+            a.set_point_normals(False)
+            a.set_cell_pixels(False)
+            assert mesh_bytes(a, False) == [kept["points"].tobytes(), kept["cells"].tobytes()]
+            assert a.device_bytes() == b.device_bytes(), (a.device_bytes(), b.device_bytes())
+        for call in (a.download_normals, a.download_cell_pixels):
+            with pytest.raises(pkg._abi.CuberilleError) as e:
+                call()
+            assert e.value.code == STATE
+        # everything on again: the extraction, launched from this context's history, and the keep behind it
+        whole_f, kept_f, counters_f = extract_and_keep(fresh, True, "fresh")
+        whole_a, kept_a, counters_a = extract_and_keep(a, True, "A again")
+        for got, want, what in ((whole_a, whole_f, "extraction"), (kept_a, kept_f, "keep")):
+            same(got, keep_ref.Kept(**{k: v for k, v in want.items() if k != "offset"}), (order, what, "against a fresh context"))
+        assert counters_a == counters_f
+    finally:
+        for e in (a, b, fresh):
+            e.close()
+
+
+def test_another_pixel_width_and_cell_count_behind_a_keep(pkg, ex):
+    """Cell pixels stay on across three extractions of one context, a keep behind each: uint8, then float64 on a larger mesh (the
+    pixel row the keep left in place is one of the kept size and of one byte per cell, its extraction-sized partner a spare row
+    of one byte per cell too), then uint8 on the smaller mesh again.  Every extraction gives the points and cells a fresh context
+    gives and the pixels of cell_pixels_ref on the volume; every keep the reference's on those rows."""
+    import cell_pixels_ref
+    small, large = cases.gradient_noise((20, 22, 70), seed=9), cases.gradient_noise((24, 30, 70), seed=3)
+    ex.set_cell_pixels(True)
+    fresh = pkg.Extractor(0)
+    cells = []
+    try:
+        for step, (vox, dtype, rule) in enumerate(((small, np.uint8, "largest"), (large, np.float64, "min_cells"), (small, np.uint8, "mask"))):
+            vox = vox.astype(dtype)
+            iso = cases.noise_isos(vox)[1]
+            prm = params(pkg, iso, project=1, triangles=1)
+            ex.extract_host(pkg.Volume(vox), prm)
+            whole = snapshot(ex, pixels=True)
+            fresh.extract_host(pkg.Volume(vox), prm)
+            want = fresh.download()
+            assert whole["points"].tobytes() == want.points.tobytes() and whole["cells"].tobytes() == want.cells.tobytes(), step
+            pixels = cell_pixels_ref.cell_pixels(*cell_pixels_ref.whole(vox, iso if np.dtype(dtype).kind == "f" else int(iso)), True)
+            assert whole["cell_pixels"].dtype == pixels.dtype == np.dtype(dtype) and whole["cell_pixels"].tobytes() == pixels.tobytes(), step
+            counts = whole["component_cells"]
+            assert len(counts) >= 3
+            n = int(np.sort(counts)[-2])
+            after = keep_held(ex, whole, rule, n, (counts < n) if rule == "mask" else None, ("pixel width", step, rule))
+            assert 0 < len(after["cells"]) < len(whole["cells"]) and after["cell_pixels"].dtype == np.dtype(dtype)
+            cells.append((len(whole["cells"]), len(after["cells"])))
+        # (another cell count every time, before and behind the keep)
+        assert cells[0][0] == cells[2][0] != cells[1][0] and cells[0][1] != cells[1][1]
+    finally:
+        fresh.close()
 
 
 def test_refusals_and_the_allocation_drill(pkg, ex):
