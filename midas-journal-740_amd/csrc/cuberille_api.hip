@@ -106,13 +106,39 @@ struct HostBuf {
   }
 };
 
+// ---- the mesh's rows and the optional outputs (the attributes' words: kAttrWords, below enum Route) ----------
+enum Attr { ATTR_NONE = -1, ATTR_NORMALS, ATTR_CELL_PIXELS, ATTR_COMPONENTS, N_ATTRS };
+enum Row { ROW_POINTS, ROW_CELLS, ROW_NORMALS, ROW_CELL_PIX, ROW_COMP_POINT, ROW_COMP_CELL, ROW_COMP_COUNT, N_ROWS };
+enum Per { PER_POINT, PER_CELL, PER_COMPONENT, N_PERS };
+// A row: what it has one element of, that element's bytes, its attribute (ATTR_NONE: the mesh itself), and whether a
+// reservation for no element still asks for one.  In the order an emit reserves them, and the keep their spare partners.
+struct RowInfo { const char *name; Per per; size_t (*elem)(int verts_per_cell, size_t pixel); int attr; bool oneIfEmpty; };
+const RowInfo kRows[N_ROWS] = {
+    {"points", PER_POINT, [](int, size_t) { return 3 * sizeof(float); }, ATTR_NONE, false},
+    {"cells", PER_CELL, [](int nv, size_t) { return (size_t)nv * sizeof(uint64_t); }, ATTR_NONE, true},
+    {"normals", PER_POINT, [](int, size_t) { return 3 * sizeof(float); }, ATTR_NORMALS, false},
+    {"cellPix", PER_CELL, [](int, size_t pixel) { return pixel; }, ATTR_CELL_PIXELS, true},
+    {"compPoint", PER_POINT, [](int, size_t) { return sizeof(uint32_t); }, ATTR_COMPONENTS, false},
+    {"compCell", PER_CELL, [](int, size_t) { return sizeof(uint32_t); }, ATTR_COMPONENTS, true},
+    {"compCount", PER_COMPONENT, [](int, size_t) { return sizeof(uint64_t); }, ATTR_COMPONENTS, false},
+};
+const Per kAttrOf[N_ATTRS] = {PER_POINT, PER_CELL, PER_POINT};   // what an attribute hangs on: an emit with none of them reserves none of its rows
+// The bytes a row of n[per] elements is reserved with (n: points, cells, components)
+size_t row_reserve_bytes(int r, const u64 n[N_PERS], int verts_per_cell, size_t pixel) {
+  const u64 have = n[kRows[r].per];
+  return (size_t)(have || !kRows[r].oneIfEmpty ? have : 1) * kRows[r].elem(verts_per_cell, pixel);
+}
+struct MeshRow { DevBuf row, spare; };
+
 }  // namespace
 
 struct cuberille_ctx {
   int device = 0;
   hipStream_t own = nullptr, stream = nullptr;
   std::string err;
-  DevBuf voxOwn, bits, flatBits, occ, prefix, segPre, blockTot, blockBase, points, cells, cmap, headV, headQ, vqueue, escList;
+  DevBuf voxOwn, bits, flatBits, occ, prefix, segPre, blockTot, blockBase, cmap, headV, headQ, vqueue, escList;
+  MeshRow rows[N_ROWS];                  // the mesh (kRows): an attribute's rows exist only while its setting is on, a spare behind a keep
+  DevBuf &row(int r) { return rows[r].row; }
   DevBuf gradImg, rgA, rgB, rgScratch;   // gradient_variant 1: the gradient image and what its passes go through
   DevBuf heldGrad;                       // cuberille_hold_gradient: the float gradient image of the first projecting extraction
   HeldGradient held{};                   // ... with its geometry (img == null: none yet); what every later walk follows
@@ -133,24 +159,14 @@ struct cuberille_ctx {
   int64_t regionSize[3] = {0, 0, 0};     // ... and its size
   int bsValidBits = 0;                   // the coefficient image of the last B-spline extraction: its width (0: none) ...
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
-  bool pointNormals = false;             // cuberille_set_point_normals: every later extraction also leaves the normal of every point ...
-  DevBuf normals;                        // ... 3 floats per point of `points`, same order (reserved and written only while the setting is on)
-  bool countNormals = false;             // ... the setting as the running count/emit pair found it
-  bool haveNormals = false;              // ... and whether the last mesh came with its normals
-  bool cellPixels = false;               // cuberille_set_cell_pixels: every later extraction also leaves the pixel of every cell's voxel ...
-  DevBuf cellPix;                        // ... one value of the pixel type per cell of `cells`, same order (reserved and written only while the setting is on)
-  bool countCellPixels = false;          // ... the setting as the running count/emit pair found it
-  bool haveCellPixels = false;           // ... and whether the last mesh came with them
-  bool components = false;               // cuberille_set_components: every later extraction also labels the mesh's connected surfaces ...
-  DevBuf compParent, compPoint, compCell, compCount, compScan;   // ... the rows of CompRows (reserved and written only while the setting is on)
-  u64 *hostK = nullptr;                  // ... K on its way to the host (pinned; allocated with the first extraction that has the setting on)
-  bool countComponents = false;          // ... the setting as the running count/emit pair found it
-  bool haveComponents = false;           // ... and whether the last mesh came with them
+  // the optional outputs (kAttrWords): the setting, the setting as the running count/emit pair found it, whether the last mesh has it
+  struct { bool on = false, counting = false, have = false; } attr[N_ATTRS];
+  // the components' scratch, no rows of the mesh: the union-find's forest and the numbering's scan row (CompRows), and what
+  // cuberille_keep_components decides and scans in; freed with the component rows
+  DevBuf compParent, compScan, keepSel, keepScan, *const compScratch[4] = {&compParent, &compScan, &keepSel, &keepScan};
+  u64 *hostK = nullptr;                  // K on its way to the host (pinned; allocated with the first extraction that has components on)
   u64 nComponents = 0;                   // ... K of the last mesh
-  // cuberille_keep_components: the decision and the scans' rows, and the spare rows the kept mesh is written to before the
-  // buffers change places (reserved by that call alone, sized by the kept counts; freed with the component rows) ...
-  DevBuf keepSel, keepScan, sparePoints, spareCells, spareNormals, spareCellPix, spareCompPoint, spareCompCell, spareCompCount;
-  u64 *hostKeep = nullptr;               // ... K', n_points', n_cells' on their way to the host (pinned; allocated by the first call)
+  u64 *hostKeep = nullptr;               // cuberille_keep_components: K', n_points', n_cells' on their way to the host (pinned; allocated by the first call)
   hipEvent_t keepEv[2] = {};             // ... and the call's one event pair (created by the first call)
   HostBuf hostPoints, hostCells;         // cuberille_mesh_host: the last mesh in host memory of the context's own
   bool hostMeshValid = false;            // ... holds the mesh of the last emit
@@ -216,17 +232,18 @@ hipError_t mark(cuberille_ctx *c, Mark m);
 
 // every device buffer a context owns (cuberille_destroy frees them, cuberille_debug_device_bytes adds them up)
 std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
-  return {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
-          &c->points, &c->cells, &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
-          &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch, &c->normals, &c->cellPix,
-          &c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan,
-          &c->keepSel, &c->keepScan, &c->sparePoints, &c->spareCells, &c->spareNormals, &c->spareCellPix, &c->spareCompPoint,
-          &c->spareCompCell, &c->spareCompCount};
+  std::vector<DevBuf *> all = {&c->voxOwn, &c->bits, &c->flatBits, &c->occ, &c->prefix, &c->segPre, &c->blockTot, &c->blockBase,
+                               &c->cmap, &c->headV, &c->headQ, &c->vqueue, &c->escList,
+                               &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch};
+  all.insert(all.end(), c->compScratch, c->compScratch + 4);
+  for (MeshRow &m : c->rows) { all.push_back(&m.row); all.push_back(&m.spare); }
+  return all;
 }
 
 // cuberille_set_components: the rows as their kernels take them
 CompRows comp_rows(cuberille_ctx *c) {
-  return {(u32 *)c->compParent.p, (u32 *)c->compPoint.p, (u32 *)c->compCell.p, (u64 *)c->compCount.p, c->compScan.p};
+  return {(u32 *)c->compParent.p, (u32 *)c->row(ROW_COMP_POINT).p, (u32 *)c->row(ROW_COMP_CELL).p, (u64 *)c->row(ROW_COMP_COUNT).p,
+          c->compScan.p};
 }
 
 int fail(cuberille_ctx *c, int code, const std::string &msg) {
@@ -255,6 +272,12 @@ size_t pixel_size(int pt) {
     case CUBERILLE_PIX_F64: case CUBERILLE_PIX_I64: case CUBERILLE_PIX_U64: return 8;
   }
   return 0;
+}
+
+// The last mesh (as extracted, or as cuberille_keep_components left it): the bytes of a row -- what a download copies
+size_t mesh_row_bytes(const cuberille_ctx *c, int r) {
+  const u64 n[N_PERS] = {c->res.n_points, c->res.n_cells, c->nComponents};
+  return (size_t)n[kRows[r].per] * kRows[r].elem(c->res.verts_per_cell, pixel_size(c->pixel_type));
 }
 
 // 3x3 inverse by cofactors (the parity tests hand the same matrix to the CPU checker, which
@@ -386,6 +409,42 @@ bool converts(int pixel_type, double v) {
 // (the border, the region), not at the band nor at the parameters.
 enum Route { ROUTE_DEVICE, ROUTE_HOST, ROUTE_SLAB, ROUTE_STEP, ROUTE_STREAM, ROUTE_GROUP, ROUTE_WARM_UP, N_ROUTES };
 
+// (an all-zero slab stands for the whole volume)
+bool whole_volume(const cuberille_slab *slab) {
+  return !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);
+}
+
+// What is said of an attribute (modelled on kViewWords): its name in words and as the C setter.  Every attribute describes ONE
+// context's whole volume, so why a route does not offer it (null: offered) and why a slab does not is said once for all.
+const struct { const char *noun, *fn; } kAttrWords[N_ATTRS] = {
+    {"point normals", "cuberille_set_point_normals"}, {"cell pixels", "cuberille_set_cell_pixels"}, {"components", "cuberille_set_components"}};
+const char *const kAttrRoute[N_ROUTES] = {nullptr, nullptr, nullptr, " belong to one context's whole volume: not offered with the cuberille_step_* calls",
+                                          nullptr, "they belong to one context's whole volume, not offered in a group", nullptr};
+const char *const kAttrSlab = " belong to a whole volume: not offered on slabs";
+std::string attr_missing(int a) { return std::string("no ") + kAttrWords[a].noun + ": the last extraction ran with the setting off (" + kAttrWords[a].fn + ")"; }
+
+// Is every attribute that is on offered to an extraction on this route, with these parameters (null: not looked at), of this
+// slab of a buffer of nz slices (null or all zero: the whole volume; a slab that is the whole buffer passes)?  CUBERILLE_OK, or
+// the first refusal with its text in *why.  No device is touched.
+int attrs_offered(const cuberille_ctx *c, const cuberille_params *prm, Route route, const cuberille_slab *slab, int64_t nz, const char **why) {
+  static thread_local std::string text;
+  auto no = [&](const std::string &m) { text = m; *why = text.c_str(); return CUBERILLE_ERR_ARGUMENT; };
+  *why = "";
+  for (int a = 0; a < N_ATTRS; a++) {
+    if (!c->attr[a].on) continue;
+    const std::string noun = kAttrWords[a].noun, fn = kAttrWords[a].fn, name = noun + " (" + fn + ")";
+    if (const char *r = kAttrRoute[route]) return route == ROUTE_GROUP ? no("has " + noun + " set (" + fn + "): " + r) : no(name + r);
+    if (a == ATTR_NORMALS && prm) {   // one definition, the central-difference gradient of the CURRENT whole volume at the final vertex
+      if (c->holdGradient)
+        return no(name + " are not offered on a context holding a gradient (cuberille_hold_gradient): the reference would evaluate the stale image there");
+      if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
+        return no(name + " are the central-difference gradient: not offered with CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN");
+    }
+    if (!whole_volume(slab) && (slab->global_nz != nz || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + nz)) return no(name + kAttrSlab);
+  }
+  return CUBERILLE_OK;
+}
+
 int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox, const cuberille_params *prm, Route route = ROUTE_DEVICE) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!img || !vox || !prm) return fail(c, CUBERILLE_ERR_ARGUMENT, "null image, voxel or parameter pointer");
@@ -415,24 +474,9 @@ int validate(cuberille_ctx *c, const cuberille_image_desc *img, const void *vox,
     if (c->holdGradient)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "the B-spline interpolator is not offered on a context holding a gradient (cuberille_hold_gradient)");
   }
-  if (c->pointNormals) {
-    // cuberille_set_point_normals: one definition, the central-difference gradient of the CURRENT whole volume at the final vertex
-    // (a slab that is not the whole volume: count_prepare)
-    if (route == ROUTE_STEP)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to one context's whole volume: not offered with the cuberille_step_* calls");
-    if (c->holdGradient)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) are not offered on a context holding a gradient "
-                                             "(cuberille_hold_gradient): the reference would evaluate the stale image there");
-    if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) are the central-difference gradient: not offered with CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN");
-  }
-  // cuberille_set_cell_pixels: the pixel of each cell's voxel in ONE context's whole volume (a slab that is not the whole volume:
-  // count_prepare)
-  if (c->cellPixels && route == ROUTE_STEP)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to one context's whole volume: not offered with the cuberille_step_* calls");
-  // cuberille_set_components: a component does not stop at a slab's face (a slab that is not the whole volume: count_prepare)
-  if (c->components && route == ROUTE_STEP)
-    return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) belong to one context's whole volume: not offered with the cuberille_step_* calls");
+  // the optional outputs against the route (a slab that is not the whole volume: count_prepare)
+  const char *why = "";
+  if (const int rc = attrs_offered(c, prm, route, nullptr, 0, &why)) return fail(c, rc, why);
   // the iso value is an InputPixelType in the reference (h:180-181)
   if (!converts(img->pixel_type, prm->iso_value))
     return fail(c, CUBERILLE_ERR_ARGUMENT, "iso value is not representable in the pixel type");
@@ -717,11 +761,6 @@ int view_of(cuberille_ctx *c, const cuberille_image_desc *img, const cuberille_p
   return rc ? fail(c, rc, why) : CUBERILLE_OK;
 }
 
-// (an all-zero slab stands for the whole volume)
-bool whole_volume(const cuberille_slab *slab) {
-  return !slab || (slab->global_nz == 0 && slab->z_begin == 0 && slab->own_z0 == 0 && slab->own_z1 == 0);
-}
-
 // RecursiveGaussianImageFilter::SetUp of ITK 3.x (Deriche's fourth-order recursive Gaussian): the 20 coefficients of one
 // separable pass -- order 0 smoothing, order 1 first derivative with NormalizeAcrossScale (txx:490) -- for `sigma` in
 // physical units on an axis of the given spacing.  Evaluated on the host in double, once per extraction; the kernels
@@ -842,35 +881,29 @@ size_t cmap_bytes(const Grid &g, const Tuning &t) {
 // blindly from these counts (cuberille_step_begin: + 25 %), taken where a buffer has to grow anyway (dyn: they are that).
 struct Want { size_t bytes, cover; };
 struct EmitSizes {
-  Want points, cells;                 // required
-  Want normals;                       // cuberille_set_point_normals: required while the setting is on (0 bytes: off)
-  Want cellPix;                       // cuberille_set_cell_pixels: likewise, one pixel per cell
-  Want compPoint, compCell, compCount, compScan;   // cuberille_set_components: likewise -- 4 B per point (twice: the forest and the
-                                      // labels), 4 B per cell, 8 B per point (K <= points), the numbering's scan row
+  Want rows[N_ROWS];                  // kRows: points and cells required; an attribute's while it is on and the mesh has what it hangs on
+  Want compScan;                      // cuberille_set_components: the numbering's scan row (the forest is sized as the point labels)
   Want headV, headQ;                  // optional (4 B per 64 outputs)
   size_t cmap, escCap;                // optional; THIN_HALO: entries of the escape list (required there)
 };
 
+// on: the attributes as the count found them; pixel: the size of a pixel
 EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u64 nV, u64 totQ, u64 nQ, size_t planeCorners,
-                     size_t nwords, bool normals, size_t cellPixelBytes = 0,
-                     bool components = false) {
+                     size_t nwords, const bool on[N_ATTRS], size_t pixel) {
   const u64 nextV = dyn ? nV : nV + nV / 4 + 4096, nextQ = dyn ? nQ : totQ + totQ / 4 + 4096;
-  const size_t quad = (triangles ? 6 : 4) * sizeof(u64);
+  const int nv = triangles ? 3 : 4, perQuad = triangles ? 2 : 1;     // (a quad is one cell or two)
+  const size_t quad = (size_t)perQuad * nv * sizeof(u64);
   const bool heads = nwords < 0xffffffffULL && !t.no_heads;
   EmitSizes s;
-  s.points = {(size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float), (size_t)(nextV + planeCorners) * 3 * sizeof(float)};
-  s.cells = {(size_t)(nQ ? nQ : 1) * quad, (size_t)nextQ * quad};
-  s.normals = normals && nV ? Want{(size_t)nV * 3 * sizeof(float), (size_t)nextV * 3 * sizeof(float)} : Want{0, 0};   // (a whole volume: no plane behind them)
-  // (cellPixelBytes: the size of a pixel, 0 with the setting off; a quad is one cell or two)
-  const size_t perQuad = (triangles ? 2 : 1) * cellPixelBytes;
-  s.cellPix = perQuad && nQ ? Want{(size_t)nQ * perQuad, (size_t)nextQ * perQuad} : Want{0, 0};
-  // (components: the point and cell figures of `points` and `cells`, the same covering sizes; a whole volume: no plane, no ghosts)
-  const u64 nC = nQ * (triangles ? 2 : 1), nextC = nextQ * (triangles ? 2 : 1);
-  const bool comp = components && nV;
-  s.compPoint = comp ? Want{(size_t)nV * sizeof(u32), (size_t)nextV * sizeof(u32)} : Want{0, 0};
-  s.compCell = comp ? Want{(size_t)(nC ? nC : 1) * sizeof(u32), (size_t)nextC * sizeof(u32)} : Want{0, 0};
-  s.compCount = comp ? Want{(size_t)nV * sizeof(u64), (size_t)nextV * sizeof(u64)} : Want{0, 0};
-  s.compScan = components ? Want{comp_scan_bytes(nV), comp_scan_bytes(nextV)} : Want{0, 0};   // (K's slot also for an empty mesh)
+  s.rows[ROW_POINTS] = {(size_t)(nV + planeCorners ? nV + planeCorners : 1) * 3 * sizeof(float), (size_t)(nextV + planeCorners) * 3 * sizeof(float)};
+  s.rows[ROW_CELLS] = {(size_t)(nQ ? nQ : 1) * quad, (size_t)nextQ * quad};
+  // the attributes' rows (a whole volume: no plane, no ghosts): the point and cell figures of `points` and `cells`, K <= points
+  const u64 n[N_PERS] = {nV, nQ * perQuad, nV}, next[N_PERS] = {nextV, nextQ * perQuad, nextV};
+  for (int r = ROW_CELLS + 1; r < N_ROWS; r++) {
+    const bool wanted = on[kRows[r].attr] && n[kAttrOf[kRows[r].attr]];
+    s.rows[r] = wanted ? Want{row_reserve_bytes(r, n, nv, pixel), (size_t)next[kRows[r].per] * kRows[r].elem(nv, pixel)} : Want{0, 0};
+  }
+  s.compScan = on[ATTR_COMPONENTS] ? Want{comp_scan_bytes(nV), comp_scan_bytes(nextV)} : Want{0, 0};   // (K's slot also for an empty mesh)
   s.headV = heads ? Want{(size_t)(nV / 64 + 2) * sizeof(u32), (size_t)(nextV / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.headQ = heads ? Want{(size_t)(totQ / 64 + 2) * sizeof(u32), (size_t)(nextQ / 64 + 2) * sizeof(u32)} : Want{0, 0};
   s.cmap = nV < 0xffffffffULL ? cmap_bytes(g, t) : 0;   // (more than 2^32 vertices: the cell kernel recomputes ids instead)
@@ -885,6 +918,17 @@ void *optional(DevBuf &b, size_t bytes, size_t cover = 0) {
   return nullptr;
 }
 
+// cuberille_keep_components let the mesh's rows change places with spare rows sized by the kept counts.  Once that mesh is gone,
+// the larger buffer of each pair is the one the extraction was sized for: back in its place, nothing is reserved again.  (The
+// normals' and the cell pixels' only while their setting is on: off, its setter released both partners.)  Touches no device.
+void rows_home(cuberille_ctx *c) {
+  for (int r = 0; r < N_ROWS; r++) {
+    const int a = kRows[r].attr;
+    if (a != ATTR_NONE && a != ATTR_COMPONENTS && !c->attr[a].on) continue;
+    if (c->rows[r].spare.cap > c->rows[r].row.cap) std::swap(c->rows[r].row, c->rows[r].spare);
+  }
+}
+
 // First half of a count: layout, parameters, workspace, zeroed state.  The caller then thresholds the slices
 // (all at once, or z-range by z-range as they arrive) and calls count_finish.
 // view: what resolve_view made of the context's settings for this image and route.
@@ -893,23 +937,14 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->counted = false;
   c->pointsEmitted = false;
   c->haveMesh = false;
-  c->haveNormals = false;
-  c->haveCellPixels = false;
-  c->haveComponents = false;
+  for (auto &a : c->attr) a.have = false;
   c->hostMeshValid = false;
   c->stepMode = 0;
   c->voxelHaloEvent = nullptr;
   c->aliasBelowBuffer = false;
   c->aliasMustResolve = false;
   c->aliasZ = -1;
-  // (cuberille_keep_components let the mesh's rows change places with spare rows sized by the kept counts: the mesh is gone now,
-  //  and the larger buffer of each pair is the one the extraction was sized for -- back in its place, nothing is reserved again)
-  for (auto pair : {std::make_pair(&c->points, &c->sparePoints), std::make_pair(&c->cells, &c->spareCells),
-                    std::make_pair(&c->normals, c->pointNormals ? &c->spareNormals : &c->normals),
-                    std::make_pair(&c->cellPix, c->cellPixels ? &c->spareCellPix : &c->cellPix),
-                    std::make_pair(&c->compPoint, &c->spareCompPoint), std::make_pair(&c->compCell, &c->spareCompCell),
-                    std::make_pair(&c->compCount, &c->spareCompCount)})
-    if (pair.second->cap > pair.first->cap) std::swap(*pair.first, *pair.second);
+  rows_home(c);                              // (the mesh is gone now)
   HIP_TRY(c, hipSetDevice(c->device));
 
   // ---- layout -----------------------------------------------------------------------------
@@ -930,12 +965,8 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
     if (slab->global_nz < 1 || slab->z_begin < 0 || slab->z_begin + g.nzb > slab->global_nz ||
         slab->own_z0 < slab->z_begin || slab->own_z1 > slab->z_begin + g.nzb || slab->own_z0 >= slab->own_z1)
       return fail(c, CUBERILLE_ERR_ARGUMENT, "slab ranges are inconsistent with the buffer");
-    if (c->pointNormals && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "point normals (cuberille_set_point_normals) belong to a whole volume: not offered on slabs");
-    if (c->cellPixels && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "cell pixels (cuberille_set_cell_pixels) belong to a whole volume: not offered on slabs");
-    if (c->components && (slab->global_nz != g.nzb || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + g.nzb))
-      return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) belong to a whole volume: not offered on slabs");
+    const char *why = "";                    // (the optional outputs against the slab alone: validate saw to the parameters)
+    if (const int rc = attrs_offered(c, nullptr, ROUTE_SLAB, slab, g.nzb, &why)) return fail(c, rc, why);
     // the owned range needs 2 slices below (ids of corners created one slice down depend on the
     // slice below that) and 1 above; with the projection on, as far as a walk can reach (both unless the
     // volume ends there)
@@ -1001,9 +1032,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   HIP_TRY(c, mark(c, PASS_BEGIN));
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
   c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
-  c->countNormals = c->pointNormals;
-  c->countCellPixels = c->cellPixels;
-  c->countComponents = c->components;
+  for (auto &a : c->attr) a.counting = a.on;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -1240,28 +1269,27 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   const u32 nVW = dyn ? coverVW : c->tot.nVertexWords;
   // room behind this rank's points for the positions of a plane of the rank below's vertices (quirk Q1 across slabs)
   const size_t planeCorners = (c->slabMode || c->g.extAlias) ? (size_t)(c->g.nx + 1) * (c->g.ny + 1) : 0;
-  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, c->countNormals,
-                                  c->countCellPixels ? pixel_size(c->pixel_type) : 0, c->countComponents);
+  bool counting[N_ATTRS];
+  for (int a = 0; a < N_ATTRS; a++) counting[a] = c->attr[a].counting;
+  const EmitSizes sz = emit_sizes(c->g, c->tune, c->prm.triangles, dyn, nV, totQ, nQ, planeCorners, c->nwords, counting,
+                                  pixel_size(c->pixel_type));
   // (cuberille_set_components: uint32 labels, like the corner map's entries)
-  if (c->countComponents && nV >= 0xffffffffULL)
+  if (c->attr[ATTR_COMPONENTS].counting && nV >= 0xffffffffULL)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "components (cuberille_set_components) are 32-bit labels: not offered with 2^32 points or more");
-  HIP_TRY(c, c->points.reserve_covering(sz.points.bytes, sz.points.cover));
-  HIP_TRY(c, c->cells.reserve_covering(sz.cells.bytes, sz.cells.cover));
-  if (sz.normals.bytes) HIP_TRY(c, c->normals.reserve_covering(sz.normals.bytes, sz.normals.cover));
-  if (sz.cellPix.bytes) HIP_TRY(c, c->cellPix.reserve_covering(sz.cellPix.bytes, sz.cellPix.cover));
-  if (sz.compPoint.bytes) {
-    HIP_TRY(c, c->compParent.reserve_covering(sz.compPoint.bytes, sz.compPoint.cover));
-    HIP_TRY(c, c->compPoint.reserve_covering(sz.compPoint.bytes, sz.compPoint.cover));
-    HIP_TRY(c, c->compCell.reserve_covering(sz.compCell.bytes, sz.compCell.cover));
-    HIP_TRY(c, c->compCount.reserve_covering(sz.compCount.bytes, sz.compCount.cover));
+  for (int r = 0; r < N_ROWS; r++) {
+    const Want &want = sz.rows[r];
+    if (!want.bytes) continue;
+    if (r == ROW_COMP_POINT)   // (the components' forest: scratch, ahead of the point labels it turns into and sized as they are)
+      HIP_TRY(c, c->compParent.reserve_covering(want.bytes, want.cover));
+    HIP_TRY(c, c->row(r).reserve_covering(want.bytes, want.cover));
   }
   if (sz.compScan.bytes) {
     HIP_TRY(c, c->compScan.reserve_covering(sz.compScan.bytes, sz.compScan.cover));
     if (!c->hostK) HIP_TRY(c, hipHostMalloc((void **)&c->hostK, sizeof(u64), hipHostMallocDefault));
   }
   Workspace &w = c->w;
-  w.points = (float *)c->points.p;
-  w.cells = (u64 *)c->cells.p;
+  w.points = (float *)c->row(ROW_POINTS).p;
+  w.cells = (u64 *)c->row(ROW_CELLS).p;
   // without the corner map the cell kernel recomputes ids, without the head tables the waves search their outputs' words
   w.cmap = (u32 *)optional(c->cmap, sz.cmap);
   w.headQ = (u32 *)optional(c->headQ, sz.headQ.bytes, sz.headQ.cover);
@@ -1349,7 +1377,8 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   }
   // cuberille_set_point_normals: the points are final -- behind the walk, or behind the vertex scatter with the projection off --
   // and one more pass reads each of them once (with stage timing on, part of ms_project)
-  if (sz.normals.bytes) HIP_TRY(c, launch_point_normals(c->pixel_type, w, c->g, c->geo, (float *)c->normals.p, nV, dyn ? 1 : 0, s));
+  if (sz.rows[ROW_NORMALS].bytes)
+    HIP_TRY(c, launch_point_normals(c->pixel_type, w, c->g, c->geo, (float *)c->row(ROW_NORMALS).p, nV, dyn ? 1 : 0, s));
   if (ahead) c->pointsStartedEarly = true;   // the caller turns to the other ranks now: the cells come as an interval of their own
   HIP_TRY(c, mark(c, PROJECT_END));
   c->pointsEmitted = true;
@@ -1433,12 +1462,27 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->histShortWalks = c->prm.project && c->tot.iters > 0 && c->tot.iters < 4 * c->tot.totV;
   c->stepMode = 0;
   c->haveMesh = true;
-  c->haveNormals = c->countNormals;
-  c->haveCellPixels = c->countCellPixels;
-  c->haveComponents = c->countComponents;
-  c->nComponents = c->countComponents && c->hostK ? *c->hostK : 0;
+  for (auto &a : c->attr) a.have = a.counting;
+  c->nComponents = c->attr[ATTR_COMPONENTS].counting && c->hostK ? *c->hostK : 0;
   c->counted = false;                        // the workspace now belongs to this mesh
   if (res) *res = r;
+  return CUBERILLE_OK;
+}
+
+// The tail of the cell phase, behind launch_emit_cells and ahead of mark(END) (with stage timing on, part of ms_emit_cells): one
+// more pass over the quads reads each one's voxel; the union-find over the cells, the numbering, the labels.  base: the point id
+// offset; nV, nQ: points and quads, or with dyn what the launches and the rows are sized for.
+int launch_cell_attrs(cuberille_ctx *c, u64 base, u64 nV, u64 nQ, bool dyn) {
+  if (c->attr[ATTR_CELL_PIXELS].counting)
+    HIP_TRY(c, launch_cell_pixels(c->pixel_type, c->w, c->g, c->prm.triangles, c->row(ROW_CELL_PIX).p, nQ, dyn ? 1 : 0, c->stream));
+  if (c->attr[ATTR_COMPONENTS].counting)
+    HIP_TRY(c, launch_components(c->w, comp_rows(c), c->prm.triangles, base, nV, nQ, dyn ? 1 : 0, c->stream));
+  return CUBERILLE_OK;
+}
+// ... and behind mark(END): K rides with the totals, ahead of the one wait
+int component_count_to_host(cuberille_ctx *c) {
+  if (c->attr[ATTR_COMPONENTS].counting && c->hostK && c->compScan.p)
+    HIP_TRY(c, hipMemcpyAsync(c->hostK, c->compScan.p, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   return CUBERILLE_OK;
 }
 
@@ -1545,15 +1589,9 @@ int cuberille_emit(cuberille_ctx *c, uint64_t point_id_offset, cuberille_result 
     HIP_TRY(c, hipMemcpyAsync(w.points + 3 * nV, c->extPts, planeCorners * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, launch_emit_cells(w, c->g, c->prm.triangles, c->prm.q1, point_id_offset, nQ, needPlane ? c->extIds : nullptr,
                                nullptr, 0, 0, 0, s));
-  // cuberille_set_cell_pixels: one more pass over the quads reads each one's voxel (with stage timing on, part of ms_emit_cells)
-  if (c->countCellPixels)
-    HIP_TRY(c, launch_cell_pixels(c->pixel_type, w, c->g, c->prm.triangles, c->cellPix.p, nQ, 0, s));
-  // cuberille_set_components: the cells are written -- the union-find over them, the numbering, the labels (likewise part of
-  // ms_emit_cells); K rides behind the totals, ahead of the one wait
-  if (c->countComponents)
-    HIP_TRY(c, launch_components(w, comp_rows(c), c->prm.triangles, point_id_offset, nV, nQ, 0, s));
+  if ((rc = launch_cell_attrs(c, point_id_offset, nV, nQ, false)) != CUBERILLE_OK) return rc;
   HIP_TRY(c, mark(c, END));
-  if (c->countComponents && c->hostK && c->compScan.p) HIP_TRY(c, hipMemcpyAsync(c->hostK, c->compScan.p, sizeof(u64), hipMemcpyDeviceToHost, s));
+  if ((rc = component_count_to_host(c)) != CUBERILLE_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->hostTotals, w.totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return finish_result(c, res);
@@ -1700,22 +1738,13 @@ int step_end_impl(cuberille_ctx *c, const void *dev_rows, int n_ranks, int rank,
     const u64 nQ = blind ? c->histQ + c->histQ / 4 + 4096 : c->tot.totQ - c->tot.Q0;
     HIP_TRY(c, launch_emit_cells(c->w, c->g, c->prm.triangles, c->prm.q1, base, nQ, nullptr, (const Totals *)dev_rows, n_ranks, rank,
                                  blind ? 1 : 0, s));
-    // (cuberille_set_cell_pixels: the one-call routes alone come here with it, the context their only rank -- the step calls refuse)
-    if (c->countCellPixels)
-      HIP_TRY(c, launch_cell_pixels(c->pixel_type, c->w, c->g, c->prm.triangles, c->cellPix.p, nQ, blind ? 1 : 0, s));
-    // (cuberille_set_components: likewise; blind, the rows are sized as the points and cells were, by the gate's cover)
-    if (c->countComponents) {
-      const u64 nV = blind ? c->histV + c->histV / 4 + 4096 : c->tot.totV;
-      HIP_TRY(c, launch_components(c->w, comp_rows(c), c->prm.triangles, base, nV, nQ, blind ? 1 : 0, s));
-    }
+    // (the one-call routes alone come here with an attribute, the context their only rank; blind, its rows are sized by the gate's cover)
+    const u64 nV = blind ? c->histV + c->histV / 4 + 4096 : c->tot.totV;
+    if (const int rc = launch_cell_attrs(c, base, nV, nQ, blind)) return rc;
   }
   HIP_TRY(c, mark(c, END));
-  // (K rides with the totals in the step's one wait; a flagged step leaves it unread)
-  if (c->countComponents && c->hostK && c->compScan.p) HIP_TRY(c, hipMemcpyAsync(c->hostK, c->compScan.p, sizeof(u64), hipMemcpyDeviceToHost, s));
-  {
-    const int rc = totals_to_host(c);
-    if (rc) return rc;
-  }
+  if (const int rc = component_count_to_host(c)) return rc;   // (a flagged step leaves K unread)
+  if (const int rc = totals_to_host(c)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->hostRows, dev_rows, (size_t)n_ranks * sizeof(Totals), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));                  // the one wait of the step
   u32 flags = 0;
@@ -2075,9 +2104,7 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     }
     c->haveHistory = false;                  // (sizes of a toy volume: the first real extraction reads its own counts)
     c->haveMesh = false;
-    c->haveNormals = false;
-    c->haveCellPixels = false;
-    c->haveComponents = false;
+    for (auto &a : c->attr) a.have = false;
     c->counted = false;
     c->warm = true;
   }
@@ -2198,8 +2225,8 @@ int cuberille_debug_set_option(cuberille_ctx *c, const char *name, int64_t value
 
 int cuberille_mesh_device(const cuberille_ctx *c, const float **d_points, const uint64_t **d_cells) {
   if (!c || !c->haveMesh) return CUBERILLE_ERR_STATE;
-  if (d_points) *d_points = (const float *)c->points.p + 3 * c->tot.V0;
-  if (d_cells) *d_cells = (const uint64_t *)c->cells.p;
+  if (d_points) *d_points = (const float *)c->rows[ROW_POINTS].row.p + 3 * c->tot.V0;
+  if (d_cells) *d_cells = (const uint64_t *)c->rows[ROW_CELLS].row.p;
   return CUBERILLE_OK;
 }
 
@@ -2259,11 +2286,11 @@ int cuberille_mesh_download(cuberille_ctx *c, float *points, uint64_t *cells) {
   HIP_TRY(c, hipSetDevice(c->device));
   const cuberille_result &r = c->res;
   if (points && r.n_points) {
-    const int rc = download_pipelined(c, points, (const float *)c->points.p + 3 * c->tot.V0, r.n_points * 3 * sizeof(float));
+    const int rc = download_pipelined(c, points, (const float *)c->row(ROW_POINTS).p + 3 * c->tot.V0, mesh_row_bytes(c, ROW_POINTS));
     if (rc) return rc;
   }
   if (cells && r.n_cells) {
-    const int rc = download_pipelined(c, cells, c->cells.p, r.n_cells * r.verts_per_cell * sizeof(uint64_t));
+    const int rc = download_pipelined(c, cells, c->row(ROW_CELLS).p, mesh_row_bytes(c, ROW_CELLS));
     if (rc) return rc;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2273,9 +2300,8 @@ int cuberille_mesh_download(cuberille_ctx *c, float *points, uint64_t *cells) {
 int cuberille_mesh_host(cuberille_ctx *c, float **points, uint64_t **cells) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
-  const cuberille_result &r = c->res;
   if (!c->hostMeshValid) {
-    const size_t pb = (size_t)r.n_points * 3 * sizeof(float), cb = (size_t)r.n_cells * r.verts_per_cell * sizeof(uint64_t);
+    const size_t pb = mesh_row_bytes(c, ROW_POINTS), cb = mesh_row_bytes(c, ROW_CELLS);
     if (!c->hostPoints.reserve(pb ? pb : 1) || !c->hostCells.reserve(cb ? cb : 1))
       return fail(c, CUBERILLE_ERR_HIP, "cuberille_mesh_host: out of host memory");
     const int rc = cuberille_mesh_download(c, (float *)c->hostPoints.p, (uint64_t *)c->hostCells.p);
@@ -2287,140 +2313,103 @@ int cuberille_mesh_host(cuberille_ctx *c, float **points, uint64_t **cells) {
   return CUBERILLE_OK;
 }
 
-int cuberille_set_point_normals(cuberille_ctx *c, int on) {
+// What the three setters share.  Off: the context holds what one that never heard of the setting holds -- the last mesh stays, the
+// attribute's rows go with their partners (behind a keep, whichever of the two the extraction was sized for) and its scratch.
+static int set_attr(cuberille_ctx *c, int a, int on, bool *released = nullptr) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
   if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
-  c->pointNormals = on != 0;
-  if (!on && (c->normals.p || c->spareNormals.p)) {
-    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its normals go -- and behind a
-    // cuberille_keep_components the row's partner, whichever of the two the extraction was sized for)
-    (void)hipSetDevice(c->device);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
-    c->normals.release();
-    c->spareNormals.release();
-    c->haveNormals = false;
-    c->countNormals = false;
-  }
+  c->attr[a].on = on != 0;
+  if (on) return CUBERILLE_OK;
+  std::vector<DevBuf *> held;
+  if (a == ATTR_COMPONENTS) held.assign(c->compScratch, c->compScratch + 4);
+  for (int r = 0; r < N_ROWS; r++)
+    if (kRows[r].attr == a) { held.push_back(&c->rows[r].row); held.push_back(&c->rows[r].spare); }
+  if (std::none_of(held.begin(), held.end(), [](const DevBuf *b) { return b->p != nullptr; })) return CUBERILLE_OK;
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
+  for (DevBuf *b : held) b->release();
+  c->attr[a].have = c->attr[a].counting = false;
+  if (released) *released = true;
   return CUBERILLE_OK;
 }
 
-static int normals_preconditions(cuberille_ctx *c) {
+static int attr_preconditions(cuberille_ctx *c, int a) {
   if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
-  if (!c->haveNormals)
-    return fail(c, CUBERILLE_ERR_STATE, "no point normals: the last extraction ran with the setting off (cuberille_set_point_normals)");
+  if (!c->attr[a].have) return fail(c, CUBERILLE_ERR_STATE, attr_missing(a));
   return CUBERILLE_OK;
 }
+
+int cuberille_set_point_normals(cuberille_ctx *c, int on) { return set_attr(c, ATTR_NORMALS, on); }
 
 int cuberille_normals_device(cuberille_ctx *c, const float **d_normals) {
   if (!c || !d_normals) return CUBERILLE_ERR_ARGUMENT;
   *d_normals = nullptr;
-  if (const int rc = normals_preconditions(c)) return rc;
-  *d_normals = (const float *)c->normals.p;        // (a whole volume: no ghost vertices ahead of the owned ones; null with no point)
+  if (const int rc = attr_preconditions(c, ATTR_NORMALS)) return rc;
+  *d_normals = (const float *)c->row(ROW_NORMALS).p;   // (a whole volume: no ghost vertices ahead of the owned ones; null with no point)
   return CUBERILLE_OK;
 }
 
 int cuberille_normals_download(cuberille_ctx *c, float *normals) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
-  if (const int rc = normals_preconditions(c)) return rc;
+  if (const int rc = attr_preconditions(c, ATTR_NORMALS)) return rc;
   if (!c->res.n_points) return CUBERILLE_OK;
   if (!normals) return fail(c, CUBERILLE_ERR_ARGUMENT, "null output pointer");
   HIP_TRY(c, hipSetDevice(c->device));
-  return download_pipelined(c, normals, c->normals.p, (size_t)c->res.n_points * 3 * sizeof(float));
+  return download_pipelined(c, normals, c->row(ROW_NORMALS).p, mesh_row_bytes(c, ROW_NORMALS));
 }
 
-int cuberille_set_cell_pixels(cuberille_ctx *c, int on) {
-  if (!c) return CUBERILLE_ERR_ARGUMENT;
-  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
-  c->cellPixels = on != 0;
-  if (!on && (c->cellPix.p || c->spareCellPix.p)) {
-    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its cell pixels go -- and
-    // behind a cuberille_keep_components the row's partner, whichever of the two the extraction was sized for)
-    (void)hipSetDevice(c->device);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
-    c->cellPix.release();
-    c->spareCellPix.release();
-    c->haveCellPixels = false;
-    c->countCellPixels = false;
-  }
-  return CUBERILLE_OK;
-}
-
-static int cell_pixels_preconditions(cuberille_ctx *c) {
-  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
-  if (!c->haveCellPixels)
-    return fail(c, CUBERILLE_ERR_STATE, "no cell pixels: the last extraction ran with the setting off (cuberille_set_cell_pixels)");
-  return CUBERILLE_OK;
-}
+int cuberille_set_cell_pixels(cuberille_ctx *c, int on) { return set_attr(c, ATTR_CELL_PIXELS, on); }
 
 int cuberille_cell_pixels_device(cuberille_ctx *c, const void **d_pixels, int *pixel_type) {
   if (!c || !d_pixels) return CUBERILLE_ERR_ARGUMENT;
   *d_pixels = nullptr;
-  if (const int rc = cell_pixels_preconditions(c)) return rc;
-  *d_pixels = c->res.n_cells ? c->cellPix.p : nullptr;   // (a row sized by an earlier mesh is no value of an empty one)
+  if (const int rc = attr_preconditions(c, ATTR_CELL_PIXELS)) return rc;
+  *d_pixels = c->res.n_cells ? c->row(ROW_CELL_PIX).p : nullptr;   // (a row sized by an earlier mesh is no value of an empty one)
   if (pixel_type) *pixel_type = c->pixel_type;
   return CUBERILLE_OK;
 }
 
 int cuberille_cell_pixels_download(cuberille_ctx *c, void *out, size_t capacity_bytes) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
-  if (const int rc = cell_pixels_preconditions(c)) return rc;
-  const size_t bytes = (size_t)c->res.n_cells * pixel_size(c->pixel_type);
+  if (const int rc = attr_preconditions(c, ATTR_CELL_PIXELS)) return rc;
+  const size_t bytes = mesh_row_bytes(c, ROW_CELL_PIX);
   if (capacity_bytes < bytes)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "the cell pixels take " + std::to_string(bytes) + " bytes, the buffer holds " + std::to_string(capacity_bytes));
   if (!bytes) return CUBERILLE_OK;
   if (!out) return fail(c, CUBERILLE_ERR_ARGUMENT, "null output pointer");
   HIP_TRY(c, hipSetDevice(c->device));
-  return download_pipelined(c, out, c->cellPix.p, bytes);
+  return download_pipelined(c, out, c->row(ROW_CELL_PIX).p, bytes);
 }
 
 int cuberille_set_components(cuberille_ctx *c, int on) {
-  if (!c) return CUBERILLE_ERR_ARGUMENT;
-  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
-  c->components = on != 0;
-  if (!on && (c->compScan.p || c->compParent.p || c->keepSel.p)) {
-    // off: the context holds what one that never heard of the setting holds (the last mesh stays, its components go)
-    (void)hipSetDevice(c->device);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the pass may still be writing them)
-    for (DevBuf *b : {&c->compParent, &c->compPoint, &c->compCell, &c->compCount, &c->compScan}) b->release();
-    // (... and what cuberille_keep_components reserved: its scratch and the spare rows.  Where a kept mesh lives in a row sized
-    //  by the kept counts, it moves back into the buffer the extraction was sized for -- one copy of the kept size -- so that the
-    //  context holds the buffers it held before the setting was on, and the next extraction reserves nothing again)
-    if (c->haveMesh) {
-      const size_t pb = (size_t)c->res.n_points * 3 * sizeof(float), cb = (size_t)c->res.n_cells * c->res.verts_per_cell * sizeof(u64);
-      const size_t xb = c->haveCellPixels ? (size_t)c->res.n_cells * pixel_size(c->pixel_type) : 0;
-      struct { DevBuf *row, *spare; size_t bytes; } rows[] = {{&c->points, &c->sparePoints, pb}, {&c->cells, &c->spareCells, cb},
-                                                              {&c->normals, &c->spareNormals, c->haveNormals ? pb : 0},
-                                                              {&c->cellPix, &c->spareCellPix, xb}};
-      for (auto &r : rows) {
-        if (r.spare->cap <= r.row->cap || !r.row->p) continue;
-        if (r.bytes) HIP_TRY(c, hipMemcpyAsync(r.spare->p, r.row->p, r.bytes, hipMemcpyDeviceToDevice, c->stream));
-        std::swap(*r.row, *r.spare);
-      }
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->w.points = (float *)c->points.p;
-      c->w.cells = (u64 *)c->cells.p;
+  bool released = false;
+  if (const int rc = set_attr(c, ATTR_COMPONENTS, on, &released)) return rc;
+  if (!released) return CUBERILLE_OK;
+  c->nComponents = 0;
+  // (... and the other rows' spares, which cuberille_keep_components reserved.  Where a kept mesh lives in a row sized by the kept
+  //  counts, it moves back into the buffer the extraction was sized for -- one copy of the kept size -- so that the context holds
+  //  the buffers it held before the setting was on, and the next extraction reserves nothing again)
+  if (c->haveMesh) {
+    for (int r = 0; r < N_ROWS; r++) {
+      MeshRow &m = c->rows[r];
+      const int a = kRows[r].attr;
+      if (a == ATTR_COMPONENTS || m.spare.cap <= m.row.cap || !m.row.p) continue;
+      const size_t bytes = a == ATTR_NONE || c->attr[a].have ? mesh_row_bytes(c, r) : 0;
+      if (bytes) HIP_TRY(c, hipMemcpyAsync(m.spare.p, m.row.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+      std::swap(m.row, m.spare);
     }
-    for (DevBuf *b : {&c->keepSel, &c->keepScan, &c->sparePoints, &c->spareCells, &c->spareNormals, &c->spareCellPix,
-                      &c->spareCompPoint, &c->spareCompCell, &c->spareCompCount})
-      b->release();
-    c->haveComponents = false;
-    c->countComponents = false;
-    c->nComponents = 0;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->w.points = (float *)c->row(ROW_POINTS).p;
+    c->w.cells = (u64 *)c->row(ROW_CELLS).p;
   }
-  return CUBERILLE_OK;
-}
-
-static int components_preconditions(cuberille_ctx *c) {
-  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
-  if (!c->haveComponents)
-    return fail(c, CUBERILLE_ERR_STATE, "no components: the last extraction ran with the setting off (cuberille_set_components)");
+  for (MeshRow &m : c->rows) m.spare.release();
   return CUBERILLE_OK;
 }
 
 int cuberille_components_info(cuberille_ctx *c, uint64_t *n_components) {
   if (!c || !n_components) return CUBERILLE_ERR_ARGUMENT;
   *n_components = 0;
-  if (const int rc = components_preconditions(c)) return rc;
+  if (const int rc = attr_preconditions(c, ATTR_COMPONENTS)) return rc;
   *n_components = c->nComponents;
   return CUBERILLE_OK;
 }
@@ -2431,28 +2420,28 @@ int cuberille_components_device(cuberille_ctx *c, const uint32_t **d_point_compo
   if (d_point_component) *d_point_component = nullptr;
   if (d_cell_component) *d_cell_component = nullptr;
   if (d_component_cells) *d_component_cells = nullptr;
-  if (const int rc = components_preconditions(c)) return rc;
+  if (const int rc = attr_preconditions(c, ATTR_COMPONENTS)) return rc;
   // (rows sized by an earlier mesh are no values of an empty one)
-  if (d_point_component && c->res.n_points) *d_point_component = (const uint32_t *)c->compPoint.p;
-  if (d_cell_component && c->res.n_cells) *d_cell_component = (const uint32_t *)c->compCell.p;
-  if (d_component_cells && c->nComponents) *d_component_cells = (const uint64_t *)c->compCount.p;
+  if (d_point_component && c->res.n_points) *d_point_component = (const uint32_t *)c->row(ROW_COMP_POINT).p;
+  if (d_cell_component && c->res.n_cells) *d_cell_component = (const uint32_t *)c->row(ROW_COMP_CELL).p;
+  if (d_component_cells && c->nComponents) *d_component_cells = (const uint64_t *)c->row(ROW_COMP_COUNT).p;
   return CUBERILLE_OK;
 }
 
 int cuberille_components_download(cuberille_ctx *c, uint32_t *point_component, uint32_t *cell_component, uint64_t *component_cells,
                                   size_t capacity_components) {
   if (!c) return CUBERILLE_ERR_ARGUMENT;
-  if (const int rc = components_preconditions(c)) return rc;
+  if (const int rc = attr_preconditions(c, ATTR_COMPONENTS)) return rc;
   if (component_cells && capacity_components < c->nComponents)
     return fail(c, CUBERILLE_ERR_ARGUMENT, "the mesh has " + std::to_string(c->nComponents) + " components, the buffer holds " +
                                            std::to_string(capacity_components));
   HIP_TRY(c, hipSetDevice(c->device));
   if (point_component && c->res.n_points)
-    if (const int rc = download_pipelined(c, point_component, c->compPoint.p, (size_t)c->res.n_points * sizeof(uint32_t))) return rc;
+    if (const int rc = download_pipelined(c, point_component, c->row(ROW_COMP_POINT).p, mesh_row_bytes(c, ROW_COMP_POINT))) return rc;
   if (cell_component && c->res.n_cells)
-    if (const int rc = download_pipelined(c, cell_component, c->compCell.p, (size_t)c->res.n_cells * sizeof(uint32_t))) return rc;
+    if (const int rc = download_pipelined(c, cell_component, c->row(ROW_COMP_CELL).p, mesh_row_bytes(c, ROW_COMP_CELL))) return rc;
   if (component_cells && c->nComponents)
-    if (const int rc = download_pipelined(c, component_cells, c->compCount.p, (size_t)c->nComponents * sizeof(uint64_t))) return rc;
+    if (const int rc = download_pipelined(c, component_cells, c->row(ROW_COMP_COUNT).p, mesh_row_bytes(c, ROW_COMP_COUNT))) return rc;
   return CUBERILLE_OK;
 }
 
@@ -2467,8 +2456,7 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
     return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: no mesh, so no components: call cuberille_extract_* or cuberille_emit first");
   if (c->slabMode)
     return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: a slab's mesh has no components (a component does not stop at a slab's face)");
-  if (!c->haveComponents)
-    return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: no components: the last extraction ran with the setting off (cuberille_set_components)");
+  if (!c->attr[ATTR_COMPONENTS].have) return fail(c, CUBERILLE_ERR_STATE, "cuberille_keep_components: " + attr_missing(ATTR_COMPONENTS));
   const u64 K = c->nComponents, nP = c->res.n_points, nC = c->res.n_cells;
   if (rule == CUBERILLE_KEEP_MASK) {
     if (mask_len != K)
@@ -2511,29 +2499,26 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
   HIP_TRY(c, hipStreamSynchronize(s));                       // the one read: K', n_points', n_cells'
   const u64 K2 = c->hostKeep[0], nP2 = c->hostKeep[1], nC2 = c->hostKeep[2];
   if (K2 > K || nP2 > nP || nC2 > nC) return fail(c, CUBERILLE_ERR_STATE, "internal: cuberille_keep_components kept more than there is");
+  // (the rows of the mesh that are kept: its own, and those of the attributes it came with)
+  bool kept[N_ROWS];
+  for (int i = 0; i < N_ROWS; i++) kept[i] = kRows[i].attr == ATTR_NONE || c->attr[kRows[i].attr].have;
   if (K2 != K && K2 != 0) {
     // decided: the spare rows by the kept counts, every one of them before the first scatter (a failure leaves the mesh as it is)
-    const size_t nv = (size_t)c->res.verts_per_cell, pix = c->haveCellPixels ? pixel_size(c->pixel_type) : 0;
-    HIP_TRY(c, c->sparePoints.reserve((size_t)nP2 * 3 * sizeof(float)));
-    HIP_TRY(c, c->spareCells.reserve((size_t)(nC2 ? nC2 : 1) * nv * sizeof(u64)));
-    if (c->haveNormals) HIP_TRY(c, c->spareNormals.reserve((size_t)nP2 * 3 * sizeof(float)));
-    if (pix) HIP_TRY(c, c->spareCellPix.reserve((size_t)(nC2 ? nC2 : 1) * pix));
-    HIP_TRY(c, c->spareCompPoint.reserve((size_t)nP2 * sizeof(u32)));
-    HIP_TRY(c, c->spareCompCell.reserve((size_t)(nC2 ? nC2 : 1) * sizeof(u32)));
-    HIP_TRY(c, c->spareCompCount.reserve((size_t)K2 * sizeof(u64)));
-    KeepOut o{};
-    o.points = (float *)c->sparePoints.p;
-    o.normals = c->haveNormals ? (float *)c->spareNormals.p : nullptr;
-    o.cells = (u64 *)c->spareCells.p;
-    o.cellPix = pix ? c->spareCellPix.p : nullptr;
-    o.pointComp = (u32 *)c->spareCompPoint.p;
-    o.cellComp = (u32 *)c->spareCompCell.p;
-    o.compCells = (u64 *)c->spareCompCount.p;
+    const size_t pix = pixel_size(c->pixel_type);
+    const u64 n2[N_PERS] = {nP2, nC2, K2};
+    void *in[N_ROWS] = {}, *out[N_ROWS] = {};                // (null where the mesh has no such row)
+    for (int i = 0; i < N_ROWS; i++) {
+      if (!kept[i]) continue;
+      HIP_TRY(c, c->rows[i].spare.reserve(row_reserve_bytes(i, n2, c->res.verts_per_cell, pix)));
+      in[i] = c->rows[i].row.p; out[i] = c->rows[i].spare.p;
+    }
+    const KeepOut o = {(float *)out[ROW_POINTS], (float *)out[ROW_NORMALS], (u64 *)out[ROW_CELLS], out[ROW_CELL_PIX],
+                       (u32 *)out[ROW_COMP_POINT], (u32 *)out[ROW_COMP_CELL], (u64 *)out[ROW_COMP_COUNT]};
     Workspace w = c->w;
-    w.points = (float *)c->points.p;
-    w.cells = (u64 *)c->cells.p;
-    HIP_TRY(c, launch_keep_scatter(w, r, k, o, c->haveNormals ? (const float *)c->normals.p : nullptr, pix ? c->cellPix.p : nullptr,
-                                   (int)pix, c->prm.triangles, c->pointOffset, K, nP, nC, s));
+    w.points = (float *)in[ROW_POINTS];
+    w.cells = (u64 *)in[ROW_CELLS];
+    HIP_TRY(c, launch_keep_scatter(w, r, k, o, (const float *)in[ROW_NORMALS], in[ROW_CELL_PIX], kept[ROW_CELL_PIX] ? (int)pix : 0,
+                                   c->prm.triangles, c->pointOffset, K, nP, nC, s));
   }
   HIP_TRY(c, hipEventRecord(c->keepEv[1], s));
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -2541,15 +2526,10 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
   if (K2 != K) {
     if (K2) {
       // the kept mesh is complete in the spare rows: the buffers change places (the earlier ones are the next call's spare rows)
-      std::swap(c->points, c->sparePoints);
-      std::swap(c->cells, c->spareCells);
-      if (c->haveNormals) std::swap(c->normals, c->spareNormals);
-      if (c->haveCellPixels) std::swap(c->cellPix, c->spareCellPix);
-      std::swap(c->compPoint, c->spareCompPoint);
-      std::swap(c->compCell, c->spareCompCell);
-      std::swap(c->compCount, c->spareCompCount);
-      c->w.points = (float *)c->points.p;
-      c->w.cells = (u64 *)c->cells.p;
+      for (int i = 0; i < N_ROWS; i++)
+        if (kept[i]) std::swap(c->rows[i].row, c->rows[i].spare);
+      c->w.points = (float *)c->row(ROW_POINTS).p;
+      c->w.cells = (u64 *)c->row(ROW_CELLS).p;
     }
     // (the walk counters, the ms_* fields, the count's tables and the sizes of the next blind launch stay the extraction's)
     c->res.n_points = nP2;
@@ -2694,9 +2674,10 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
   const int rc = cuberille_mesh_host(c, &pts, &cells);
   if (rc != CUBERILLE_OK) return rc;
   int wr = cuberille_write_vtk_buffers(path, pts, r.n_points, cells, r.n_cells, r.verts_per_cell, n_threads);
-  if (wr == CUBERILLE_OK && c->haveNormals) {
+  const bool withNormals = c->attr[ATTR_NORMALS].have, withPixels = c->attr[ATTR_CELL_PIXELS].have, withComponents = c->attr[ATTR_COMPONENTS].have;
+  if (wr == CUBERILLE_OK && withNormals) {
     // a context that holds normals: POINT_DATA n / NORMALS normals float behind the polygons (setting off: the file as it always was)
-    std::vector<float> nrm((size_t)r.n_points * 3);
+    std::vector<float> nrm(mesh_row_bytes(c, ROW_NORMALS) / sizeof(float));
     const int dl = cuberille_normals_download(c, nrm.data());
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_normals(path, nrm.data(), r.n_points, n_threads);
@@ -2704,22 +2685,22 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
   // a context that holds components: SCALARS component unsigned_int 1 in POINT_DATA (behind the normals) and in CELL_DATA (behind
   // the cell pixels), either block opened here where nothing else has (setting off: the file as it was)
   std::vector<uint32_t> pointComp, cellComp;
-  if (wr == CUBERILLE_OK && c->haveComponents) {
-    pointComp.resize((size_t)r.n_points);
-    cellComp.resize((size_t)r.n_cells);
+  if (wr == CUBERILLE_OK && withComponents) {
+    pointComp.resize(mesh_row_bytes(c, ROW_COMP_POINT) / sizeof(uint32_t));
+    cellComp.resize(mesh_row_bytes(c, ROW_COMP_CELL) / sizeof(uint32_t));
     const int dl = cuberille_components_download(c, pointComp.data(), cellComp.data(), nullptr, 0);
     if (dl != CUBERILLE_OK) return dl;
-    wr = cuberille::append_vtk_components(path, c->haveNormals ? nullptr : "POINT_DATA", pointComp.data(), r.n_points);
+    wr = cuberille::append_vtk_components(path, withNormals ? nullptr : "POINT_DATA", pointComp.data(), r.n_points);
   }
-  if (wr == CUBERILLE_OK && c->haveCellPixels) {
+  if (wr == CUBERILLE_OK && withPixels) {
     // a context that holds cell pixels: CELL_DATA n / SCALARS pixel <type> 1 behind everything else (setting off: the file as it was)
-    std::vector<char> pix((size_t)r.n_cells * pixel_size(c->pixel_type));
+    std::vector<char> pix(mesh_row_bytes(c, ROW_CELL_PIX));
     const int dl = cuberille_cell_pixels_download(c, pix.data(), pix.size());
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_cell_pixels(path, pix.data(), c->pixel_type, r.n_cells);
   }
-  if (wr == CUBERILLE_OK && c->haveComponents)
-    wr = cuberille::append_vtk_components(path, c->haveCellPixels ? nullptr : "CELL_DATA", cellComp.data(), r.n_cells);
+  if (wr == CUBERILLE_OK && withComponents)
+    wr = cuberille::append_vtk_components(path, withPixels ? nullptr : "CELL_DATA", cellComp.data(), r.n_cells);
   if (wr != CUBERILLE_OK) return fail(c, wr, std::string("cannot write ") + path);
   return CUBERILLE_OK;
 }
@@ -2955,15 +2936,7 @@ int cuberille_group_extract_host(cuberille_group *g, const cuberille_image_desc 
     if (c->holdGradient)
       return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " holds a gradient (cuberille_hold_gradient): "
                                               "it belongs to a whole volume, not offered in a group");
-    if (c->pointNormals)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has point normals set (cuberille_set_point_normals): "
-                                              "they belong to one context's whole volume, not offered in a group");
-    if (c->cellPixels)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has cell pixels set (cuberille_set_cell_pixels): "
-                                              "they belong to one context's whole volume, not offered in a group");
-    if (c->components)
-      return gfail(g, CUBERILLE_ERR_ARGUMENT, "member " + std::to_string(i) + " has components set (cuberille_set_components): "
-                                              "they belong to one context's whole volume, not offered in a group");
+    if (const int arc = attrs_offered(c, prm, ROUTE_GROUP, nullptr, 0, &why)) return gfail(g, arc, "member " + std::to_string(i) + " " + why);
   }
   {
     const int rc = validate(g->ctx[0], img, host_voxels, prm);
