@@ -169,7 +169,7 @@ struct Workspace {     // device pointers valid for one count/emit pair
 struct Tuning {
   int no_cmap = 0, no_heads = 0, no_vqueue = 0, no_stream_classify = 0;   // drop a scratch table / the flat-stream path
   int classify_variant = 0;   // 0: staged spans with write-through stores where the volume is large, 1: always the plain sweep,
-                              // 2: the padded sweep (cuberille_set_border) through its staged spans whatever the size (tests)
+                              // 2: rows of any source (ragged plain, border, region) through k_classify_span_rows whatever the size (tests)
   int classify_grid = 0;      // workgroups of the sweep (0 = default)
   int classify_keep_tail = 0; // 1: a partly filled last round of spans stays with the span kernel (A/B of the balancing)
   int proj_chunk64_below = 0; // vertices under which the walk deals batches of 64 (0: the default, 8 M)

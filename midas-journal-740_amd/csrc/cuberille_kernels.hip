@@ -72,6 +72,14 @@ struct Vec16 {
   static constexpr int N = 16 / sizeof(T);
   union { uint4 raw; T v[N]; };
 };
+// 16 bytes streamed once (kept out of the way of the bit volume in L2 / Infinity Cache): four nontemporal dword loads, which
+// the compiler merges into one
+template <class T>
+__device__ __forceinline__ void load_nt16(Vec16<T> &r, const T *p) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(p);
+  r.raw.x = __builtin_nontemporal_load(&src->x); r.raw.y = __builtin_nontemporal_load(&src->y);
+  r.raw.z = __builtin_nontemporal_load(&src->z); r.raw.w = __builtin_nontemporal_load(&src->w);
+}
 
 // 3-input boolean function on the gfx950 v_bitop3_b32 (truth table TT: bit (a<<2 | b<<1 | c))
 template <int TT>
@@ -199,13 +207,9 @@ __global__ __launch_bounds__(256) void k_classify_flat(const T *__restrict__ vox
 #pragma unroll
     for (int u = 0; u < U; u++) {
       if (c + u < nchunks) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(vox + ((c + u) * 64 + lane) * VPL);
-        if (NT) {   // streamed once: keep it out of the way of the bit volume in L2 / Infinity Cache
-          r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
-          r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
-        } else {
-          r[u].raw = *src;
-        }
+        const T *src = vox + ((c + u) * 64 + lane) * VPL;
+        if (NT) load_nt16(r[u], src);
+        else r[u].raw = *reinterpret_cast<const uint4 *>(src);
       }
     }
 #pragma unroll
@@ -279,11 +283,7 @@ __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox
     const u64 c0 = sp * (u64)(4 * TRIPS * U);            // first 1 KiB chunk of the span
     auto load = [&](Vec16<T> (&r)[U], int tl) {
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(vox + ((c0 + (u64)tl * U + u) * 64 + lane) * VPL);
-        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
-        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
-      }
+      for (int u = 0; u < U; u++) load_nt16(r[u], vox + ((c0 + (u64)tl * U + u) * 64 + lane) * VPL);
     };
     auto pack = [&](const Vec16<T> (&r)[U], int tl) {
 #pragma unroll
@@ -314,114 +314,6 @@ __global__ __launch_bounds__(256) void k_classify_span(const T *__restrict__ vox
         if (v.x | v.y) sliceOcc[w0 + i] = 1u;
         if (v.z | v.w) sliceOcc[w0 + i + 1] = 1u;
       }
-    }
-    __syncthreads();
-  }
-}
-
-// The same sweep for rows that are NOT whole words (nx % 64 != 0 -- most real volumes -- or a pointer that is not 16-byte
-// aligned): a workgroup still owns SPAN_WORDS consecutive OUTPUT words, i.e. a range of (row, word) pairs.  Rows follow
-// each other in memory, so the voxels behind those words are one contiguous range too: it is thresholded exactly as above
-// -- a flat stream of 16-byte vectors from the 16-byte boundary at or below its first voxel, 4 KiB trips per wave, DPP OR
-// into 64-voxel words of the STREAM -- into the LDS stage; then every thread cuts two row words out of the staged stream
-// (two LDS words, funnel-shifted, the row's last word masked to the voxels it has) and the span leaves as the same 16-byte
-// write-through stores, occupancy folded in.  No flat scratch stream in memory, no second trip of the bits through L2, no
-// repack and occupancy launches (round-4 review: 1000^3 f32 swept at 5.15 TB/s through those, against 6.7 for whole-word rows).
-template <class T, bool BAND = false>
-__global__ __launch_bounds__(256) void k_classify_span_rows(const T *__restrict__ vox, u64 *__restrict__ bits, u64 nspans,
-                                                            u64 nwordsAll, int nx, int W, u32 ny, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI,
-                                                            u32 *__restrict__ sliceOcc) {
-  constexpr int U = 4;
-  constexpr int VPL = 16 / sizeof(T);
-  constexpr int LPW = 64 / VPL;
-  // stream words of a span: SPAN_WORDS * 64 voxels at most, + the skew to the 16-byte boundary, rounded up to whole trips
-  // (chunks past the stream's end repeat its last vector: never read back), + the word a funnel shift looks ahead
-  constexpr int STAGE = SPAN_WORDS + (4 * U + 1) * VPL + 2;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
-  const T iso = sweep_lower<T>(isoD, isoI);
-  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
-  [[maybe_unused]] const bool invert = sweep_invert(isoI);
-  const int lane = threadIdx.x & 63;
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int sub = lane % LPW;
-  const bool last = sub == LPW - 1;
-  const u32 qStep = 512u / (u32)W, rStep = 512u % (u32)W;
-  for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
-    // (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic)
-    const u64 w0 = sp * (u64)SPAN_WORDS;
-    const u64 left = nwordsAll - w0;
-    const u32 nw = left < (u64)SPAN_WORDS ? (u32)left : (u32)SPAN_WORDS;
-    const u32 r0 = (u32)w0 / (u32)W;
-    const u32 k0 = (u32)w0 - r0 * (u32)W;
-    const u32 wl = (u32)w0 + nw - 1, r1 = wl / (u32)W;
-    const u32 k1 = wl - r1 * (u32)W;
-    const u64 v0 = (u64)r0 * (u64)nx + (u64)k0 * 64;
-    const u32 e1 = (k1 + 1) * 64u < (u32)nx ? (k1 + 1) * 64u : (u32)nx;
-    const u32 nvox = (r1 - r0) * (u32)nx + e1 - k0 * 64u;                  // voxels behind this span's words
-    const uintptr_t a0 = (uintptr_t)(vox + v0), ab = a0 & ~(uintptr_t)15;
-    const u32 skew = (u32)((a0 - ab) / sizeof(T));
-    const T *abase = reinterpret_cast<const T *>(ab);
-    // (the first and the last vector may reach up to 15 bytes outside the range: the same 16-byte granule as valid voxels,
-    //  so the loads cannot fault, and those bits are never used)
-    const u32 nvec = (skew + nvox + VPL - 1) / VPL;
-    const u32 n1k = (nvec + 63) / 64;                      // 1 KiB chunks of the stream
-#pragma unroll 1
-    for (u32 c = (u32)wib * U; c < n1k; c += 4 * U) {      // the waves take the stream's 4 KiB trips in turn
-      Vec16<T> r[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        u32 vi = (c + u) * 64 + lane;
-        vi = vi < nvec ? vi : nvec - 1;
-        const uint4 *src = reinterpret_cast<const uint4 *>(abase + (size_t)vi * VPL);
-        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
-        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        u32 m;
-        if constexpr (BAND) m = inside_bits_band<T>(r[u], iso, upper, invert);
-        else m = inside_bits<T>(r[u], iso);
-        const u64 word = group_or<LPW>((u64)m << (sub * VPL));
-        if (last) stage[(c + u) * VPL + lane / LPW] = word;
-      }
-    }
-    __syncthreads();
-    auto rsrc = __builtin_amdgcn_make_buffer_rsrc(bits + w0, 0, (int)(nw * 8u), 0x00020000);
-    // slice of a row: a span seldom crosses a slice boundary (SPAN_WORDS / W rows); where slices are shorter than a span's
-    // rows the division is taken per word
-    const u32 s0 = r0 / ny;
-    const u32 b1 = (s0 + 1) * ny;                          // first row of the next slice
-    const bool manySlices = r1 - r0 + 1 > ny;
-    u32 i = threadIdx.x * 2;
-    u32 row = r0 + (k0 + i) / (u32)W;
-    u32 k = (k0 + i) % (u32)W;
-    auto cut = [&](u32 rw, u32 kk, bool live) -> u64 {
-      if (!live) return 0ull;
-      const u32 rel = skew + (rw - r0) * (u32)nx + kk * 64u - k0 * 64u;       // bit of the staged stream the word starts at
-      const u32 j = rel >> 6, sh = rel & 63u;
-      const u64 lo = stage[j], hi = stage[j + 1];
-      u64 word = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-      const int n = nx - (int)kk * 64;
-      if (n < 64) word &= lowmask(n);
-      return word;
-    };
-    auto mark = [&](u64 word, u32 rw) {
-      if (!word) return;
-      const u32 sl = manySlices ? rw / ny : s0 + (rw >= b1 ? 1u : 0u);
-      sliceOcc[sl] = 1u;                                   // benign race: all store 1
-    };
-    for (; i < (u32)SPAN_WORDS; i += 512) {
-      const u32 rowB = k + 1 < (u32)W ? row : row + 1;
-      const u32 kB = k + 1 < (u32)W ? k + 1 : 0;
-      const u64 a = cut(row, k, i < nw), b = cut(rowB, kB, i + 1 < nw);
-      u32x4 v;
-      v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, i * 8, 0, 16);          // aux 16 = sc1: write-through; past nw: dropped
-      mark(a, row);
-      mark(b, rowB);
-      k += rStep; row += qStep;
-      if (k >= (u32)W) { k -= (u32)W; row++; }
     }
     __syncthreads();
   }
@@ -474,257 +366,264 @@ __global__ __launch_bounds__(256) void k_repack_rows(const u64 *__restrict__ fla
   bits[t] = word;
 }
 
-// Generic path (any nx): one wave per (row, word); lane l tests voxel x = 64k + l; the
-// wave ballot IS the packed word.
-template <class T, bool BAND = false>
-__global__ __launch_bounds__(256) void k_classify_rows(const T *__restrict__ vox, u64 *__restrict__ bits,
-                                                       int nx, int W, u64 t0, u64 nrows, u64 rowsPerSlice, typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI,
-                                                       u32 *__restrict__ sliceOcc) {
-  const T iso = sweep_lower<T>(isoD, isoI);
-  [[maybe_unused]] const T upper = sweep_upper<T>(isoD, isoI);            // (BAND: iso is the band's lower bound)
-  [[maybe_unused]] const bool invert = sweep_invert(isoI);
-  const int lane = threadIdx.x & 63;
-  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-  const u64 total = nrows * (u64)W;
-  for (u64 t = t0 + wave; t < total; t += nwaves) {
-    const u64 row = t / W;
-    const int k = (int)(t % W);
-    const int x = k * 64 + lane;
-    bool in = false;
-    if (x < nx) in = sweep_one<T, BAND>(vox[row * (u64)nx + x], iso, upper, invert);
-    const u64 word = __ballot(in);
-    if (lane == 0) {
-      bits[t] = word;
-      if (word) sliceOcc[row / rowsPerSlice] = 1u;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
-// The padded sweep (cuberille_set_border): the bit volume of the caller's nx x ny x nz image with a ring of one constant
-// voxel around it, in the layout every later kernel expects of an (nx+2) x (ny+2) x (nz+2) image -- rows of W =
-// (nx+2+63)/64 words, bit 0 and bit nx+1 of every row, rows 0 and ny+1 and slices 0 and nz+1 hold inside(ring value),
-// tail bits 0 -- from the caller's buffer as it is: no padded copy of the voxels exists anywhere.
+// The row sweeps: k_classify_span_rows (staged spans, large buffers) and k_classify_words (one wave per word, any size) write
+// the bit volume row by row -- rows of W words, tail bits 0, occupancy folded in -- for any source of rows.  What a source is
+// stands in a `Rows` type; the threshold (plain / band) is the separate parameter BAND, so a band form of another source is an
+// instantiation, not a kernel.  A Rows type says
+//   rows_per_slice()            rows of the bit volume per slice (the occupancy mark)
+//   inside(row, z, x, th)       the word sweep: the inside bit of voxel x of row `row` of slice z (false behind the row's end)
+//   STAGE, STAGE_GUARD          words of the span sweep's LDS stage; whether a staged word can fall behind it
+//   span(r0, k0, r1, k1)        per span -- words k0 of row r0 .. k1 of row r1 --: `nvec`, the 16-byte vectors to stage, and
+//                               whatever vector() and cut() need
+//   vector(span, v)             the address of staged vector v, clamped to the last one the span has
+//   cut(span, stage, r, k, th)  word k of row r out of the staged bits
 // ---------------------------------------------------------------------------------------------
 
-// how many rows of the caller's buffer lie below padded row `prow` (row = slice * rows-per-slice + y, in either frame)
-__device__ __forceinline__ u32 pad_rows_below(u32 prow, u32 ny, u32 nz) {
-  const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
-  const u32 full = pz == 0u ? 0u : (pz - 1u < nz ? pz - 1u : nz);
-  const u32 part = (pz >= 1u && pz <= nz) ? (py == 0u ? 0u : (py - 1u < ny ? py - 1u : ny)) : 0u;
-  return full * ny + part;
-}
-__device__ __forceinline__ bool pad_row_is_real(u32 prow, u32 ny, u32 nz) {
-  const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
-  return pz >= 1u && pz <= nz && py >= 1u && py <= ny;
-}
-
-// Any size, any alignment: one wave per output word; lane l tests padded voxel x = 64k + l, the ballot is the word.
-// Words [t0, t1) of the padded bit volume; nx, ny, nz: the caller's dims.
-template <class T>
-__global__ __launch_bounds__(256) void k_classify_pad_words(const T *__restrict__ vox, u64 *__restrict__ bits, u64 t0, u64 t1,
-                                                            int nx, int ny, int nz, int W, double isoD, long long isoI,
-                                                            double padD, long long padI, u32 *__restrict__ sliceOcc) {
-  const T iso = iso_as<T>(isoD, isoI);
-  const bool ringIn = !(iso_as<T>(padD, padI) < iso);
-  const int lane = threadIdx.x & 63;
-  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-  for (u64 t = t0 + wave; t < t1; t += nwaves) {
-    const u64 prow = t / (u64)W;
-    const int k = (int)(t - prow * (u64)W);
-    const u64 pz = prow / (u64)(ny + 2);
-    const int py = (int)(prow - pz * (u64)(ny + 2));
-    const int x = k * 64 + lane;
-    bool in = false;
-    if (x <= nx + 1) {
-      const bool ring = x == 0 || x == nx + 1 || py == 0 || py == ny + 1 || pz == 0 || pz == (u64)nz + 1;
-      in = ring ? ringIn : !(vox[((pz - 1) * (u64)ny + (u64)(py - 1)) * (u64)nx + (u64)(x - 1)] < iso);
-    }
-    const u64 word = __ballot(in);
-    if (lane == 0) {
-      bits[t] = word;
-      if (word) sliceOcc[pz] = 1u;             // benign race: all store 1
-    }
+// the threshold of a sweep in the pixel type, from the two argument slots (BAND: iso is the band's lower bound)
+template <class T, bool BAND>
+struct Threshold {
+  T iso, upper;
+  bool invert;
+  __device__ __forceinline__ Threshold(const typename SweepD<BAND>::type &d, const typename SweepI<BAND>::type &i)
+      : iso(sweep_lower<T>(d, i)), upper(sweep_upper<T>(d, i)), invert(sweep_invert(i)) {}
+  __device__ __forceinline__ u32 bits(const Vec16<T> &r) const {
+    if constexpr (BAND) return inside_bits_band<T>(r, iso, upper, invert);
+    else return inside_bits<T>(r, iso);
   }
+  __device__ __forceinline__ bool one(T v) const { return sweep_one<T, BAND>(v, iso, upper, invert); }
+};
+
+// two words as the operand of one 16-byte store
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 two_words(u64 a, u64 b) {
+  u32x4 v;
+  v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
+  return v;
 }
 
-// Large volumes: k_classify_span_rows with the rows one voxel to the right.  A workgroup owns SPAN_WORDS consecutive words
-// of the PADDED bit volume, a range of (padded row, word) pairs; the rows of the caller's buffer among them follow each other
-// in memory, so the voxels behind those words are still one contiguous range: a flat stream of 16-byte vectors into the LDS
-// stage exactly as there, and every thread cuts two words out of it -- from the bit before the word's first voxel on, so
-// that the row's voxel x lands on bit x + 1 (word 0 of a row: from its first voxel, shifted up by one, the ring's bit
-// below) -- with the ring's bit set behind the row's last voxel and nothing behind that.  Words of the ring's rows and
-// slices are a constant.  Every voxel is read once; occupancy folded in as there.
-// prow0: first padded row of the launch's range (bits and the spans start at its first word), nwordsAll: words of the range.
+// 64 bits of a staged bit stream from bit `rel` on (two LDS words, funnel-shifted) ...
+__device__ __forceinline__ u64 staged_word(const u64 *stage, u32 rel) {
+  const u32 j = rel >> 6, sh = rel & 63u;
+  const u64 lo = stage[j], hi = stage[j + 1];
+  return sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
+}
+// ... and word k of a row of nx voxels masked to the voxels it has
+__device__ __forceinline__ u64 row_end_masked(u64 word, int nx, u32 k) {
+  const int n = nx - (int)k * 64;
+  return n < 64 ? word & lowmask(n) : word;
+}
+
+// Stage of a span whose voxels are ONE stream: SPAN_WORDS * 64 voxels at most, + the skew to the 16-byte boundary, rounded up
+// to whole trips (chunks past the stream's end repeat its last vector: never read back), + the word a funnel shift looks ahead
 template <class T>
-__global__ __launch_bounds__(256) void k_classify_pad_span_rows(const T *__restrict__ vox, u64 *__restrict__ bits, u64 nspans,
-                                                                u64 nwordsAll, u32 prow0, int nx, u32 ny, u32 nz, int W,
-                                                                double isoD, long long isoI, double padD, long long padI,
-                                                                u32 *__restrict__ sliceOcc) {
-  constexpr int U = 4;
-  constexpr int VPL = 16 / sizeof(T);
-  constexpr int LPW = 64 / VPL;
-  // (the voxels behind a span are at most one per bit of its words and the one before its first: the stage of
-  //  k_classify_span_rows holds them with the same slack)
-  constexpr int STAGE = SPAN_WORDS + (4 * U + 1) * VPL + 2;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
-  const T iso = iso_as<T>(isoD, isoI);
-  const u64 ringBit = !(iso_as<T>(padD, padI) < iso) ? 1ull : 0ull;
-  const int lane = threadIdx.x & 63;
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int sub = lane % LPW;
-  const bool last = sub == LPW - 1;
-  const u32 qStep = 512u / (u32)W, rStep = 512u % (u32)W;
-  const u32 pny = ny + 2u;
-  for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
-    // (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic)
-    const u64 w0 = sp * (u64)SPAN_WORDS;
-    const u64 left = nwordsAll - w0;
-    const u32 nw = left < (u64)SPAN_WORDS ? (u32)left : (u32)SPAN_WORDS;
-    const u32 r0 = prow0 + (u32)w0 / (u32)W;
-    const u32 k0 = (u32)w0 % (u32)W;
-    const u32 wl = (u32)w0 + nw - 1, r1 = prow0 + wl / (u32)W;
-    const u32 k1 = wl % (u32)W;
+constexpr int one_stream_stage() { return SPAN_WORDS + (4 * 4 + 1) * (16 / (int)sizeof(T)) + 2; }
+
+// Rows that follow each other in memory (nx % 64 != 0 -- most real volumes -- or a pointer that is not 16-byte aligned).  The
+// voxels behind a span's words are one contiguous range: a flat stream of 16-byte vectors from the 16-byte boundary at or below
+// its first voxel (the first and the last vector may reach up to 15 bytes outside the range: the same 16-byte granule as valid
+// voxels, so the loads cannot fault, and those bits are never used).  No flat scratch stream in memory, no second trip of the
+// bits through L2, no repack and occupancy launches (round-4 review: 1000^3 f32 swept at 5.15 TB/s through those, against 6.7
+// for whole-word rows).
+template <class T>
+struct ContiguousRows {
+  static constexpr int VPL = 16 / sizeof(T);
+  static constexpr int STAGE = one_stream_stage<T>();
+  static constexpr bool STAGE_GUARD = false;
+  const T *vox;
+  int nx;
+  u32 ny;
+  struct Span {
+    const T *abase;
+    u32 nvec;
+    u32 origin;          // bit of the stage at which voxel 0 of row 0 would sit (mod 2^32)
+  };
+  __device__ __forceinline__ u32 rows_per_slice() const { return ny; }
+  template <class Th>
+  __device__ __forceinline__ bool inside(u64 row, u64, int x, const Th &th) const {
+    return x < nx && th.one(vox[row * (u64)nx + x]);
+  }
+  __device__ __forceinline__ Span span(u32 r0, u32 k0, u32 r1, u32 k1) const {
+    const u64 v0 = (u64)r0 * (u64)nx + (u64)k0 * 64;
+    const u32 e1 = (k1 + 1) * 64u < (u32)nx ? (k1 + 1) * 64u : (u32)nx;
+    const u32 nvox = (r1 - r0) * (u32)nx + e1 - k0 * 64u;                  // voxels behind this span's words
+    const uintptr_t a0 = (uintptr_t)(vox + v0), ab = a0 & ~(uintptr_t)15;
+    const u32 skew = (u32)((a0 - ab) / sizeof(T));
+    return Span{reinterpret_cast<const T *>(ab), (skew + nvox + VPL - 1) / VPL, skew - r0 * (u32)nx - k0 * 64u};
+  }
+  __device__ __forceinline__ const T *vector(const Span &s, u32 v) const {
+    return s.abase + (size_t)(v < s.nvec ? v : s.nvec - 1) * VPL;
+  }
+  template <class Th>
+  __device__ __forceinline__ u64 cut(const Span &s, const u64 *stage, u32 row, u32 k, const Th &) const {
+    return row_end_masked(staged_word(stage, s.origin + row * (u32)nx + k * 64u), nx, k);
+  }
+};
+
+// cuberille_set_border: the rows of the caller's nx x ny x nz image inside a ring of one constant voxel, in the layout every
+// later kernel expects of an (nx+2) x (ny+2) x (nz+2) image -- rows of W = (nx+2+63)/64 words, bit 0 and bit nx+1 of every
+// row, rows 0 and ny+1 and slices 0 and nz+1 hold inside(ring value), tail bits 0 -- from the caller's buffer as it is: no
+// padded copy of the voxels exists anywhere.  The rows of the buffer among a span's padded rows still follow each other in
+// memory: one stream, as above, and a word is cut from the bit before its first voxel on, so that the row's voxel x lands on
+// bit x + 1 (word 0 of a row: from its first voxel, shifted up by one, the ring's bit below), with the ring's bit set behind
+// the row's last voxel and nothing behind that.  Words of the ring's rows and slices are a constant; a span of the ring alone
+// reads nothing.
+template <class T>
+struct RingRows {
+  static constexpr int VPL = 16 / sizeof(T);
+  // (the voxels behind a span are at most one per bit of its words and the one before its first: ContiguousRows' slack holds)
+  static constexpr int STAGE = one_stream_stage<T>();
+  static constexpr bool STAGE_GUARD = false;
+  const T *vox;
+  int nx;
+  u32 ny, nz;            // the caller's dims
+  T ring;
+  struct Span {
+    const T *abase;
+    u32 nvec;
+    u32 origin;          // bit of the stage at which voxel 0 of the buffer's row 0 would sit (mod 2^32)
+  };
+  __device__ __forceinline__ u32 rows_per_slice() const { return ny + 2u; }
+  // how many rows of the caller's buffer lie below padded row `prow`, and whether it is one of them
+  __device__ __forceinline__ u32 rows_below(u32 prow) const {
+    const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
+    const u32 full = pz == 0u ? 0u : (pz - 1u < nz ? pz - 1u : nz);
+    const u32 part = (pz >= 1u && pz <= nz) ? (py == 0u ? 0u : (py - 1u < ny ? py - 1u : ny)) : 0u;
+    return full * ny + part;
+  }
+  __device__ __forceinline__ bool is_real(u32 prow) const {
+    const u32 pz = prow / (ny + 2u), py = prow - pz * (ny + 2u);
+    return pz >= 1u && pz <= nz && py >= 1u && py <= ny;
+  }
+  template <class Th>
+  __device__ __forceinline__ bool inside(u64 prow, u64 pz, int x, const Th &th) const {
+    if (x > nx + 1) return false;
+    const u32 py = (u32)(prow - pz * (u64)(ny + 2u));
+    const bool onRing = x == 0 || x == nx + 1 || py == 0u || py == ny + 1u || pz == 0 || pz == (u64)nz + 1;
+    return onRing ? th.one(ring) : th.one(vox[((pz - 1) * (u64)ny + (u64)(py - 1u)) * (u64)nx + (u64)(x - 1)]);
+  }
+  __device__ __forceinline__ Span span(u32 r0, u32 k0, u32 r1, u32 k1) const {
     // the stream: from the voxel one before word k0's first (row r0, where that is a row of the buffer) to the last voxel of
     // word k1 of row r1 (likewise); the buffer's rows between them whole
-    const u32 rr0 = pad_rows_below(r0, ny, nz), rr1 = pad_rows_below(r1, ny, nz);
-    const u32 xs0 = pad_row_is_real(r0, ny, nz) && k0 ? k0 * 64u - 1u : 0u;                      // (<= nx: W = ceil((nx + 2) / 64))
-    const u32 xe1 = pad_row_is_real(r1, ny, nz) ? ((k1 + 1) * 64u - 1u < (u32)nx ? (k1 + 1) * 64u - 1u : (u32)nx) : 0u;
+    const u32 rr0 = rows_below(r0), rr1 = rows_below(r1);
+    const u32 xs0 = is_real(r0) && k0 ? k0 * 64u - 1u : 0u;                      // (<= nx: W = ceil((nx + 2) / 64))
+    const u32 xe1 = is_real(r1) ? ((k1 + 1) * 64u - 1u < (u32)nx ? (k1 + 1) * 64u - 1u : (u32)nx) : 0u;
     const u64 v0 = (u64)rr0 * (u64)nx + xs0;
     const u32 nvox = (rr1 - rr0) * (u32)nx + xe1 - xs0;
     const uintptr_t a0 = (uintptr_t)(vox + v0), ab = a0 & ~(uintptr_t)15;
     const u32 skew = (u32)((a0 - ab) / sizeof(T));
-    const T *abase = reinterpret_cast<const T *>(ab);
-    // (the first and the last vector may reach up to 15 bytes outside the range: the same 16-byte granule as valid voxels,
-    //  so the loads cannot fault, and those bits are never used; a span of the ring alone reads nothing)
-    const u32 nvec = nvox ? (skew + nvox + VPL - 1) / VPL : 0u;
-    const u32 n1k = (nvec + 63) / 64;                      // 1 KiB chunks of the stream
-#pragma unroll 1
-    for (u32 c = (u32)wib * U; c < n1k; c += 4 * U) {      // the waves take the stream's 4 KiB trips in turn
-      Vec16<T> r[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        u32 vi = (c + u) * 64 + lane;
-        vi = vi < nvec ? vi : nvec - 1;
-        const uint4 *src = reinterpret_cast<const uint4 *>(abase + (size_t)vi * VPL);
-        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
-        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const u32 m = inside_bits<T>(r[u], iso);
-        const u64 word = group_or<LPW>((u64)m << (sub * VPL));
-        if (last) stage[(c + u) * VPL + lane / LPW] = word;
-      }
-    }
-    __syncthreads();
-    auto rsrc = __builtin_amdgcn_make_buffer_rsrc(bits + w0, 0, (int)(nw * 8u), 0x00020000);
-    auto cut = [&](u32 rw, u32 kk, bool live) -> u64 {
-      if (!live) return 0ull;
-      const int b = nx + 1 - (int)kk * 64;                 // bit of the ring's voxel behind the row (>= 0: kk < W)
-      const u64 rowMask = b < 63 ? lowmask(b + 1) : ~0ull;
-      if (!pad_row_is_real(rw, ny, nz)) return ringBit ? rowMask : 0ull;
-      // bit of the staged stream at which row rw's voxel x sits: skew + (rows of the buffer since the stream's) * nx + x - xs0
-      const u32 rowRel = skew + (pad_rows_below(rw, ny, nz) - rr0) * (u32)nx - xs0;
-      const u32 rel = rowRel + (kk ? kk * 64u - 1u : 0u);
-      const u32 j = rel >> 6, sh = rel & 63u;
-      const u64 lo = stage[j], hi = stage[j + 1];
-      u64 word = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-      if (!kk) word = (word << 1) | ringBit;
-      if (b < 64) word = (word & lowmask(b)) | (ringBit << b);
-      return word;
-    };
-    auto mark = [&](u64 word, u32 rw) {
-      if (word) sliceOcc[rw / pny] = 1u;                   // benign race: all store 1
-    };
-    u32 i = threadIdx.x * 2;
-    u32 row = r0 + (k0 + i) / (u32)W;
-    u32 k = (k0 + i) % (u32)W;
-    for (; i < (u32)SPAN_WORDS; i += 512) {
-      const u32 rowB = k + 1 < (u32)W ? row : row + 1;
-      const u32 kB = k + 1 < (u32)W ? k + 1 : 0;
-      const u64 a = cut(row, k, i < nw), b = cut(rowB, kB, i + 1 < nw);
-      u32x4 v;
-      v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, i * 8, 0, 16);          // aux 16 = sc1: write-through; past nw: dropped
-      mark(a, row);
-      mark(b, rowB);
-      k += rStep; row += qStep;
-      if (k >= (u32)W) { k -= (u32)W; row++; }
-    }
-    __syncthreads();
+    return Span{reinterpret_cast<const T *>(ab), nvox ? (skew + nvox + VPL - 1) / VPL : 0u, skew - rr0 * (u32)nx - xs0};
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The pitched sweep (cuberille_set_region): the bit volume of an nx x ny x nz BOX of a larger x-fastest buffer, in the layout
-// every later kernel expects of an nx x ny x nz image, from the caller's buffer as it is: no cropped copy of the voxels exists
-// anywhere.  `box` points at the box's first voxel; row y of slice z of the box starts at box + z * slicePitch + y * rowPitch
-// (in voxels: the buffer's Nx and Nx * Ny) and is aligned to nothing but the pixel type.
-// ---------------------------------------------------------------------------------------------
-
-// Any size: one wave per output word; lane l tests voxel x = 64k + l of its row, the ballot is the word.
-// Words [t0, t1) of the box's bit volume.
-template <class T>
-__global__ __launch_bounds__(256) void k_classify_region_words(const T *__restrict__ box, u64 *__restrict__ bits, u64 t0, u64 t1,
-                                                               int nx, int ny, int W, long long rowPitch, long long slicePitch,
-                                                               double isoD, long long isoI, u32 *__restrict__ sliceOcc) {
-  const T iso = iso_as<T>(isoD, isoI);
-  const int lane = threadIdx.x & 63;
-  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-  for (u64 t = t0 + wave; t < t1; t += nwaves) {
-    const u64 row = t / (u64)W;
-    const int k = (int)(t - row * (u64)W);
-    const u64 z = row / (u64)ny;
-    const u64 y = row - z * (u64)ny;
-    const int x = k * 64 + lane;
-    bool in = false;
-    if (x < nx) in = !(box[(long long)z * slicePitch + (long long)y * rowPitch + x] < iso);
-    const u64 word = __ballot(in);
-    if (lane == 0) {
-      bits[t] = word;
-      if (word) sliceOcc[z] = 1u;              // benign race: all store 1
-    }
+  __device__ __forceinline__ const T *vector(const Span &s, u32 v) const {
+    return s.abase + (size_t)(v < s.nvec ? v : s.nvec - 1) * VPL;
   }
-}
+  template <class Th>
+  __device__ __forceinline__ u64 cut(const Span &s, const u64 *stage, u32 prow, u32 k, const Th &th) const {
+    const u64 ringBit = th.one(ring) ? 1ull : 0ull;
+    const int b = nx + 1 - (int)k * 64;                  // bit of the ring's voxel behind the row (>= 0: k < W)
+    if (!is_real(prow)) return ringBit ? (b < 63 ? lowmask(b + 1) : ~0ull) : 0ull;
+    u64 word = staged_word(stage, s.origin + rows_below(prow) * (u32)nx + (k ? k * 64u - 1u : 0u));
+    if (!k) word = (word << 1) | ringBit;
+    if (b < 64) word = (word & lowmask(b)) | (ringBit << b);
+    return word;
+  }
+};
 
-// Large boxes: k_classify_span_rows with the rows a pitch apart.  A workgroup owns SPAN_WORDS consecutive words of the BOX's
-// bit volume, a range of (row, word) pairs; the voxels behind them are no longer one stream but one stream per row.  Every
-// row's stream is read as that kernel reads its one: 16-byte nontemporal vectors from the 16-byte boundary at or below the
-// row's first voxel to the one that holds its last (the first and the last vector of a row may reach up to 15 bytes outside
-// the row -- the same 16-byte granule as voxels of the box, so the loads cannot fault, and those bits are never used; no
-// vector lies wholly outside the box's rows).  The streams are staged back to back in LDS: the span's first row takes the vectors
-// it has, every further row a slot of VR vectors -- what a row can touch at its worst alignment -- so that a lane finds its
-// row and its vector with one division.  Then every thread cuts two row words out of the stage (two LDS words,
-// funnel-shifted, the row's last word masked to the voxels it has) and the span leaves as 16-byte write-through stores,
-// occupancy folded in.  row0: first row of the launch's range (bits and the spans start at its first word).
+// cuberille_set_region: the rows of an nx x ny x nz BOX of a larger x-fastest buffer, from the caller's buffer as it is: no
+// cropped copy of the voxels exists anywhere.  `box` points at the box's first voxel; row y of slice z of the box starts at
+// box + z * slicePitch + y * rowPitch (in voxels: the buffer's Nx and Nx * Ny) and is aligned to nothing but the pixel type.
+// The voxels behind a span's words are no longer one stream but one stream per row, each read like the one of ContiguousRows:
+// from the 16-byte boundary at or below the row's first voxel to the one that holds its last (no vector lies wholly outside
+// the box's rows).  The streams are staged back to back: the span's first row takes the vectors it has, every further row a
+// slot of VR vectors -- what a row can touch at its worst alignment -- so that a lane finds its row and its vector with one
+// division.
 template <class T>
-__global__ __launch_bounds__(256) void k_classify_region_span_rows(const T *__restrict__ box, u64 *__restrict__ bits, u64 nspans,
-                                                                   u64 nwordsAll, u32 row0, int nx, int W, u32 ny,
-                                                                   long long rowPitch, long long slicePitch, double isoD,
-                                                                   long long isoI, u32 *__restrict__ sliceOcc) {
-  constexpr int U = 4;
-  constexpr int VPL = 16 / sizeof(T);
-  constexpr int LPW = 64 / VPL;
+struct PitchedRows {
+  static constexpr int VPL = 16 / sizeof(T);
   // bits of the stage: the voxels behind the span's words (64 a word at most) + under 2 * VPL a row for the skew to the 16-byte
   // boundaries (a span has SPAN_WORDS rows at most), + the trips' rounding to whole 1 KiB chunks, + the word a funnel shift
   // looks ahead
-  constexpr int STAGE = SPAN_WORDS + SPAN_WORDS * 2 * VPL / 64 + VPL + 2;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  static constexpr int STAGE = SPAN_WORDS + SPAN_WORDS * 2 * VPL / 64 + VPL + 2;
+  static constexpr bool STAGE_GUARD = true;
+  const T *box;
+  int nx;
+  u32 ny;
+  long long rowPitch, slicePitch;
+  struct Span {
+    u32 r0, r1;
+    u32 xaFirst, xbLast;      // the first row from word k0 on, the last one up to word k1
+    u32 VR;                   // vectors a whole row touches at most
+    u32 nvec0, nvec;          // vectors of the first row, and of the whole span
+  };
+  // the stream of a span's row: the address of the vector that holds its first voxel, how many vectors it has, the voxels of
+  // that first vector that lie before the row's, and the row's first voxel
+  struct Stream {
+    uintptr_t first;
+    u32 nvec, skew, xa;
+  };
+  __device__ __forceinline__ u32 rows_per_slice() const { return ny; }
+  template <class Th>
+  __device__ __forceinline__ bool inside(u64 row, u64 z, int x, const Th &th) const {
+    const u64 y = row - z * (u64)ny;
+    return x < nx && th.one(box[(long long)z * slicePitch + (long long)y * rowPitch + x]);
+  }
+  __device__ __forceinline__ Stream stream(u32 r0, u32 xaFirst, u32 r1, u32 xbLast, u32 row) const {
+    const u32 z = row / ny, y = row - z * ny;
+    const T *p = box + (long long)z * slicePitch + (long long)y * rowPitch;
+    const u32 xa = row == r0 ? xaFirst : 0u, xb = row == r1 ? xbLast : (u32)nx;
+    const uintptr_t a = (uintptr_t)(p + xa), e = (uintptr_t)(p + xb) - 1;
+    return Stream{a & ~(uintptr_t)15, (u32)((e >> 4) - (a >> 4)) + 1u, (u32)((a & 15) / sizeof(T)), xa};
+  }
+  __device__ __forceinline__ Stream stream(const Span &s, u32 row) const { return stream(s.r0, s.xaFirst, s.r1, s.xbLast, row); }
+  __device__ __forceinline__ Span span(u32 r0, u32 k0, u32 r1, u32 k1) const {
+    const u32 xaFirst = k0 * 64u, xbLast = (k1 + 1) * 64u < (u32)nx ? (k1 + 1) * 64u : (u32)nx;
+    const u32 VR = (u32)(((u64)nx * sizeof(T) + 15 - sizeof(T)) / 16 + 1);
+    const u32 nvec0 = stream(r0, xaFirst, r1, xbLast, r0).nvec, nvecL = stream(r0, xaFirst, r1, xbLast, r1).nvec;
+    return Span{r0, r1, xaFirst, xbLast, VR, nvec0, r1 == r0 ? nvec0 : nvec0 + (r1 - r0 - 1) * VR + nvecL};
+  }
+  __device__ __forceinline__ const T *vector(const Span &s, u32 v) const {
+    v = v < s.nvec ? v : s.nvec - 1;
+    u32 row = s.r0, i = v;
+    if (v >= s.nvec0) {
+      const u32 t = v - s.nvec0, q = t / s.VR;
+      row = s.r0 + 1 + q;
+      i = t - q * s.VR;
+    }
+    const Stream st = stream(s, row);
+    i = i < st.nvec ? i : st.nvec - 1;                   // (a slot's spare vectors repeat the row's last: never read back)
+    return reinterpret_cast<const T *>(st.first + (uintptr_t)i * 16);
+  }
+  template <class Th>
+  __device__ __forceinline__ u64 cut(const Span &s, const u64 *stage, u32 row, u32 k, const Th &) const {
+    const Stream st = stream(s, row);
+    const u32 slot = row == s.r0 ? 0u : s.nvec0 + (row - s.r0 - 1) * s.VR;      // the first vector of the row's slot
+    return row_end_masked(staged_word(stage, slot * VPL + st.skew + k * 64u - st.xa), nx, k);
+  }
+};
+
+// Large buffers: the headline sweep (k_classify_span) for rows that are not whole words of the source.  A workgroup owns
+// SPAN_WORDS consecutive OUTPUT words, i.e. a range of (row, word) pairs; the 16-byte vectors behind them are thresholded
+// exactly as there -- 4 KiB trips per wave, nontemporal, DPP OR into 64-voxel words of the STREAM -- into the LDS stage; then
+// every thread cuts two row words out of the staged bits and the span leaves as the same 16-byte write-through stores,
+// occupancy folded in.  `bits` and the spans start at the first word of row row0; nwordsAll: words of the launch's range
+// (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic).
+template <class T, class Rows, bool BAND>
+__global__ __launch_bounds__(256) void k_classify_span_rows(const Rows rows, u64 *__restrict__ bits, u64 nspans, u64 nwordsAll,
+                                                            u32 row0, int W, typename SweepD<BAND>::type isoD,
+                                                            typename SweepI<BAND>::type isoI, u32 *__restrict__ sliceOcc) {
+  constexpr int U = 4;
+  constexpr int VPL = 16 / sizeof(T);
+  constexpr int LPW = 64 / VPL;
+  constexpr int STAGE = Rows::STAGE;
   __shared__ __attribute__((aligned(16))) u64 stage[STAGE];
-  const T iso = iso_as<T>(isoD, isoI);
+  const Threshold<T, BAND> th(isoD, isoI);
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane % LPW;
   const bool last = sub == LPW - 1;
   const u32 qStep = 512u / (u32)W, rStep = 512u % (u32)W;
-  const u32 VR = (u32)(((u64)nx * sizeof(T) + 15 - sizeof(T)) / 16 + 1);     // vectors a whole row touches at most
+  const u32 rps = rows.rows_per_slice();
   for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
-    // (the launcher takes this path for fewer than 2^32 words: rows and words of a span in 32-bit arithmetic)
     const u64 w0 = sp * (u64)SPAN_WORDS;
     const u64 left = nwordsAll - w0;
     const u32 nw = left < (u64)SPAN_WORDS ? (u32)left : (u32)SPAN_WORDS;
@@ -732,74 +631,31 @@ __global__ __launch_bounds__(256) void k_classify_region_span_rows(const T *__re
     const u32 k0 = (u32)w0 % (u32)W;
     const u32 wl = (u32)w0 + nw - 1, r1 = row0 + wl / (u32)W;
     const u32 k1 = wl % (u32)W;
-    const u32 xaFirst = k0 * 64u;                                             // the first row from word k0 on ...
-    const u32 xbLast = (k1 + 1) * 64u < (u32)nx ? (k1 + 1) * 64u : (u32)nx;   // ... the last one up to word k1
-    // the stream of row rw (a row of the span): the address of the vector that holds its first voxel, how many vectors it
-    // has, the voxels of that first vector that lie before the row's, and the row's first voxel
-    auto stream = [&](u32 rw, uintptr_t &first, u32 &nvec, u32 &skew, u32 &xa) {
-      const u32 z = rw / ny, y = rw - z * ny;
-      const T *row = box + (long long)z * slicePitch + (long long)y * rowPitch;
-      xa = rw == r0 ? xaFirst : 0u;
-      const u32 xb = rw == r1 ? xbLast : (u32)nx;
-      const uintptr_t a = (uintptr_t)(row + xa), e = (uintptr_t)(row + xb) - 1;
-      first = a & ~(uintptr_t)15;
-      nvec = (u32)((e >> 4) - (a >> 4)) + 1u;
-      skew = (u32)((a & 15) / sizeof(T));
-    };
-    uintptr_t f0, fl;
-    u32 nvec0, nvecL, sk, xx;
-    stream(r0, f0, nvec0, sk, xx);
-    stream(r1, fl, nvecL, sk, xx);
-    // vectors of the whole span, and the first vector of row rw's slot
-    const u32 nvTot = r1 == r0 ? nvec0 : nvec0 + (r1 - r0 - 1) * VR + nvecL;
-    auto slot = [&](u32 rw) -> u32 { return rw == r0 ? 0u : nvec0 + (rw - r0 - 1) * VR; };
-    const u32 n1k = (nvTot + 63) / 64;                     // 1 KiB chunks of the staged streams
+    const typename Rows::Span span = rows.span(r0, k0, r1, k1);
+    const u32 n1k = (span.nvec + 63) / 64;                 // 1 KiB chunks of the staged vectors
 #pragma unroll 1
     for (u32 c = (u32)wib * U; c < n1k; c += 4 * U) {      // the waves take the 4 KiB trips in turn
       Vec16<T> r[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        u32 v = (c + u) * 64 + lane;
-        v = v < nvTot ? v : nvTot - 1;
-        u32 rw = r0, i = v;
-        if (v >= nvec0) {
-          const u32 t = v - nvec0, q = t / VR;
-          rw = r0 + 1 + q;
-          i = t - q * VR;
-        }
-        uintptr_t first;
-        u32 nvec, skew, xa;
-        stream(rw, first, nvec, skew, xa);
-        i = i < nvec ? i : nvec - 1;                       // (a slot's spare vectors repeat the row's last: never read back)
-        const uint4 *src = reinterpret_cast<const uint4 *>(first + (uintptr_t)i * 16);
-        r[u].raw.x = __builtin_nontemporal_load(&src->x); r[u].raw.y = __builtin_nontemporal_load(&src->y);
-        r[u].raw.z = __builtin_nontemporal_load(&src->z); r[u].raw.w = __builtin_nontemporal_load(&src->w);
-      }
+      for (int u = 0; u < U; u++) load_nt16(r[u], rows.vector(span, (c + u) * 64 + lane));
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        const u32 m = inside_bits<T>(r[u], iso);
-        const u64 word = group_or<LPW>((u64)m << (sub * VPL));
+        const u64 word = group_or<LPW>((u64)th.bits(r[u]) << (sub * VPL));
         const u32 at = (c + u) * VPL + lane / LPW;
-        if (last && at < (u32)STAGE) stage[at] = word;
+        if (last && (!Rows::STAGE_GUARD || at < (u32)STAGE)) stage[at] = word;
       }
     }
     __syncthreads();
     auto rsrc = __builtin_amdgcn_make_buffer_rsrc(bits + w0, 0, (int)(nw * 8u), 0x00020000);
-    auto cut = [&](u32 rw, u32 kk, bool live) -> u64 {
-      if (!live) return 0ull;
-      uintptr_t first;
-      u32 nvec, skew, xa;
-      stream(rw, first, nvec, skew, xa);
-      const u32 rel = slot(rw) * VPL + skew + kk * 64u - xa;                  // bit of the stage the word starts at
-      const u32 j = rel >> 6, sh = rel & 63u;
-      const u64 lo = stage[j], hi = stage[j + 1];
-      u64 word = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-      const int n = nx - (int)kk * 64;
-      if (n < 64) word &= lowmask(n);
-      return word;
-    };
+    // slice of a row: a span seldom crosses a slice boundary (SPAN_WORDS / W rows); where slices are shorter than a span's
+    // rows the division is taken per word
+    const u32 s0 = r0 / rps;
+    const u32 b1 = (s0 + 1) * rps;                         // first row of the next slice
+    const bool manySlices = r1 - r0 + 1 > rps;
     auto mark = [&](u64 word, u32 rw) {
-      if (word) sliceOcc[rw / ny] = 1u;                    // benign race: all store 1
+      if (!word) return;
+      const u32 sl = manySlices ? rw / rps : s0 + (rw >= b1 ? 1u : 0u);
+      sliceOcc[sl] = 1u;                                   // benign race: all store 1
     };
     u32 i = threadIdx.x * 2;
     u32 row = r0 + (k0 + i) / (u32)W;
@@ -807,16 +663,38 @@ __global__ __launch_bounds__(256) void k_classify_region_span_rows(const T *__re
     for (; i < (u32)SPAN_WORDS; i += 512) {
       const u32 rowB = k + 1 < (u32)W ? row : row + 1;
       const u32 kB = k + 1 < (u32)W ? k + 1 : 0;
-      const u64 a = cut(row, k, i < nw), b = cut(rowB, kB, i + 1 < nw);
-      u32x4 v;
-      v.x = (u32)a; v.y = (u32)(a >> 32); v.z = (u32)b; v.w = (u32)(b >> 32);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, i * 8, 0, 16);          // aux 16 = sc1: write-through; past nw: dropped
+      const u64 a = i < nw ? rows.cut(span, stage, row, k, th) : 0ull;
+      const u64 b = i + 1 < nw ? rows.cut(span, stage, rowB, kB, th) : 0ull;
+      __builtin_amdgcn_raw_buffer_store_b128(two_words(a, b), rsrc, i * 8, 0, 16);   // aux 16 = sc1: write-through; past nw: dropped
       mark(a, row);
       mark(b, rowB);
       k += rStep; row += qStep;
       if (k >= (u32)W) { k -= (u32)W; row++; }
     }
     __syncthreads();
+  }
+}
+
+// Any size, any alignment: one wave per word; lane l tests voxel x = 64k + l of its row, the wave ballot IS the packed word.
+// Words [t0, t1) of the bit volume.
+template <class T, class Rows, bool BAND>
+__global__ __launch_bounds__(256) void k_classify_words(const Rows rows, u64 *__restrict__ bits, u64 t0, u64 t1, int W,
+                                                        typename SweepD<BAND>::type isoD, typename SweepI<BAND>::type isoI,
+                                                        u32 *__restrict__ sliceOcc) {
+  const Threshold<T, BAND> th(isoD, isoI);
+  const int lane = threadIdx.x & 63;
+  const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+  const u64 rps = rows.rows_per_slice();
+  for (u64 t = t0 + wave; t < t1; t += nwaves) {
+    const u64 row = t / (u64)W;
+    const int k = (int)(t - row * (u64)W);
+    auto slice = [&] { return row / rps; };    // (taken where it is used: contiguous rows need it for the mark alone)
+    const u64 word = __ballot(rows.inside(row, slice(), k * 64 + lane, th));
+    if (lane == 0) {
+      bits[t] = word;
+      if (word) sliceOcc[slice()] = 1u;        // benign race: all store 1
+    }
   }
 }
 
@@ -4461,7 +4339,7 @@ static inline unsigned grid_for(u64 threads, unsigned block, unsigned cap) {
 static int occupancy_shift(const Grid &g) {
   const u64 wps = (u64)g.ny * g.W;
   if (g.nx % 64 != 0 || (wps & (wps - 1)) != 0) return -1;
-  if (((u64)g.nzb * wps) % 16 != 0) return -1;    // a ragged tail goes through k_classify_rows
+  if (((u64)g.nzb * wps) % 16 != 0) return -1;    // a ragged tail goes through k_classify_words
   int lg = 0;
   while ((1ull << lg) < wps) lg++;
   return lg;
@@ -4477,14 +4355,12 @@ static bool ragged_stream_path(const Workspace &w, const Grid &g, size_t elem, c
   return g.nx % 64 != 0 && w.flatBits && ((uintptr_t)w.vox % elem) == 0 && !tn.no_stream_classify && !small_volume(g);
 }
 
-// The staged span sweeps (k_classify_*span_rows: occupancy on the fly, no scratch stream) are for buffers of `bytes` = 256 MiB
-// and more whose pointer holds whole elements, with fewer than 2^32 words in the bit volume.  What differs between the callers
-// stays an argument: classify_variant 1 (always the plain sweep) keeps every caller off them; anyVariant: every other value
-// of it may take them, forceSmall: and classify_variant 2 takes them below 256 MiB too (tests) -- else only the default, 0.
-static bool staged_spans(const void *vox, size_t elem, u64 bytes, const Grid &g, const Tuning &tn, bool anyVariant, bool forceSmall) {
-  const bool variant = anyVariant ? tn.classify_variant != 1 : tn.classify_variant == 0;
-  return variant && !tn.no_stream_classify && ((uintptr_t)vox % elem) == 0 &&
-         (bytes >= (256ull << 20) || (forceSmall && tn.classify_variant == 2)) && (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
+// The staged span sweep (k_classify_span_rows: occupancy on the fly, no scratch stream) is for buffers of `bytes` = 256 MiB
+// and more whose pointer holds whole elements, with fewer than 2^32 words in the bit volume.  classify_variant 1 (always the
+// plain sweep) keeps every source off it, 2 takes it below 256 MiB too (tests).
+static bool staged_spans(const void *vox, size_t elem, u64 bytes, const Grid &g, const Tuning &tn) {
+  return tn.classify_variant != 1 && !tn.no_stream_classify && ((uintptr_t)vox % elem) == 0 &&
+         (bytes >= (256ull << 20) || tn.classify_variant == 2) && (u64)g.ny * (u64)g.nzb * (u64)g.W < 0xffff0000ull;
 }
 
 // Workgroups for nspans spans taken in rounds by `want` of them (two per CU, or Tuning::classify_grid): as many as fill every
@@ -4495,15 +4371,33 @@ static unsigned whole_rounds(u64 nspans, const Tuning &tn) {
   return (unsigned)((nspans + rounds - 1) / rounds);
 }
 
-// the grid of the one-wave-per-word sweeps (k_classify_rows, _pad_words, _region_words) over `words` words
-static unsigned word_sweep_grid(u64 words) { return grid_for(words * 64, 256, 8192); }
-
 // Ragged rows of a plain buffer through the span sweep (k_classify_span_rows); also taken by whole-word rows behind a pointer
 // that is not 16-byte aligned.  A property of the BUFFER, so that every z-range of it takes the same route and
 // launch_occupancy knows which.
+static u64 frame_bytes(const Grid &g, size_t elem) { return (u64)g.nx * (u64)g.ny * (u64)g.nzb * (u64)elem; }
 static bool ragged_span_path(const Workspace &w, const Grid &g, size_t elem, const Tuning &tn) {
   const bool wholeAligned = g.nx % 64 == 0 && ((uintptr_t)w.vox % 16) == 0;
-  return !wholeAligned && staged_spans(w.vox, elem, (u64)g.nx * (u64)g.ny * (u64)g.nzb * (u64)elem, g, tn, false, false);
+  return !wholeAligned && staged_spans(w.vox, elem, frame_bytes(g, elem), g, tn);
+}
+
+// Words [t0, t1) of the bit volume (whole rows from t0 on, or the tail of the whole-word path) by one wave per word
+template <class T, bool BAND, class Rows, class D, class I>
+static void launch_words(const Rows &rows, const Workspace &w, const Grid &g, u64 t0, u64 t1, const D &iso, const I &isoI, hipStream_t s,
+                         unsigned blocks = 0) {
+  hipLaunchKernelGGL((k_classify_words<T, Rows, BAND>), dim3(blocks ? blocks : grid_for((t1 - t0) * 64, 256, 8192)), dim3(256), 0, s, rows, w.bits, t0,
+                     t1, g.W, iso, isoI, w.sliceOcc);
+}
+
+// The one span-or-words decision of every source of rows: words [t0, t1) -- whole rows -- of the bit volume from `rows`, a
+// buffer of `bytes` bytes at w.vox
+template <class T, bool BAND, class Rows, class D, class I>
+static void launch_row_sweep(const Rows &rows, u64 bytes, const Workspace &w, const Grid &g, u64 t0, u64 t1, const D &iso, const I &isoI,
+                             const Tuning &tn, hipStream_t s) {
+  if (!staged_spans(w.vox, sizeof(T), bytes, g, tn)) return launch_words<T, BAND>(rows, w, g, t0, t1, iso, isoI, s);
+  const u64 nwordsAll = t1 - t0;
+  const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
+  hipLaunchKernelGGL((k_classify_span_rows<T, Rows, BAND>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, rows, w.bits + t0, nspans, nwordsAll,
+                     (u32)(t0 / (u64)g.W), g.W, iso, isoI, w.sliceOcc);
 }
 
 // a (double, integer) pair in the pixel type, as iso_as does on the device
@@ -4540,16 +4434,8 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       const int nx = g.nx - 2, ny = g.ny - 2, nz = g.nzb - 2;
       const u64 pz0 = z0 == 0 ? 0 : (u64)z0 + 1, pz1 = z1 == nz ? (u64)nz + 2 : (u64)z1 + 1;
       const u64 wps = (u64)g.ny * g.W, t0 = pz0 * wps, t1 = pz1 * wps;
-      const T *vox = (const T *)wAll.vox;
-      if (staged_spans(vox, sizeof(T), (u64)nx * (u64)ny * (u64)nz * sizeof(T), g, tn, true, true)) {
-        const u64 nwordsAll = t1 - t0;
-        const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-        hipLaunchKernelGGL((k_classify_pad_span_rows<T>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, vox, wAll.bits + t0, nspans, nwordsAll,
-                           (u32)(pz0 * (u64)g.ny), nx, (u32)ny, (u32)nz, g.W, iso, isoI, wAll.view.padValue, wAll.view.padValueInt, wAll.sliceOcc);
-      } else {
-        hipLaunchKernelGGL((k_classify_pad_words<T>), dim3(word_sweep_grid(t1 - t0)), dim3(256), 0, s, vox, wAll.bits, t0, t1, nx, ny, nz, g.W, iso, isoI,
-                           wAll.view.padValue, wAll.view.padValueInt, wAll.sliceOcc);
-      }
+      const RingRows<T> rows{(const T *)wAll.vox, nx, (u32)ny, (u32)nz, value_as<T>(wAll.view.padValue, wAll.view.padValueInt)};
+      launch_row_sweep<T, false>(rows, (u64)nx * (u64)ny * (u64)nz * sizeof(T), wAll, g, t0, t1, iso, isoI, tn, s);
       return hipGetLastError();
     });
   if (wAll.view.kind == VIEW_REGION && wAll.view.pitched)
@@ -4557,16 +4443,8 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
       // cuberille_set_region: `g` is the box's layout, wAll.vox its first voxel in the caller's buffer, z0 / z1 slices of the box
       const u64 wps = (u64)g.ny * g.W, t0 = (u64)z0 * wps, t1 = (u64)z1 * wps;
-      const T *box = (const T *)wAll.vox;
-      if (staged_spans(box, sizeof(T), (u64)g.nx * (u64)g.ny * (u64)g.nzb * sizeof(T), g, tn, true, true)) {
-        const u64 nwordsAll = t1 - t0;
-        const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-        hipLaunchKernelGGL((k_classify_region_span_rows<T>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, box, wAll.bits + t0, nspans, nwordsAll,
-                           (u32)((u64)z0 * (u64)g.ny), g.nx, g.W, (u32)g.ny, wAll.view.rowPitch, wAll.view.slicePitch, iso, isoI, wAll.sliceOcc);
-      } else {
-        hipLaunchKernelGGL((k_classify_region_words<T>), dim3(word_sweep_grid(t1 - t0)), dim3(256), 0, s, box, wAll.bits, t0, t1, g.nx, g.ny, g.W,
-                           wAll.view.rowPitch, wAll.view.slicePitch, iso, isoI, wAll.sliceOcc);
-      }
+      const PitchedRows<T> rows{(const T *)wAll.vox, g.nx, (u32)g.ny, wAll.view.rowPitch, wAll.view.slicePitch};
+      launch_row_sweep<T, false>(rows, frame_bytes(g, sizeof(T)), wAll, g, t0, t1, iso, isoI, tn, s);
       return hipGetLastError();
     });
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
@@ -4579,6 +4457,8 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
     w.bits = wAll.bits + (size_t)z0 * g.ny * g.W;
     w.sliceOcc = wAll.sliceOcc + z0;
     const u64 nrows = (u64)g.ny * (z1 - z0);
+    const u64 t0 = (u64)z0 * g.ny * g.W, t1 = (u64)z1 * g.ny * g.W;        // the range's words, for the sweeps by rows
+    const ContiguousRows<T> rows{(const T *)wAll.vox, g.nx, (u32)g.ny};
     const bool aligned = ((uintptr_t)vox % 16) == 0;
     if (g.nx % 64 == 0 && aligned) {
       constexpr int VPL = 16 / sizeof(T);
@@ -4616,15 +4496,9 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
         hipLaunchKernelGGL((k_classify_flat<T, 8, true, BAND>), dim3(blocks), dim3(256), 0, s, vox + spanWords * 64, w.bits + spanWords,
                            nchunks, iso, isoI, w.sliceOcc, lg, spanWords);
       }
-      if (spanWords + nchunks * VPL < nwordsAll)
-        hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(1), dim3(256), 0, s, vox, w.bits, g.nx, g.W, spanWords + nchunks * VPL, nrows,
-                           (u64)g.ny, iso, isoI, w.sliceOcc);
-    } else if (ragged_span_path(wAll, g, sizeof(T), tn)) {
-      const u64 nwordsAll = nrows * g.W;
-      const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
-      hipLaunchKernelGGL((k_classify_span_rows<T, BAND>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, vox, w.bits, nspans, nwordsAll, g.nx, g.W, (u32)g.ny,
-                         iso, isoI, w.sliceOcc);
-    } else if (ragged_stream_path(wAll, g, sizeof(T), tn)) {
+      if (spanWords + nchunks * VPL < nwordsAll)      // (the < VPL words left: one block of the word sweep)
+        launch_words<T, BAND>(rows, wAll, g, t0 + spanWords + nchunks * VPL, t1, iso, isoI, s, 1);
+    } else if (!ragged_span_path(wAll, g, sizeof(T), tn) && ragged_stream_path(wAll, g, sizeof(T), tn)) {
       // ragged rows: flat stream of aligned 16-byte vectors (the first and last vector may reach up to 15 bytes
       // outside the range -- same 16-byte granule as valid voxels, so the loads cannot fault, and those bits
       // are never used), then cut into rows.  Each z-range uses its own part of the scratch.
@@ -4645,9 +4519,8 @@ hipError_t launch_classify(int pixel_type, const Workspace &wAll, const Grid &g,
       if (nvec % 64) hipLaunchKernelGGL((k_classify_tail<T, BAND>), dim3(1), dim3(64), 0, s, abase, flat, nchunks * 64, nvec, iso, isoI);
       hipLaunchKernelGGL(k_repack_rows, dim3(grid_for(nrows * g.W, 256, 0)), dim3(256), 0, s, flat, w.bits, g.nx, g.W, nrows, skew);
     } else {
-      const u64 total = nrows * g.W;
-      hipLaunchKernelGGL((k_classify_rows<T, BAND>), dim3(word_sweep_grid(total)), dim3(256), 0, s, vox, w.bits, g.nx, g.W, (u64)0, nrows,
-                         (u64)g.ny, iso, isoI, w.sliceOcc);
+      // the span sweep (ragged_span_path) or one wave per word
+      launch_row_sweep<T, BAND>(rows, frame_bytes(g, sizeof(T)), wAll, g, t0, t1, iso, isoI, tn, s);
     }
     return hipGetLastError();
     };

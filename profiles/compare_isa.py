@@ -4,8 +4,10 @@ literals aside, which move with a kernel's place in the code object).  It compar
 
     python profiles/compare_isa.py <parent's libcuberille_hip.so> midas-journal-740_amd/csrc/libcuberille_hip.so
 
-A kernel is matched by its canonical name: the kernel and its template arguments, argument lists aside.  The one rename rule
-kept here is that of the source views: the walk's three trailing bools of the parent (PAD, REGION, BAND, at most one true)
+A kernel is matched by its canonical name: the kernel and its template arguments, argument lists aside.  Two rename rules are
+kept here.  The row sweeps: the parent's six kernels by source (k_classify_span_rows / _pad_span_rows / _region_span_rows,
+k_classify_rows / _pad_words / _region_words) are k_classify_span_rows<T, Rows<T>, BAND> and k_classify_words<T, Rows<T>, BAND>
+here (ROW_SWEEPS; result: profiles/span_rows_isa.txt, where those 80 are meant to differ).  The source views: the walk's three trailing bools of the parent (PAD, REGION, BAND, at most one true)
 are its one VIEW value here (0 whole, 1 border, 2 region, 3 band).  Results: profiles/view_isa.txt, profiles/point_normals_isa.txt; the comparisons of the
 changes that added the border, the region and the band (region_walk_isa.txt, band_isa.txt) were made by this script's
 predecessors, which git history keeps (profiles/README.md).
@@ -21,6 +23,12 @@ import tempfile
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 VIEW_OF_BOOLS = {("false", "false", "false"): "0", ("true", "false", "false"): "1", ("false", "true", "false"): "2",
                  ("false", "false", "true"): "3"}
+# the six row sweeps of the parent -> the two kernels here and their source of rows (<T[, BAND]> -> <T, Rows<T>, BAND>)
+ROW_SWEEPS = {"k_classify_pad_span_rows": ("k_classify_span_rows", "RingRows"),
+              "k_classify_region_span_rows": ("k_classify_span_rows", "PitchedRows"),
+              "k_classify_rows": ("k_classify_words", "ContiguousRows"),
+              "k_classify_pad_words": ("k_classify_words", "RingRows"),
+              "k_classify_region_words": ("k_classify_words", "PitchedRows")}
 
 
 def kernels(lib):
@@ -53,9 +61,14 @@ def canonical(name):
     m = re.match(r"^(?:void )?(?:cuberille::)?(\w+)<(.*)>\(.*\)$", name)
     if not m:
         return re.sub(r"\(.*\)$", "", name), ()
-    args = [a.strip() for a in m.group(2).split(",")]
+    args = [a.strip().replace("cuberille::", "") for a in m.group(2).split(",")]
     if m.group(1) == "k_project" and tuple(args[-3:]) in VIEW_OF_BOOLS:
         args[-3:] = [VIEW_OF_BOOLS[tuple(args[-3:])]]
+    if m.group(1) == "k_classify_span_rows" and len(args) == 2:
+        return m.group(1), (args[0], "ContiguousRows<%s>" % args[0], args[1])
+    if m.group(1) in ROW_SWEEPS:
+        kernel, rows = ROW_SWEEPS[m.group(1)]
+        return kernel, (args[0], "%s<%s>" % (rows, args[0]), args[1] if len(args) > 1 else "false")
     return m.group(1), tuple(args)
 
 

@@ -359,11 +359,11 @@ int main(int argc, char **argv) {
     fflush(stdout);
   };
   // reference result with the product kernel
-  hipLaunchKernelGGL((k_classify_flat<float, 8, true>), dim3(2048), dim3(256), 0, 0, vox, bitsRef, nchunks, 0.5, occ, lg, (u64)0);
+  hipLaunchKernelGGL((k_classify_flat<float, 8, true>), dim3(2048), dim3(256), 0, 0, vox, bitsRef, nchunks, 0.5, 0ll, occ, lg, (u64)0);
   CK(hipDeviceSynchronize());
 
   report("read-only U8 nt grid 2048", T.run([&] { hipLaunchKernelGGL((k_read_only<8, true>), dim3(2048), dim3(256), 0, 0, (const uint4 *)vox, nchunks, diff); }, reps), false);
-  report("product grid 2048", T.run([&] { hipLaunchKernelGGL((k_classify_flat<float, 8, true>), dim3(2048), dim3(256), 0, 0, vox, bitsVar, nchunks, 0.5, occ, lg, (u64)0); }, reps), true);
+  report("product grid 2048", T.run([&] { hipLaunchKernelGGL((k_classify_flat<float, 8, true>), dim3(2048), dim3(256), 0, 0, vox, bitsVar, nchunks, 0.5, 0ll, occ, lg, (u64)0); }, reps), true);
 #define SPB(U, SPAN, BLOCK, GRID)                                                                                                \
   {                                                                                                                              \
     char nm[96];                                                                                                                 \

@@ -30,13 +30,13 @@ def main():
                            capture_output=True, text=True).stdout.splitlines()
     # (sspill: scalar registers spilled into the lanes of a vector register -- every use inside a loop is a v_readlane; the walk
     #  kernel lost 5 % to 62 of them before it got its forms by geometry, round 5)
-    print("%-70s %5s %5s %6s %6s %7s %4s %5s" % ("kernel", "VGPR", "SGPR", "sspill", "vspill", "scratch", "occ", "LDS"))
+    print("%-80s %5s %5s %6s %6s %7s %4s %5s" % ("kernel", "VGPR", "SGPR", "sspill", "vspill", "scratch", "occ", "LDS"))
     for r, n in zip(rows, names):
-        n = re.sub(r"^void cuberille::", "", n)
+        n = re.sub(r"^void ", "", n).replace("cuberille::", "")
         n = re.sub(r"\(.*$", "", n)
         if flt and flt not in n:
             continue
-        print("%-70s %5s %5s %6s %6s %7s %4s %5s" % (n[:70], r.get("VGPRs"), r.get("TotalSGPRs", r.get("SGPRs")), r.get("SGPRs Spill"),
+        print("%-80s %5s %5s %6s %6s %7s %4s %5s" % (n[:80], r.get("VGPRs"), r.get("TotalSGPRs", r.get("SGPRs")), r.get("SGPRs Spill"),
                                                        r.get("VGPRs Spill"), r.get("ScratchSize [bytes/lane]"),
                                                        r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
 

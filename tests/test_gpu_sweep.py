@@ -1,7 +1,8 @@
 """-m gpu: the threshold sweep (txx:139-141: inside <=> !(pixel < iso), in the pixel type) at the sizes where it is a kernel of
 its own -- buffers of 256 MiB and more -- for rows that are NOT whole 64-voxel words and for pointers that are not 16-byte
 aligned (k_classify_span_rows): packed bits against a torch threshold, slice occupancy, counts against the closed form, and one
-such volume byte for byte against the oracle."""
+such volume byte for byte against the oracle; and the same kernel at small shapes, where the development switch
+classify_variant 2 sends a plain buffer of any size through it (test_span_sweep_at_small_shapes)."""
 import numpy as np
 import pytest
 
@@ -100,6 +101,92 @@ def test_ragged_span_sweep_every_pixel_type(pkg, extractor, dtype, shape, skew):
     finally:
         extractor.debug_option("defaults", 0)
     del vol, raw, inside, words
+
+
+def _small_span_sweep(pkg, extractor, dtype, dims, skew=0, inverted_band=False):
+    """One buffer of `dims` = (nx, ny, nz), `skew` elements off its allocation, through k_classify_span_rows (classify_variant 2
+    sends a buffer of any size there) and through k_classify_words (classify_variant 1): the packed bits of the first against a
+    torch threshold (tail bits of every row zero) and against the second's, the slice occupancy of both against "any inside
+    voxel in the slice" -- with empty slices at both ends and in the middle where the volume has five slices or more (a
+    one-slice volume has none to spare)."""
+    import torch
+    nx, ny, nz = dims
+    vol, iso = _field((nz, ny, nx), dtype)
+    blank = vol.min()
+    if inverted_band:
+        # bit = NOT (lower <= pixel <= upper): the empty slices lie inside the band
+        mn, mx = vol.min().item(), vol.max().item()
+        lower, upper = int(mn + (mx - mn) * 0.4), int(mn + (mx - mn) * 0.6)
+        blank = (lower + upper) // 2
+    if nz >= 5:
+        n = 2 if nz >= 20 else 1
+        for a in (0, nz // 2, nz - n):
+            vol[a:a + n] = blank
+    item = np.dtype(dtype).itemsize
+    assert vol.element_size() == item
+    raw = torch.empty(vol.numel() + 16, dtype=vol.dtype, device="cuda")
+    raw[skew:skew + vol.numel()] = vol.reshape(-1)
+    torch.cuda.synchronize()
+    ptr = raw.data_ptr() + skew * item
+    assert nx % 64 != 0
+    desc = pkg.make_desc(dtype, (nx, ny, nz))
+    if inverted_band:
+        inside = ~((vol >= lower) & (vol <= upper))
+        prm = pkg.make_params(1, triangles=False, project=False)
+    else:
+        inside = vol >= iso
+        prm = pkg.make_params(iso, triangles=False, project=False)
+    assert inside.any() and not inside.all()
+    got = {}
+    try:
+        if inverted_band:
+            extractor.set_band(lower, upper, 0, 1)
+        for variant in (2, 1):
+            extractor.debug_option("classify_variant", variant)
+            extractor.extract_device(ptr, desc, prm)
+            got[variant] = (extractor.debug_bits((nx, ny, nz)), extractor.slice_occupancy(nz))
+    finally:
+        extractor.debug_option("defaults", 0)
+        if inverted_band:
+            extractor.clear_band()
+    W = (nx + 63) // 64
+    words = torch.from_numpy(got[2][0].view(np.int64)).cuda()
+    shifts = torch.arange(64, device="cuda", dtype=torch.int64)
+    bits = ((words[:, :, :, None] >> shifts) & 1).bool().reshape(nz, ny, W * 64)
+    assert torch.equal(bits[:, :, :nx], inside), "packed bits differ from the threshold"
+    assert not bits[:, :, nx:].any(), "bits beyond the end of a row"
+    assert np.array_equal(got[2][0], got[1][0]), "the span sweep and the word sweep pack different words"
+    occupied = inside.reshape(nz, -1).any(1).cpu().numpy()
+    if nz >= 5:
+        assert not occupied[0] and not occupied[nz // 2] and not occupied[nz - 1] and occupied.any()
+    assert np.array_equal(got[2][1], occupied) and np.array_equal(got[1][1], occupied)
+
+
+# W = 18 does not divide 4096: spans begin inside a row, the last span is partial; W = 1: a span covers 4096 rows of some 81
+# slices, the slice of a word by division; W = 516 > 512: a thread's next pair of words lies in the same row or the next
+# (qStep = 0); one word in all (nw = 1)
+SMALL_SPAN_DIMS = [(1100, 37, 29), (40, 50, 300), (33000, 3, 5), (63, 1, 1)]
+
+
+@pytest.mark.parametrize("dims", SMALL_SPAN_DIMS, ids=lambda d: "%dx%dx%d" % d)
+@pytest.mark.parametrize("dtype", [np.uint8, np.int16, np.float32, np.float64], ids=lambda t: np.dtype(t).name)
+def test_span_sweep_at_small_shapes(pkg, extractor, dtype, dims):
+    """The staged span sweep of a plain buffer at shapes of a few thousand to a few million voxels, pixels of 1, 2, 4 and 8
+    bytes (_small_span_sweep)."""
+    _small_span_sweep(pkg, extractor, dtype, dims)
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32], ids=lambda t: np.dtype(t).name)
+def test_span_sweep_at_small_shapes_every_pointer_residue(pkg, extractor, dtype):
+    """... with the pointer at every element residue of 16 bytes: the stream starts at the 16-byte boundary below the span's
+    first voxel."""
+    for skew in range(16 // np.dtype(dtype).itemsize):
+        _small_span_sweep(pkg, extractor, dtype, SMALL_SPAN_DIMS[0], skew=skew)
+
+
+def test_span_sweep_at_small_shapes_inverted_band(pkg, extractor):
+    """... and its band form, inverted: the bit is NOT (lower <= pixel <= upper)."""
+    _small_span_sweep(pkg, extractor, np.uint8, SMALL_SPAN_DIMS[0], skew=3, inverted_band=True)
 
 
 def test_ragged_1000_wide_volume_matches_oracle(pkg, oracle, extractor):
