@@ -48,6 +48,13 @@ namespace cuberille {
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ u64 lowmask(int b) { return (1ull << b) - 1ull; }   // b in 0..63
 __device__ __forceinline__ int popc64(u64 v) { return __popcll(v); }
+// is a row-major 3x3 matrix (Geo's dir, p2i) the identity, to the bit?
+__host__ __device__ __forceinline__ bool is_identity3(const double m[9]) {
+  bool is = true;
+#pragma unroll
+  for (int i = 0; i < 9; i++) is = is && (m[i] == ((i % 4 == 0) ? 1.0 : 0.0));
+  return is;
+}
 
 // the iso value in the pixel type (txx:140: m_IsoSurfaceValue IS an InputPixelType): a C cast of the double, except for
 // the 64-bit integer types, whose value travels as an integer
@@ -2579,19 +2586,73 @@ __global__ __launch_bounds__(256) void k_emit_cells(EmitArgs a, Grid g, size_t n
 // Every arithmetic step mirrors the ITK 3.x contract I3..I9 in the same
 // operation order as the oracle, so the float coordinates come out bit-identical.
 // ---------------------------------------------------------------------------------------------
+// The image the vertex side reads, as one source view (View, cuberille_internal.h) shows it.  Every position is one of the
+// view's FRAME: nx, ny, nzb are the frame's dims (all but VIEW_WHOLE: a whole volume, zglob0 = 0, gnz = nzb), every clamp happens
+// at the frame's faces.  What a view adds is said here and nowhere else -- its payload (ViewPayload; make_sampler fills it from
+// the kernel's four trailing arguments), the rim IN of the frame that is not in memory, how a position becomes an address
+// (row, frame), the ring's select (frame, on_ring / in_buffer) and what a loaded pixel stands for (map):
+//   VIEW_BORDER (cuberille_set_border): the frame is the caller's image with a ring of one constant voxel around it, and the
+//     ring is not stored: vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels, voxel p is vox[p - 1] where
+//     1 <= p <= n - 2 on every axis and `ring` elsewhere.
+//   VIEW_REGION (cuberille_set_region): the frame is a box of a larger buffer, as a cropped copy would be; vox points at the
+//     box's first voxel and rows / slices lie rowS / sliceS voxels apart -- the buffer's Nx and Nx * Ny.  Nothing outside the
+//     box is ever addressed.
+//   VIEW_BAND (cuberille_set_band): the image is B = (lower <= pixel && pixel <= upper) ? inside : outside, what
+//     itk::BinaryThresholdImageFilter makes of the volume, and B is not stored: every pixel the walk loads -- the 12 row
+//     segments of an interior cell like the clamped taps -- becomes one of the two values, in T, before any conversion or
+//     arithmetic.  A NaN pixel fails both comparisons and is `outside`.
+template <class T, int VIEW> struct ViewPayload {};
+template <class T> struct ViewPayload<T, VIEW_BORDER> { T ring; };
+template <class T> struct ViewPayload<T, VIEW_REGION> { long long rowS, sliceS; };
+template <class T> struct ViewPayload<T, VIEW_BAND> { T lower, upper, inside, outside; };
+
 template <class T, int VIEW = VIEW_WHOLE>
 struct Sampler {
   const T *vox;
   int nx, ny, nzb;
   int zglob0, gnz;
-  __device__ __forceinline__ T map(T v) const { return v; }       // (what a loaded pixel stands for: itself; see the VIEW_BAND form)
-  __device__ __forceinline__ int zlocal(int zg) const {          // global z -> buffer slice
-    const int z = zg - zglob0;
+  ViewPayload<T, VIEW> v;
+  static constexpr int IN = VIEW == VIEW_BORDER ? 1 : 0;          // voxels of the frame's rim that are not in memory
+  __device__ __forceinline__ T map(T p) const {                   // what a loaded pixel stands for
+    if constexpr (VIEW == VIEW_BAND) return (v.lower <= p && p <= v.upper) ? v.inside : v.outside;
+    else return p;
+  }
+  __device__ __forceinline__ int zlocal(int zg) const {           // global z -> the frame's slice (VIEW_WHOLE alone serves slabs)
+    const int z = VIEW == VIEW_WHOLE ? zg - zglob0 : zg;
     return z < 0 ? 0 : (z > nzb - 1 ? nzb - 1 : z);
   }
-  __device__ __forceinline__ T at(int x, int y, int zg) const {   // global z in
-    return vox[((size_t)zlocal(zg) * ny + y) * nx + x];
+  // How a position becomes an address.  Memory positions are frame positions - IN per axis.  The two forms below spell each
+  // view's expression out as it has always stood (a single index in `frame`, a pointer moved by slices, then rows in `row`):
+  // written through one shared helper they are the same addresses, but the compiler schedules the walk differently.
+  // the address of a row of memory; the two pitches between rows and slices
+  __device__ __forceinline__ const T *row(int y, int z) const {
+    if constexpr (VIEW == VIEW_REGION) return vox + z * v.sliceS + y * v.rowS;
+    else return vox + ((size_t)z * (ny - 2 * IN) + y) * (nx - 2 * IN);
   }
+  __device__ __forceinline__ ptrdiff_t row_pitch() const {
+    if constexpr (VIEW == VIEW_REGION) return (ptrdiff_t)v.rowS;
+    else return (ptrdiff_t)(nx - 2 * IN);
+  }
+  __device__ __forceinline__ ptrdiff_t slice_pitch() const {
+    if constexpr (VIEW == VIEW_REGION) return (ptrdiff_t)v.sliceS;
+    else return (ptrdiff_t)(ny - 2 * IN) * (nx - 2 * IN);
+  }
+  // the frame's pixel before any band mapping, z the frame's slice: the rim that is not in memory yields the ring's value
+  __device__ __forceinline__ T frame(int x, int y, int z) const {
+    if constexpr (VIEW == VIEW_BORDER) {
+      // (unsigned compare: p - 1 in [0, n - 3])
+      const bool real = (unsigned)(x - 1) < (unsigned)(nx - 2) && (unsigned)(y - 1) < (unsigned)(ny - 2) &&
+                        (unsigned)(z - 1) < (unsigned)(nzb - 2);
+      if (!real) return v.ring;
+      return vox[((size_t)(z - 1) * (ny - 2) + (y - 1)) * (nx - 2) + (x - 1)];
+    } else if constexpr (VIEW == VIEW_REGION) return vox[z * v.sliceS + y * v.rowS + x];
+    else return vox[((size_t)z * ny + y) * nx + x];
+  }
+  // a position p of the frame (0 .. n - 1) along an axis of length n: on the rim that is not in memory?  its memory position,
+  // clamped into the buffer (so that a load is always legal; the rim's taps are replaced afterwards)
+  __device__ __forceinline__ bool on_ring(int p, int n) const { return IN && (p == 0 || p == n - 1); }
+  __device__ __forceinline__ int in_buffer(int p, int n) const { return IN ? min(max(p - 1, 0), n - 3) : p; }
+  __device__ __forceinline__ T at(int x, int y, int zg) const { return map(frame(x, y, zlocal(zg))); }   // global z in
   __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
     x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
     y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
@@ -2600,79 +2661,23 @@ struct Sampler {
   }
 };
 
-// cuberille_set_border: the image the walk sees is the caller's with a ring of one constant voxel around it, and the ring
-// is not stored.  nx, ny, nzb are the PADDED dims (a whole volume: zglob0 = 0, gnz = nzb) and every position is one of
-// the padded frame; vox is the caller's buffer of (nx-2) x (ny-2) x (nzb-2) voxels.  Voxel p is vox[p - 1] where
-// 1 <= p <= n - 2 on every axis and `ring` elsewhere.
-template <class T>
-struct Sampler<T, VIEW_BORDER> {
-  const T *vox;
-  int nx, ny, nzb;
-  int zglob0, gnz;
-  T ring;
-  __device__ __forceinline__ T map(T v) const { return v; }
-  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
-  __device__ __forceinline__ T at_buffer(int x, int y, int z) const {   // positions inside the padded frame
-    // (unsigned compare: p - 1 in [0, n - 3])
-    const bool real = (unsigned)(x - 1) < (unsigned)(nx - 2) && (unsigned)(y - 1) < (unsigned)(ny - 2) &&
-                      (unsigned)(z - 1) < (unsigned)(nzb - 2);
-    if (!real) return ring;
-    return vox[((size_t)(z - 1) * (ny - 2) + (y - 1)) * (nx - 2) + (x - 1)];
-  }
-  // a position p of the padded frame (0 .. n - 1) along an axis of padded length n: on the ring?  its place in the buffer,
-  // clamped into it (so that a load is always legal; the ring's taps are replaced afterwards)
-  __device__ __forceinline__ bool on_ring(int p, int n) const { return p == 0 || p == n - 1; }
-  __device__ __forceinline__ int in_buffer(int p, int n) const { return min(max(p - 1, 0), n - 3); }
-  __device__ __forceinline__ T at(int x, int y, int zg) const { return at_buffer(x, y, zlocal(zg)); }
-  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
-    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
-    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
-    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
-    return at(x, y, zg);
-  }
-};
+// A view's payload travels as the four trailing arguments of its kernels: the ring's value as padD / padI (the pair the iso
+// value travels as), the region's rowPitch / slicePitch, the band's lower, upper, inside, outside as four scalars of T in the
+// place of those four, which that view has no use for.  The instantiations that need none never read them.
+template <class T, int VIEW, class A> struct WalkArg { typedef A type; };
+template <class T, class A> struct WalkArg<T, VIEW_BAND, A> { typedef T type; };
 
-// cuberille_set_region: the image the walk sees is a box of a larger buffer.  nx, ny, nzb are the BOX's dims (a whole volume:
-// zglob0 = 0, gnz = nzb), every position is one of the box's frame and every clamp happens at the box's faces, as it would on a
-// cropped copy; vox points at the box's first voxel and rows / slices lie rowS / sliceS voxels apart -- the buffer's Nx and
-// Nx * Ny.  Nothing outside the box is ever addressed.
-template <class T>
-struct Sampler<T, VIEW_REGION> {
-  const T *vox;
-  int nx, ny, nzb;
-  int zglob0, gnz;
-  long long rowS, sliceS;
-  __device__ __forceinline__ T map(T v) const { return v; }
-  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
-  __device__ __forceinline__ T at(int x, int y, int zg) const { return vox[zlocal(zg) * sliceS + y * rowS + x]; }
-  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
-    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
-    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
-    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
-    return at(x, y, zg);
-  }
-};
-
-// cuberille_set_band: the image the walk sees is B = (lower <= pixel && pixel <= upper) ? inside : outside, what
-// itk::BinaryThresholdImageFilter makes of the volume, and B is not stored: every pixel the walk loads -- the 12 row segments
-// of an interior cell like the clamped taps -- becomes one of the two values, in T, before any conversion or arithmetic.  A NaN
-// pixel fails both comparisons and is `outside`.  A whole volume (zglob0 = 0, gnz = nzb), no ring, no pitches.
-template <class T>
-struct Sampler<T, VIEW_BAND> {
-  const T *vox;
-  int nx, ny, nzb;
-  int zglob0, gnz;
-  T lower, upper, inside, outside;
-  __device__ __forceinline__ T map(T v) const { return (lower <= v && v <= upper) ? inside : outside; }
-  __device__ __forceinline__ int zlocal(int zg) const { return zg < 0 ? 0 : (zg > nzb - 1 ? nzb - 1 : zg); }
-  __device__ __forceinline__ T at(int x, int y, int zg) const { return map(vox[((size_t)zlocal(zg) * ny + y) * nx + x]); }
-  __device__ __forceinline__ T at_clamped(int x, int y, int zg) const {
-    x = x < 0 ? 0 : (x > nx - 1 ? nx - 1 : x);
-    y = y < 0 ? 0 : (y > ny - 1 ? ny - 1 : y);
-    zg = zg < 0 ? 0 : (zg > gnz - 1 ? gnz - 1 : zg);
-    return at(x, y, zg);
-  }
-};
+template <class T, int VIEW = VIEW_WHOLE>
+__device__ __forceinline__ Sampler<T, VIEW> make_sampler(const T *vox, const Grid &g, typename WalkArg<T, VIEW, double>::type a0 = {},
+                                                         typename WalkArg<T, VIEW, long long>::type a1 = {},
+                                                         typename WalkArg<T, VIEW, long long>::type a2 = {},
+                                                         typename WalkArg<T, VIEW, long long>::type a3 = {}) {
+  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
+  if constexpr (VIEW == VIEW_BORDER) s.v.ring = iso_as<T>(a0, a1);
+  if constexpr (VIEW == VIEW_REGION) { s.v.rowS = a2; s.v.sliceS = a3; }
+  if constexpr (VIEW == VIEW_BAND) { s.v.lower = a0; s.v.upper = a1; s.v.inside = a2; s.v.outside = a3; }
+  return s;
+}
 
 __device__ __forceinline__ int to_index_clamped(double b, int end) {
   // branch-free: fmax(NaN, 0) is 0, so a NaN coordinate (quirk Q4) lands on index 0 and never reads
@@ -2827,17 +2832,17 @@ __device__ __forceinline__ void cell_gradients(const Geo &geo, bool dirIdentity,
 // up to the SIGN OF A ZERO result, and a zero gradient component only ever enters the walk as a term added to a
 // sum that starts at +0 -- so the walk cannot tell.  Non-finite taps always give a non-finite component here too;
 // the caller tests for that and gathers again with LITERAL = true.
-// VIEW_BORDER: positions are those of the padded frame; "interior" then means that the cell and its ring lie
-// inside the caller's buffer -- one voxel further in on every side -- and the 12 row segments are read through a base pointer
-// moved back by one voxel per axis, with the buffer's own row and slice pitch.  Only cells that touch the implied ring
-// take the clamped forms, whose taps go through Sampler::at_buffer.
-// VIEW_REGION: positions are those of the box, whose rows and slices lie the BUFFER's pitch apart in memory.
+// The view enters through the Sampler alone, which is asked for three things: the interior form's base pointer and two pitches
+// (row, row_pitch, slice_pitch), the clamped form's row pointer (row again) and a tap with the view's mapping (map) or, in the
+// one branch by view that is left here, the ring's select (in_buffer, on_ring).
+// "Interior" means that the cell and its ring of neighbours lie in memory: IN voxels further in on every side where the
+// frame has a rim that is not stored (VIEW_BORDER), and only cells that touch that rim take the clamped forms.
 template <class T, bool LITERAL, int VIEW = VIEW_WHOLE>
 __device__ __forceinline__ void gather_cell(const Sampler<T, VIEW> &s, const Geo &geo, bool dirIdentity, const Cell8 &c,
                                             float G[8][3], typename SiteValue<T>::type Vd[8]) {
   const bool unit = c.lo[0] + 1 == c.hi[0] && c.lo[1] + 1 == c.hi[1] && c.lo[2] + 1 == c.hi[2];
   const int zl = c.lo[2] - s.zglob0;              // buffer slice of the cell's lower z
-  constexpr int IN = VIEW == VIEW_BORDER ? 1 : 0;                 // voxels of the frame's rim that are not in memory
+  constexpr int IN = Sampler<T, VIEW>::IN;
   const bool interior = unit && c.lo[0] >= 1 + IN && c.lo[0] + 2 + IN < s.nx && c.lo[1] >= 1 + IN && c.lo[1] + 2 + IN < s.ny &&
                         zl >= 1 + IN && zl + 2 + IN < s.nzb;
   // one address form per gather pass: the immediate-offset form only when EVERY lane gathering now sits in the
@@ -2847,16 +2852,8 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, VIEW> &s, const Geo
   if (interior && allInterior) {
     // the cell and its ring of neighbours lie inside the buffer: nothing is clamped, so the 12 row segments are
     // the cell's own address plus wave-uniform strides, and the x neighbours are immediate offsets
-    const int pnx = s.nx - 2 * IN, pny = s.ny - 2 * IN;      // row and slice pitch of the buffer in memory
-    const T *base;
-    ptrdiff_t rowS, sliceS;
-    if constexpr (VIEW == VIEW_REGION) {
-      rowS = (ptrdiff_t)s.rowS; sliceS = (ptrdiff_t)s.sliceS;
-      base = s.vox + zl * sliceS + c.lo[1] * rowS + c.lo[0];
-    } else {
-      base = s.vox + ((size_t)(zl - IN) * pny + (c.lo[1] - IN)) * pnx + (c.lo[0] - IN);
-      rowS = (ptrdiff_t)pnx; sliceS = (ptrdiff_t)pny * pnx;
-    }
+    const T *base = s.row(c.lo[1] - IN, zl - IN) + (c.lo[0] - IN);
+    const ptrdiff_t rowS = s.row_pitch(), sliceS = s.slice_pitch();
     T V[4][4][4];
 #pragma unroll
     for (int zi = 0; zi < 4; zi++)
@@ -2889,33 +2886,25 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, VIEW> &s, const Geo
         if (!zin && !yin) continue;
         if constexpr (VIEW == VIEW_BORDER) {
           // every tap is loaded from the buffer at its position clamped into it -- the same unconditional loads as the
-          // unpadded form -- and replaced by the ring's value where an axis says "ring": per axis four flags, per tap a select
+          // form below -- and replaced by the ring's value where an axis says "ring": per axis four flags, per tap a select
+          // (folded into the form below it is the same taps, but other instructions in the walk)
           const bool oyz = s.on_ring(ys[yi], s.ny) || s.on_ring(zs[zi], s.nzb);
-          const T *row = s.vox + ((size_t)s.in_buffer(zs[zi], s.nzb) * (s.ny - 2) + s.in_buffer(ys[yi], s.ny)) * (s.nx - 2);
-          if (zin && yin) {
+          const int zb = s.in_buffer(zs[zi], s.nzb), yb = s.in_buffer(ys[yi], s.ny);
+          const T *row = s.row(yb, zb);
 #pragma unroll
-            for (int xi = 0; xi < 4; xi++) {
-              const T v = row[s.in_buffer(xs[xi], s.nx)];
-              V[zi][yi][xi] = (oyz || s.on_ring(xs[xi], s.nx)) ? s.ring : v;
-            }
-          } else {
-#pragma unroll
-            for (int xi = 1; xi < 3; xi++) {
-              const T v = row[s.in_buffer(xs[xi], s.nx)];
-              V[zi][yi][xi] = (oyz || s.on_ring(xs[xi], s.nx)) ? s.ring : v;
-            }
+          for (int xi = (zin && yin ? 0 : 1); xi < (zin && yin ? 4 : 3); xi++) {
+            const T v = row[s.in_buffer(xs[xi], s.nx)];
+            V[zi][yi][xi] = (oyz || s.on_ring(xs[xi], s.nx)) ? s.v.ring : v;
           }
         } else {
-        const T *row;
-        if constexpr (VIEW == VIEW_REGION) row = s.vox + zs[zi] * s.sliceS + ys[yi] * s.rowS;
-        else row = s.vox + ((size_t)zs[zi] * s.ny + ys[yi]) * s.nx;
-        if (zin && yin) {
+          const T *row = s.row(ys[yi], zs[zi]);
+          if (zin && yin) {
 #pragma unroll
-          for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = s.map(row[xs[xi]]);
-        } else {
-          V[zi][yi][1] = s.map(row[xs[1]]);
-          V[zi][yi][2] = s.map(row[xs[2]]);
-        }
+            for (int xi = 0; xi < 4; xi++) V[zi][yi][xi] = s.map(row[xs[xi]]);
+          } else {
+            V[zi][yi][1] = s.map(row[xs[1]]);
+            V[zi][yi][2] = s.map(row[xs[2]]);
+          }
         }
       }
     cell_gradients<T, LITERAL>(geo, dirIdentity, V, G, Vd);
@@ -2963,9 +2952,6 @@ __device__ __forceinline__ void gather_cell(const Sampler<T, VIEW> &s, const Geo
 // VIEW_BAND: every pixel the walk loads is mapped to the band's
 // `inside` or `outside` first (Sampler's VIEW_BAND form); the two bounds and the two values arrive as four scalars of T in the place
 // of the four arguments above, which that form has no use for -- the other instantiations keep their argument block to the letter.
-template <class T, int VIEW, class A> struct WalkArg { typedef A type; };
-template <class T, class A> struct WalkArg<T, VIEW_BAND, A> { typedef T type; };
-
 template <class T, int MODE, int GEOM, int VIEW = VIEW_WHOLE>
 __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentityArg,
                                                  float *__restrict__ points, u64 nPoints, u64 nGhost, u64 chunk,
@@ -3009,10 +2995,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   if (wave >= nBatches) return;
   u64 next = 0;                                   // wave-uniform cursor
   const u64 end = ((nBatches - wave + NW - 1) / NW) << lgChunk;
-  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
-  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
-  if constexpr (VIEW == VIEW_BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
+  const Sampler<T, VIEW> s = make_sampler<T, VIEW>(vox, g, padD, padI, rowPitch, slicePitch);
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
   const double iso = (double)iso_as<T>(prm.iso, prm.isoInt);
   unsigned myIters = 0;
@@ -3033,6 +3016,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
   constexpr bool IDENT = GEOM == 2, DIAG = GEOM == 1;
   bool unitP2I = true;
   if constexpr (GEOM == 0) {
+    // (is_identity3, spelt out: through the helper this kernel comes out of the compiler with other instructions)
 #pragma unroll
     for (int i = 0; i < 9; i++) unitP2I = unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
   } else {
@@ -3238,6 +3222,36 @@ __global__ __launch_bounds__(256, (sizeof(T) == 8 ? 3 : 4)) void k_project(const
 // every interpolation replayed to the letter (zero weights skipped, stop once the weights sum to 1), IEEE sqrt and
 // divide -- and share only the gather with k_project.
 // ---------------------------------------------------------------------------------------------
+// The reference's linear interpolation to the letter (I5, I7): the eight corners of the cell in counter order, a corner of zero
+// weight skipped ("if (overlap)"), the loop left once the weights sum to exactly 1.  site(corner, x, y, z, weight) gets each
+// visited corner: its number, the site's three indices and the weight.
+template <class F>
+__device__ __forceinline__ void interpolate_literal(const Cell8 &c, F &&site) {
+  double total = 0.0;
+#pragma unroll
+  for (unsigned counter = 0; counter < 8; counter++) {
+    double overlap = 1.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
+    if (overlap != 0.0 && total != 1.0) {
+      site(counter, (counter & 1) ? c.hi[0] : c.lo[0], (counter & 2) ? c.hi[1] : c.lo[1], (counter & 4) ? c.hi[2] : c.lo[2], overlap);
+      total += overlap;
+    }
+  }
+}
+
+// I8 of the shipped gradient type, CovariantVector<float,3>: the interpolated sum narrowed to float, the sum of squares and its
+// sqrt in double, one IEEE divide per component, each rounded to float again.  Quirk Q4: no zero guard.
+__device__ __forceinline__ void normalize_narrowed(const double acc[3], float out[3]) {
+  float normal[3];
+  double sq = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { normal[k] = (float)acc[k]; const double e = (double)normal[k]; sq += e * e; }
+  const double norm = sqrt(sq);
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[k] = (float)((double)normal[k] / norm);
+}
+
 template <class T>
 struct VariantCtx {
   Sampler<T> s;
@@ -3259,21 +3273,14 @@ __device__ void variant_normal(const VariantCtx<T> &x, const float vertex[3], do
   const double p[3] = {(double)vertex[0], (double)vertex[1], (double)vertex[2]};
   Cell8 c;
   make_cell(x.geo, x.unitP2I, x.n, p, c);
+  float normal[3];
+  double acc[3] = {0.0, 0.0, 0.0};
   if (x.gimg) {
-    double acc[3] = {0.0, 0.0, 0.0}, total = 0.0;
+    interpolate_literal(c, [&](unsigned, int sx, int sy, int sz, double overlap) {
+      const double *gp = x.gimg + 3 * (((size_t)sz * x.n[1] + sy) * x.n[0] + sx);
 #pragma unroll
-    for (unsigned counter = 0; counter < 8; counter++) {
-      double overlap = 1.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
-      if (overlap != 0.0 && total != 1.0) {
-        const int sx = (counter & 1) ? c.hi[0] : c.lo[0], sy = (counter & 2) ? c.hi[1] : c.lo[1], sz = (counter & 4) ? c.hi[2] : c.lo[2];
-        const double *gp = x.gimg + 3 * (((size_t)sz * x.n[1] + sy) * x.n[0] + sx);
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[k] += overlap * gp[k];
-        total += overlap;
-      }
-    }
+      for (int k = 0; k < 3; k++) acc[k] += overlap * gp[k];
+    });
     double sq = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; k++) sq += acc[k] * acc[k];
@@ -3282,48 +3289,29 @@ __device__ void variant_normal(const VariantCtx<T> &x, const float vertex[3], do
     for (int k = 0; k < 3; k++) nd[k] = acc[k] / norm;
     return;
   }
-  float normal[3];
-  double acc[3] = {0.0, 0.0, 0.0}, total = 0.0;
   if (x.held.img) {
     // the cached interpolator of txx:484: the point goes through the HELD image's geometry, the eight sites come from its
     // gradient image (I7), clamped to ITS extent (I5)
     Cell8 h;
     make_cell(x.held.geo, x.heldUnitP2I, x.held.n, p, h);
+    interpolate_literal(h, [&](unsigned, int sx, int sy, int sz, double overlap) {
+      const float *gp = x.held.img + 3 * (((size_t)sz * x.held.n[1] + sy) * x.held.n[0] + sx);
 #pragma unroll
-    for (unsigned counter = 0; counter < 8; counter++) {
-      double overlap = 1.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? h.d[k] : (1.0 - h.d[k]);
-      if (overlap != 0.0 && total != 1.0) {
-        const int sx = (counter & 1) ? h.hi[0] : h.lo[0], sy = (counter & 2) ? h.hi[1] : h.lo[1], sz = (counter & 4) ? h.hi[2] : h.lo[2];
-        const float *gp = x.held.img + 3 * (((size_t)sz * x.held.n[1] + sy) * x.held.n[0] + sx);
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[k] += overlap * (double)gp[k];
-        total += overlap;
-      }
-    }
+      for (int k = 0; k < 3; k++) acc[k] += overlap * (double)gp[k];
+    });
   } else {
+    // the shipped gradient, evaluated on the fly (K4e, k_point_normals, is this path with a view's Sampler)
     float G[8][3];
     typename SiteValue<T>::type Vd[8];
-    gather_cell<T, true>(x.s, x.geo, x.dirIdentity, c, G, Vd);
+    gather_cell<T, /*LITERAL*/ true>(x.s, x.geo, x.dirIdentity, c, G, Vd);           // I6
+    interpolate_literal(c, [&](unsigned counter, int, int, int, double overlap) {   // I7
 #pragma unroll
-    for (unsigned counter = 0; counter < 8; counter++) {
-      double overlap = 1.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
-      if (overlap != 0.0 && total != 1.0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[k] += overlap * (double)G[counter][k];
-        total += overlap;
-      }
-    }
+      for (int k = 0; k < 3; k++) acc[k] += overlap * (double)G[counter][k];
+    });
   }
-  double sq = 0.0;
+  normalize_narrowed(acc, normal);                                                  // I8
 #pragma unroll
-  for (int k = 0; k < 3; k++) { normal[k] = (float)acc[k]; const double e = (double)normal[k]; sq += e * e; }
-  const double norm = sqrt(sq);
-#pragma unroll
-  for (int k = 0; k < 3; k++) nd[k] = (double)(float)((double)normal[k] / norm);
+  for (int k = 0; k < 3; k++) nd[k] = (double)normal[k];
 }
 
 // I5: the interpolated pixel value at `q` (txx:368-369, 424)
@@ -3332,19 +3320,60 @@ __device__ double variant_value(const VariantCtx<T> &x, const float q[3]) {
   const double p[3] = {(double)q[0], (double)q[1], (double)q[2]};
   Cell8 c;
   make_cell(x.geo, x.unitP2I, x.n, p, c);
-  double value = 0.0, total = 0.0;
-#pragma unroll
-  for (unsigned counter = 0; counter < 8; counter++) {
-    double overlap = 1.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
-    if (overlap != 0.0 && total != 1.0) {
-      const T pix = x.s.at((counter & 1) ? c.hi[0] : c.lo[0], (counter & 2) ? c.hi[1] : c.lo[1], (counter & 4) ? c.hi[2] : c.lo[2]);
-      value += overlap * (double)pix;
-      total += overlap;
-    }
-  }
+  double value = 0.0;
+  interpolate_literal(c, [&](unsigned, int sx, int sy, int sz, double overlap) { value += overlap * (double)x.s.at(sx, sy, sz); });
   return value;
+}
+
+template <class T>
+__device__ __forceinline__ VariantCtx<T> make_variant_ctx(const T *vox, const Grid &g, const Geo &geo, const Params &prm, int dirIdentity,
+                                                          const double *gimg, const HeldGradient &held) {
+  VariantCtx<T> x;
+  x.s = make_sampler<T>(vox, g);
+  x.geo = geo;
+  x.dirIdentity = dirIdentity != 0;
+  x.unitP2I = is_identity3(geo.p2i);
+  x.n[0] = g.nx; x.n[1] = g.ny; x.n[2] = (int)g.gnz;
+  x.iso = (double)iso_as<T>(prm.iso, prm.isoInt);
+  x.gimg = gimg;
+  x.held = held;
+  x.heldUnitP2I = is_identity3(held.geo.p2i);
+  return x;
+}
+
+// The default branch of the walk (txx:439-474) to the letter, one lane per vertex: the refilling kernel k_project is this
+// branch with the shipped gradient and the linear value.  valueAt(vertex) is the interpolated value of txx:455.
+struct WalkEnd { unsigned passes; bool byThr, bySteps; };
+
+template <class T, class V>
+__device__ __forceinline__ void walk_default(const VariantCtx<T> &x, const Params &prm, V &&valueAt, float vertex[3], WalkEnd &end) {
+  double normal[3];
+  double step = prm.step;
+  unsigned numberOfSteps = 0;
+  for (;;) {
+    end.passes++;
+    variant_normal(x, vertex, normal);                                          // txx:451-452
+    const double value = valueAt(vertex);                                       // txx:455
+    if (fabs(value - x.iso) < prm.thr) { end.byThr = true; break; }             // txx:456-460
+    const double sign = (value < x.iso) ? +1.0 : -1.0;                          // txx:463
+#pragma unroll
+    for (int k = 0; k < 3; k++) vertex[k] = (float)((double)vertex[k] + (normal[k] * sign * step));   // txx:464-467
+    step *= prm.relax;                                                          // txx:468
+    if (numberOfSteps++ > prm.max_steps) { end.bySteps = true; break; }         // txx:469-473
+  }
+}
+
+// The statistics of a lane-per-vertex walk, wave-summed: one atomic per wave and counter.  Both ways a walk ends are counted
+// here (k_project counts the rare one only): the host checks they add up to n_points.  Every lane of the wave calls it.
+__device__ __forceinline__ void walk_statistics(Totals *tot, const WalkEnd &end) {
+  const int lane = threadIdx.x & 63;
+  unsigned sum = end.passes;
+#pragma unroll
+  for (int sft = 32; sft > 0; sft >>= 1) sum += __shfl_down(sum, sft, 64);
+  if (lane == 0 && sum) atomicAdd(&tot->iters, (u64)sum);
+  const u64 nThr = __ballot(end.byThr), nSteps = __ballot(end.bySteps);
+  if (lane == 0 && nThr) atomicAdd(&tot->stopThr, (u64)__popcll(nThr));
+  if (lane == 0 && nSteps) atomicAdd(&tot->stopSteps, (u64)__popcll(nSteps));
 }
 
 template <class T>
@@ -3352,48 +3381,22 @@ __global__ __launch_bounds__(256) void k_project_variant(const T *__restrict__ v
                                                          float *__restrict__ points, u64 nPoints, u64 nGhost,
                                                          Totals *__restrict__ tot, const double *__restrict__ gimg,
                                                          HeldGradient held) {
-  const int lane = threadIdx.x & 63;
   const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned passes = 0;
-  bool byThr = false, bySteps = false;
+  WalkEnd end{0, false, false};
   // (a ghost vertex on the ghost slice's bottom plane is NaN and nobody's business here: see k_project)
   if (idx < nPoints && !(idx < nGhost && points[3 * idx] != points[3 * idx])) {
-    VariantCtx<T> x;
-    x.s = Sampler<T>{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-    x.geo = geo;
-    x.dirIdentity = dirIdentity != 0;
-    x.unitP2I = true;
-    for (int i = 0; i < 9; i++) x.unitP2I = x.unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
-    x.n[0] = g.nx; x.n[1] = g.ny; x.n[2] = (int)g.gnz;
-    x.iso = (double)iso_as<T>(prm.iso, prm.isoInt);
-    x.gimg = gimg;
-    x.held = held;
-    x.heldUnitP2I = true;
-    for (int i = 0; i < 9; i++) x.heldUnitP2I = x.heldUnitP2I && (held.geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
+    const VariantCtx<T> x = make_variant_ctx<T>(vox, g, geo, prm, dirIdentity, gimg, held);
     float vertex[3] = {points[3 * idx], points[3 * idx + 1], points[3 * idx + 2]};
     double normal[3];
     if (prm.variant == CUBERILLE_PROJECT_DEFAULT) {
-      // txx:439-474 to the letter (the refilling kernel k_project is this branch with the shipped gradient; here for the
-      // recursive-Gaussian one)
-      double step = prm.step;
-      unsigned numberOfSteps = 0;
-      for (;;) {
-        passes++;
-        variant_normal(x, vertex, normal);                                        // txx:451-452
-        const double value = variant_value(x, vertex);                            // txx:455
-        if (fabs(value - x.iso) < prm.thr) { byThr = true; break; }               // txx:456-460
-        const double sign = (value < x.iso) ? +1.0 : -1.0;                        // txx:463
-#pragma unroll
-        for (int k = 0; k < 3; k++) vertex[k] = (float)((double)vertex[k] + (normal[k] * sign * step));   // txx:464-467
-        step *= prm.relax;                                                        // txx:468
-        if (numberOfSteps++ > prm.max_steps) { bySteps = true; break; }           // txx:469-473
-      }
+      // (here for the recursive-Gaussian gradient and the held one)
+      walk_default(x, prm, [&](const float *q) { return variant_value(x, q); }, vertex, end);
     } else if (prm.variant == CUBERILLE_PROJECT_ADVANCED) {
       double step = prm.step;
       unsigned numberOfSteps = 0, swaps = 0;
       int previousi = -1;
       for (;;) {
-        passes++;
+        end.passes++;
         variant_normal(x, vertex, normal);                                        // txx:356-357
         float temp[2][3];
 #pragma unroll
@@ -3409,8 +3412,8 @@ __global__ __launch_bounds__(256) void k_project_variant(const T *__restrict__ v
         swaps += (unsigned)(previousi != i);                                      // txx:374
 #pragma unroll
         for (int k = 0; k < 3; k++) vertex[k] = i ? temp[1][k] : temp[0][k];      // txx:375
-        if ((i ? d1 : d0) < prm.thr) { byThr = true; break; }                     // txx:378-382
-        if (numberOfSteps++ > prm.max_steps) { bySteps = true; break; }           // txx:385-389
+        if ((i ? d1 : d0) < prm.thr) { end.byThr = true; break; }                 // txx:378-382
+        if (numberOfSteps++ > prm.max_steps) { end.bySteps = true; break; }       // txx:385-389
         if (swaps >= 5) break;                                                    // txx:392-396
       }
     } else {
@@ -3421,7 +3424,7 @@ __global__ __launch_bounds__(256) void k_project_variant(const T *__restrict__ v
       variant_normal(x, vertex, normal);                                          // txx:408-409
       for (double sign = -1.0; sign <= 1.0; sign += 2.0)                          // txx:412
         for (unsigned j = 1; j < prm.max_steps / 2; j++) {                        // txx:415
-          passes++;
+          end.passes++;
           const double d = (double)j / ((double)prm.max_steps / 2.0);             // txx:418
           float temp[3];
 #pragma unroll
@@ -3438,15 +3441,9 @@ __global__ __launch_bounds__(256) void k_project_variant(const T *__restrict__ v
       for (int k = 0; k < 3; k++) vertex[k] = best[k];                            // txx:437
     }
     points[3 * idx] = vertex[0]; points[3 * idx + 1] = vertex[1]; points[3 * idx + 2] = vertex[2];
-    if (idx < nGhost) { passes = 0; byThr = bySteps = false; }   // the statistics count owned vertices only
+    if (idx < nGhost) end = WalkEnd{0, false, false};   // the statistics count owned vertices only
   }
-  unsigned sum = passes;
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) sum += __shfl_down(sum, sft, 64);
-  if (lane == 0 && sum) atomicAdd(&tot->iters, (u64)sum);
-  const u64 nThr = __ballot(byThr), nSteps = __ballot(bySteps);
-  if (lane == 0 && nThr) atomicAdd(&tot->stopThr, (u64)__popcll(nThr));
-  if (lane == 0 && nSteps) atomicAdd(&tot->stopSteps, (u64)__popcll(nSteps));
+  walk_statistics(tot, end);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3744,48 +3741,16 @@ template <class T, class C>
 __global__ __launch_bounds__(256) void k_project_bspline(const T *__restrict__ vox, Grid g, Geo geo, Params prm, int dirIdentity,
                                                          float *__restrict__ points, u64 nPoints, Totals *__restrict__ tot,
                                                          const C *__restrict__ coef) {
-  const int lane = threadIdx.x & 63;
   const u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned passes = 0;
-  bool byThr = false, bySteps = false;
+  WalkEnd end{0, false, false};
   if (idx < nPoints) {
-    VariantCtx<T> x;
-    x.s = Sampler<T>{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-    x.geo = geo;
-    x.dirIdentity = dirIdentity != 0;
-    x.unitP2I = true;
-    for (int i = 0; i < 9; i++) x.unitP2I = x.unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
-    x.n[0] = g.nx; x.n[1] = g.ny; x.n[2] = (int)g.gnz;
-    x.iso = (double)iso_as<T>(prm.iso, prm.isoInt);
-    x.gimg = nullptr;
-    x.held = HeldGradient{};
-    x.heldUnitP2I = false;
+    const VariantCtx<T> x = make_variant_ctx<T>(vox, g, geo, prm, dirIdentity, nullptr, HeldGradient{});
     const int n[3] = {g.nx, g.ny, g.nzb};
     float vertex[3] = {points[3 * idx], points[3 * idx + 1], points[3 * idx + 2]};
-    double normal[3];
-    double step = prm.step;
-    unsigned numberOfSteps = 0;
-    for (;;) {
-      passes++;
-      variant_normal(x, vertex, normal);                                          // txx:451-452
-      const double value = bspline_value<C>(coef, geo, n, vertex);                // txx:455
-      if (fabs(value - x.iso) < prm.thr) { byThr = true; break; }                 // txx:456-460
-      const double sign = (value < x.iso) ? +1.0 : -1.0;                          // txx:463
-#pragma unroll
-      for (int k = 0; k < 3; k++) vertex[k] = (float)((double)vertex[k] + (normal[k] * sign * step));   // txx:464-467
-      step *= prm.relax;                                                          // txx:468
-      if (numberOfSteps++ > prm.max_steps) { bySteps = true; break; }             // txx:469-473
-    }
+    walk_default(x, prm, [&](const float *q) { return bspline_value<C>(coef, geo, n, q); }, vertex, end);
     points[3 * idx] = vertex[0]; points[3 * idx + 1] = vertex[1]; points[3 * idx + 2] = vertex[2];
   }
-  unsigned sum = passes;
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) sum += __shfl_down(sum, sft, 64);
-  if (lane == 0 && sum) atomicAdd(&tot->iters, (u64)sum);
-  // both ways a walk ends are counted here (k_project counts the rare one only): the host checks they add up to n_points
-  const u64 nThr = __ballot(byThr), nSteps = __ballot(bySteps);
-  if (lane == 0 && nThr) atomicAdd(&tot->stopThr, (u64)__popcll(nThr));
-  if (lane == 0 && nSteps) atomicAdd(&tot->stopSteps, (u64)__popcll(nSteps));
+  walk_statistics(tot, end);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3816,11 +3781,11 @@ __global__ __launch_bounds__(256) void k_point_normals(const T *__restrict__ vox
     if (!tot->go) return;
     nPoints = tot->totV;
   }
-  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
-  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
-  if constexpr (VIEW == VIEW_BAND) { s.lower = padD; s.upper = padI; s.inside = rowPitch; s.outside = slicePitch; }
+  const Sampler<T, VIEW> s = make_sampler<T, VIEW>(vox, g, padD, padI, rowPitch, slicePitch);
   const int n[3] = {g.nx, g.ny, (int)g.gnz};
+  // (is_identity3, interpolate_literal and normalize_narrowed, spelt out below as they have always stood: through any one of
+  //  the three helpers the compiler allocates this kernel's registers differently, and five of its forty instantiations drop
+  //  an occupancy step)
   bool unitP2I = true;
 #pragma unroll
   for (int i = 0; i < 9; i++) unitP2I = unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
@@ -3865,8 +3830,8 @@ __global__ __launch_bounds__(256) void k_point_normals(const T *__restrict__ vox
 // its voxel -- quads follow raster order, so the lanes of a wave read from a few rows -- and one store at out[q] (TRI: the
 // pair as one store of 2 sizeof(T) <= 16 bytes).  No LDS, no atomics, nothing written but that.
 // I is the view's FRAME before any band mapping: VIEW_WHOLE reads the buffer (it serves cuberille_set_band too: the caller's
-// raw pixel, never Sampler::map), VIEW_BORDER goes through at_buffer (a ring voxel yields the constant, nothing outside the
-// caller's buffer is addressed), VIEW_REGION through the buffer's pitches.  A whole volume (the host layer offers nothing
+// raw pixel, never Sampler::map), VIEW_BORDER yields the constant at a ring voxel (nothing outside the caller's buffer is
+// addressed), VIEW_REGION goes through the buffer's pitches: Sampler::frame.  A whole volume (the host layer offers nothing
 // else with the setting): z of locate_quad is the buffer's slice.  dyn: the count and the go flag as k_emit_cells reads them.
 // ---------------------------------------------------------------------------------------------
 template <class T> struct alignas(2 * sizeof(T)) PixelPair { T a, b; };
@@ -3886,12 +3851,9 @@ __global__ __launch_bounds__(256) void k_cell_pixels(const T *__restrict__ vox, 
   const u64 Q0 = a.tot->Q0;
   int x, y, z = 0, f;
   if (!locate_quad(a, g, nwords, q, q < nQ, Q0, x, y, z, f)) return;
-  Sampler<T, VIEW> s{vox, g.nx, g.ny, g.nzb, (int)g.zglob0, (int)g.gnz};
-  if constexpr (VIEW == VIEW_BORDER) s.ring = iso_as<T>(padD, padI);
-  if constexpr (VIEW == VIEW_REGION) { s.rowS = rowPitch; s.sliceS = slicePitch; }
-  T v;
-  if constexpr (VIEW == VIEW_BORDER) v = s.at_buffer(x, y, z);
-  else v = s.at(x, y, z);
+  const Sampler<T, VIEW> s = make_sampler<T, VIEW>(vox, g, padD, padI, rowPitch, slicePitch);
+  // (z is the frame's slice already; the forms without a ring keep the clamp they have always passed it through)
+  const T v = s.frame(x, y, VIEW == VIEW_BORDER ? z : s.zlocal(z));
   if constexpr (TRI) reinterpret_cast<PixelPair<T> *>(out)[q] = PixelPair<T>{v, v};
   else out[q] = v;
 }
@@ -4328,6 +4290,31 @@ static hipError_t by_pixel_type(int pt, F &&fn) {
   return hipErrorInvalidValue;
 }
 
+// fn(std::integral_constant<int, VIEW>()) for a ViewKind
+template <class F>
+static void by_view(int kind, F &&fn) {
+  if (kind == VIEW_BAND) fn(std::integral_constant<int, VIEW_BAND>());
+  else if (kind == VIEW_BORDER) fn(std::integral_constant<int, VIEW_BORDER>());
+  else if (kind == VIEW_REGION) fn(std::integral_constant<int, VIEW_REGION>());
+  else fn(std::integral_constant<int, VIEW_WHOLE>());
+}
+
+// a (double, integer) pair in the pixel type, as iso_as does on the device
+template <class T>
+static T value_as(double d, long long i) {
+  if constexpr (std::is_integral<T>::value && sizeof(T) == 8) return (T)i;
+  else return (T)d;
+}
+
+// fn(a0, a1, a2, a3): a view's payload as the four trailing arguments of its kernels, in the types of WalkArg<T, VIEW, .>
+template <class T, int VIEW, class F>
+static void with_view_payload(const View &v, F &&fn) {
+  if constexpr (VIEW == VIEW_BAND)
+    fn(value_as<T>(v.bandV[0], v.bandVi[0]), value_as<T>(v.bandV[1], v.bandVi[1]), value_as<T>(v.bandV[2], v.bandVi[2]),
+       value_as<T>(v.bandV[3], v.bandVi[3]));
+  else fn(v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
+}
+
 static inline unsigned grid_for(u64 threads, unsigned block, unsigned cap) {
   u64 b = (threads + block - 1) / block;
   if (b < 1) b = 1;
@@ -4398,13 +4385,6 @@ static void launch_row_sweep(const Rows &rows, u64 bytes, const Workspace &w, co
   const u64 nspans = (nwordsAll + SPAN_WORDS - 1) / SPAN_WORDS;
   hipLaunchKernelGGL((k_classify_span_rows<T, Rows, BAND>), dim3(whole_rounds(nspans, tn)), dim3(256), 0, s, rows, w.bits + t0, nspans, nwordsAll,
                      (u32)(t0 / (u64)g.W), g.W, iso, isoI, w.sliceOcc);
-}
-
-// a (double, integer) pair in the pixel type, as iso_as does on the device
-template <class T>
-static T value_as(double d, long long i) {
-  if constexpr (std::is_integral<T>::value && sizeof(T) == 8) return (T)i;
-  else return (T)d;
 }
 
 // cuberille_set_band: what the band instantiations of the sweep take.  The image B holds two values, so !(B(u) < iso) is
@@ -4775,7 +4755,8 @@ __global__ __launch_bounds__(256) void k_gradient_image(const T *__restrict__ vo
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nvox) return;
   const int x = (int)(i % (size_t)g.nx), y = (int)((i / (size_t)g.nx) % (size_t)g.ny), z = (int)(i / ((size_t)g.nx * g.ny));
-  const Sampler<T> s{vox, g.nx, g.ny, g.nzb, 0, g.nzb};
+  g.zglob0 = 0; g.gnz = g.nzb;                   // the buffer is the whole image here
+  const Sampler<T> s = make_sampler<T>(vox, g);
   float gr[3];
   gradient_at(s, geo, dirIdentity != 0, x, y, z, (float)vox[i], gr);
   out[3 * i] = gr[0]; out[3 * i + 1] = gr[1]; out[3 * i + 2] = gr[2];
@@ -4785,8 +4766,7 @@ hipError_t launch_gradient_image(int pixel_type, const Workspace &w, const Grid 
   const size_t nvox = (size_t)g.nx * g.ny * g.nzb;
   if (nvox == 0) return hipSuccess;
   if ((nvox + 255) / 256 > 0x7fffffffull) return hipErrorInvalidValue;
-  int dirIdentity = 1;
-  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  const int dirIdentity = is_identity3(geo.dir);
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
     hipLaunchKernelGGL((k_gradient_image<T>), dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, s, (const T *)w.vox, g, geo,
@@ -4801,8 +4781,7 @@ hipError_t launch_gradient_image(int pixel_type, const Workspace &w, const Grid 
 hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, const Params &p, u64 nPoints,
                           u64 nGhost, const Tuning &tn, int mode, int dyn, hipStream_t s) {
   if (nPoints == 0) return hipSuccess;
-  int dirIdentity = 1;
-  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  const int dirIdentity = is_identity3(geo.dir);
   if (p.variant != CUBERILLE_PROJECT_DEFAULT || p.gradVariant != 0 || (w.held && w.held->img))
     return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
       typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
@@ -4887,11 +4866,9 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     const int view = v.kind == VIEW_REGION && !v.pitched && geo.istart[0] == 0 && geo.istart[1] == 0 && geo.istart[2] == 0 ? (int)VIEW_WHOLE : v.kind;
     const int at0 = view == VIEW_BORDER ? -1 : 0;
     bool diag = dirIdentity != 0 && (view == VIEW_REGION || (geo.istart[0] == at0 && geo.istart[1] == at0 && geo.istart[2] == at0)) && tn.proj_ident != 0;
-    bool unit = diag;
-    for (int i = 0; i < 9; i++) {
+    const bool unit = diag && is_identity3(geo.p2i);
+    for (int i = 0; i < 9; i++)
       if (i % 4 != 0) diag = diag && geo.p2i[i] == 0.0;
-      unit = unit && geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0);
-    }
     const int geom = unit ? 2 : diag ? 1 : 0;
     // a border, a region and a band belong to a whole volume with every slice in the buffer: MODE 0, the only one offered
     // with them (resolve_view)
@@ -4899,17 +4876,12 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
     // one instantiation per (MODE, GEOM, VIEW); the four trailing arguments are the view's payload in the types of WalkArg
     auto launch = [&](auto modeTag, auto geomTag, auto viewTag) {
       constexpr int MODE = decltype(modeTag)::value, GEOM = decltype(geomTag)::value, VIEW = decltype(viewTag)::value;
-      if constexpr (MODE == 0 || VIEW == VIEW_WHOLE) {
-        auto go = [&](auto a0, auto a1, auto a2, auto a3) {
+      if constexpr (MODE == 0 || VIEW == VIEW_WHOLE)
+        with_view_payload<T, VIEW>(v, [&](auto a0, auto a1, auto a2, auto a3) {
           hipLaunchKernelGGL((k_project<T, MODE, GEOM, VIEW>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, p, dirIdentity,
                              w.points, nPoints, nGhost, chunk, tn.proj_refill, xcd, tn.proj_literal, w.totals, w.escList,
                              w.escCap, dyn, a0, a1, a2, a3);
-        };
-        if constexpr (VIEW == VIEW_BAND)
-          go(value_as<T>(v.bandV[0], v.bandVi[0]), value_as<T>(v.bandV[1], v.bandVi[1]), value_as<T>(v.bandV[2], v.bandVi[2]),
-             value_as<T>(v.bandV[3], v.bandVi[3]));
-        else go(v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
-      }
+        });
     };
     auto by_geom = [&](auto modeTag, auto viewTag) {
       if (geom == 2) launch(modeTag, std::integral_constant<int, 2>(), viewTag);
@@ -4921,10 +4893,7 @@ hipError_t launch_project(int pixel_type, const Workspace &w, const Grid &g, con
       else if (mode == 2) by_geom(std::integral_constant<int, 2>(), viewTag);
       else by_geom(std::integral_constant<int, 0>(), viewTag);
     };
-    if (view == VIEW_BAND) by_mode(std::integral_constant<int, VIEW_BAND>());
-    else if (view == VIEW_BORDER) by_mode(std::integral_constant<int, VIEW_BORDER>());
-    else if (view == VIEW_REGION) by_mode(std::integral_constant<int, VIEW_REGION>());
-    else by_mode(std::integral_constant<int, VIEW_WHOLE>());
+    by_view(view, by_mode);
     return hipGetLastError();
   });
 }
@@ -4987,8 +4956,7 @@ hipError_t launch_bspline_prefilter(int pixel_type, const void *vox, const Grid 
 hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, const Params &p, u64 nPoints,
                                   const void *coef, int coefBits, hipStream_t s) {
   if (nPoints == 0) return hipSuccess;
-  int dirIdentity = 1;
-  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  const int dirIdentity = is_identity3(geo.dir);
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
     if (coefBits == 64)
@@ -5007,27 +4975,17 @@ hipError_t launch_project_bspline(int pixel_type, const Workspace &w, const Grid
 hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &g, const Geo &geo, float *normals, u64 nPoints,
                                 int dyn, hipStream_t s) {
   if (nPoints == 0) return hipSuccess;
-  int dirIdentity = 1;
-  for (int i = 0; i < 9; i++) if (geo.dir[i] != ((i % 4 == 0) ? 1.0 : 0.0)) dirIdentity = 0;
+  const int dirIdentity = is_identity3(geo.dir);
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
-    const View &v = w.view;
     const unsigned blocks = grid_for(nPoints, 256, 0x7fffffffu);
-    auto launch = [&](auto viewTag) {
+    by_view(w.view.kind, [&](auto viewTag) {
       constexpr int VIEW = decltype(viewTag)::value;
-      auto go = [&](auto a0, auto a1, auto a2, auto a3) {
+      with_view_payload<T, VIEW>(w.view, [&](auto a0, auto a1, auto a2, auto a3) {
         hipLaunchKernelGGL((k_point_normals<T, VIEW>), dim3(blocks), dim3(256), 0, s, (const T *)w.vox, g, geo, dirIdentity,
                            (const float *)w.points, normals, nPoints, (const Totals *)w.totals, dyn, a0, a1, a2, a3);
-      };
-      if constexpr (VIEW == VIEW_BAND)
-        go(value_as<T>(v.bandV[0], v.bandVi[0]), value_as<T>(v.bandV[1], v.bandVi[1]), value_as<T>(v.bandV[2], v.bandVi[2]),
-           value_as<T>(v.bandV[3], v.bandVi[3]));
-      else go(v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
-    };
-    if (v.kind == VIEW_BAND) launch(std::integral_constant<int, VIEW_BAND>());
-    else if (v.kind == VIEW_BORDER) launch(std::integral_constant<int, VIEW_BORDER>());
-    else if (v.kind == VIEW_REGION) launch(std::integral_constant<int, VIEW_REGION>());
-    else launch(std::integral_constant<int, VIEW_WHOLE>());
+      });
+    });
     return hipGetLastError();
   });
 }
@@ -5045,19 +5003,16 @@ hipError_t launch_cell_pixels(int pixel_type, const Workspace &w, const Grid &g,
   const dim3 grid(grid_for(nQ, 256, 0)), block(256);
   return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
     typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
-    const View &v = w.view;
-    auto launch = [&](auto viewTag) {
+    by_view(w.view.kind == VIEW_BAND ? (int)VIEW_WHOLE : w.view.kind, [&](auto viewTag) {
       constexpr int VIEW = decltype(viewTag)::value;
-      if (triangles)
-        hipLaunchKernelGGL((k_cell_pixels<T, VIEW, true>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out,
-                           v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
-      else
-        hipLaunchKernelGGL((k_cell_pixels<T, VIEW, false>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out,
-                           v.padValue, v.padValueInt, v.rowPitch, v.slicePitch);
-    };
-    if (v.kind == VIEW_BORDER) launch(std::integral_constant<int, VIEW_BORDER>());
-    else if (v.kind == VIEW_REGION) launch(std::integral_constant<int, VIEW_REGION>());
-    else launch(std::integral_constant<int, VIEW_WHOLE>());
+      if constexpr (VIEW != VIEW_BAND)
+        with_view_payload<T, VIEW>(w.view, [&](auto a0, auto a1, auto a2, auto a3) {
+          if (triangles)
+            hipLaunchKernelGGL((k_cell_pixels<T, VIEW, true>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out, a0, a1, a2, a3);
+          else
+            hipLaunchKernelGGL((k_cell_pixels<T, VIEW, false>), grid, block, 0, s, (const T *)w.vox, a, g, nwords, nQ, (T *)out, a0, a1, a2, a3);
+        });
+    });
     return hipGetLastError();
   });
 }

@@ -8,7 +8,10 @@ A kernel is matched by its canonical name: the kernel and its template arguments
 kept here.  The row sweeps: the parent's six kernels by source (k_classify_span_rows / _pad_span_rows / _region_span_rows,
 k_classify_rows / _pad_words / _region_words) are k_classify_span_rows<T, Rows<T>, BAND> and k_classify_words<T, Rows<T>, BAND>
 here (ROW_SWEEPS; result: profiles/span_rows_isa.txt, where those 80 are meant to differ).  The source views: the walk's three trailing bools of the parent (PAD, REGION, BAND, at most one true)
-are its one VIEW value here (0 whole, 1 border, 2 region, 3 band).  Results: profiles/view_isa.txt, profiles/point_normals_isa.txt; the comparisons of the
+are its one VIEW value here (0 whole, 1 border, 2 region, 3 band).  Results: profiles/view_isa.txt, profiles/point_normals_isa.txt,
+profiles/view_sampler_isa.txt (the vertex side on one Sampler<T, VIEW>: no rename rule; every k_project, k_point_normals,
+k_cell_pixels and k_gradient_image and everything outside the vertex side identical, the two lane-per-vertex walks
+k_project_variant and k_project_bspline meant to differ; their registers in profiles/view_sampler_resource_usage.txt); the comparisons of the
 changes that added the border, the region and the band (region_walk_isa.txt, band_isa.txt) were made by this script's
 predecessors, which git history keeps (profiles/README.md).
 """
