@@ -295,7 +295,8 @@ public:
    *  InsideBandOn() it is the input's RAW pixel (which label), with PadBorderOn() the padded image's, with SetExtractionRegion
    *  the box's.  Offered on every route of a single device, the host walk included (its triangles repeat the quad's value on the
    *  host); with SetDevices of more than one device the library refuses and Update() throws an itk::ExceptionObject that says
-   *  so.  Default off: the array is empty and the mesh has no cell-data container. */
+   *  so.  Default off: the array is empty and the mesh has no cell-data container (nor has a mesh without cells, the switch on:
+   *  itk::Mesh makes the container with the first SetCellData( id, value )). */
   itkGetMacro(SavePixelAsCellData, bool);
   itkSetMacro(SavePixelAsCellData, bool);
   itkBooleanMacro(SavePixelAsCellData);
@@ -344,6 +345,16 @@ public:
   const std::vector<int> &GetDevices() const { return m_Devices; }
   unsigned int GetLastNumberOfSlabs() const { return m_LastNumberOfSlabs; }
 
+  // THE ACCESSORS AFTER A THROWING Update() -- a refused combination of switches, a region outside the buffer, a failure of the
+  // library: GetPointNormals(), GetCellPixels(), GetPointComponents(), GetCellComponents() and GetComponentCellCounts() are all
+  // empty and GetNumberOfComponents() is 0, whatever the update before left there: nothing of an earlier mesh is handed out
+  // beside an output the pipeline has re-initialised.  The filter object stays usable: the next Update() with an accepted
+  // combination gives what a fresh object would.
+
+  /** Not in the reference: the image description and the extraction region as a box of the buffer (all zero: none) that
+   *  Update() would hand the library for the current input and SetExtractionRegion; false when nothing is buffered.  Needs no GPU. */
+  bool DescribeInput(::cuberille_image_desc &desc, int64_t boxStart[3], int64_t boxSize[3]);
+
 protected:
   CuberilleImageToMeshFilter();
   ~CuberilleImageToMeshFilter();
@@ -385,6 +396,7 @@ private:
   std::vector<uint64_t> m_ComponentCellCounts;
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
+  void ClearAttributeOutputs();               // the five vectors above, emptied: how every Update() begins and how a throwing one ends
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them
   // SetExtractionRegion as a position in the buffer `desc` describes: ITK index - the buffer's start index (all zero: none)
   void BufferBox(const ::cuberille_image_desc &desc, int64_t start[3], int64_t size[3]) const;

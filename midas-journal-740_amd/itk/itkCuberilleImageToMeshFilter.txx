@@ -672,6 +672,14 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   const unsigned int Dim = InputImageType::ImageDimension;
   if (Dim != 3) itkExceptionMacro(<< "the cuberille path is three-dimensional");
   if (cuberille_detail::PixelCode<InputPixelType>::Value < 0) itkExceptionMacro(<< "unsupported pixel type");
+  // One rule for what the accessors hold when Update() throws, whichever line throws: nothing.  GetPointNormals(), GetCellPixels() and
+  // the three component vectors are emptied before the first refusal, and emptied again by whatever leaves this function early.
+  struct EmptyUnlessDone
+    {
+    Self *filter; bool done;
+    ~EmptyUnlessDone() { if (!done) filter->ClearAttributeOutputs(); }
+    } outputs = {this, false};
+  this->ClearAttributeOutputs();
   if (!m_DevicesError.empty()) itkExceptionMacro(<< m_DevicesError);
   // the B-spline interpolator of order 3 walks on the device where the library offers it (SetBSplineOnDevice); any other
   // TInterpolator than the linear one the kernels implement: topology and lattice points on the GPU, the walk on the host
@@ -718,7 +726,6 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "an implied border (PadBorderOn / cuberille_set_border) is not offered with an interpolator that takes "
                          "the host walk: the caller's interpolator object is bound to the unpadded image");
 
-  m_PointNormals.clear();
   if (m_GeneratePointNormals && hostWalk)
     itkExceptionMacro(<< "point normals (GeneratePointNormalsOn / cuberille_set_point_normals) are not offered with an interpolator "
                          "that takes the host walk: the library never sees the final vertices");
@@ -841,7 +848,6 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_normals_download(m_Context, m_PointNormals.empty() ? 0 : &m_PointNormals[0]) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_normals_download: " << cuberille_last_error(m_Context));
     }
-  m_CellPixels.clear();
   if (m_SavePixelAsCellData)                  // (the single context: a group has refused above)
     {
     m_CellPixels.resize(static_cast<size_t>(res.n_cells));
@@ -849,9 +855,6 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
                                        m_CellPixels.size() * sizeof(InputPixelType)) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_cell_pixels_download: " << cuberille_last_error(m_Context));
     }
-  m_PointComponents.clear();
-  m_CellComponents.clear();
-  m_ComponentCellCounts.clear();
   if (components)                             // (the single context: a group has refused above)
     {
     uint64_t nComponents = 0;
@@ -924,6 +927,26 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (grouped) (void)cuberille_group_release_host_mesh(m_Group);
     else (void)cuberille_release_host_mesh(m_Context);
     }
+  outputs.done = true;
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::ClearAttributeOutputs()
+{
+  m_PointNormals.clear();
+  m_CellPixels.clear();
+  m_PointComponents.clear();
+  m_CellComponents.clear();
+  m_ComponentCellCounts.clear();
+}
+
+template <class TInputImage, class TOutputMesh, class TInterpolator>
+bool CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::DescribeInput(::cuberille_image_desc &desc, int64_t boxStart[3],
+                                                                                       int64_t boxSize[3])
+{
+  const bool any = cuberille_detail::DescribeImage(Superclass::GetInput(0), desc);
+  this->BufferBox(desc, boxStart, boxSize);
+  return any;
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>

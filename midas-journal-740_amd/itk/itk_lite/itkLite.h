@@ -668,6 +668,71 @@ protected:
   CellsAllocationMethodType m_CellsAllocationMethod;
 };
 
+namespace lite {
+
+// the 3x3 inverse by cofactors (ITK: vnl's inverse of m_IndexToPhysicalPoint).  The same formula, operation for operation,
+// as the library uses (csrc/cuberille_api.hip, invert3), so that all sides divide by the same doubles.
+inline void Invert3(const double m[9], double inv[9]) {
+  const double c00 = m[4] * m[8] - m[5] * m[7];
+  const double c01 = m[5] * m[6] - m[3] * m[8];
+  const double c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+  inv[0] = c00 / det;
+  inv[1] = (m[2] * m[7] - m[1] * m[8]) / det;
+  inv[2] = (m[1] * m[5] - m[2] * m[4]) / det;
+  inv[3] = c01 / det;
+  inv[4] = (m[0] * m[8] - m[2] * m[6]) / det;
+  inv[5] = (m[2] * m[3] - m[0] * m[5]) / det;
+  inv[6] = c02 / det;
+  inv[7] = (m[1] * m[6] - m[0] * m[7]) / det;
+  inv[8] = (m[0] * m[4] - m[1] * m[3]) / det;
+}
+
+// What both linear interpolators share (I4, I5): ImageBase::TransformPhysicalPointToContinuousIndex in double, then per axis
+// the floor, the distance to it and the two neighbour indices clamped into the buffered region.  A coordinate that is not
+// a number takes the region's first index (quirk Q4: a vertex gone NaN must still read inside the buffer).
+template <class TImage> class LinearNeighbourhood {
+public:
+  enum { N = TImage::ImageDimension };
+  void SetImage(const TImage *image) {
+    for (unsigned int k = 0; k < N; k++) {
+      m_Lo[k] = image->GetBufferedRegion().GetIndex()[k];
+      m_Hi[k] = m_Lo[k] + static_cast<long>(image->GetBufferedRegion().GetSize()[k]) - 1;
+      m_Origin[k] = image->GetOrigin()[k];
+    }
+    double i2p[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};      // (an image of fewer dimensions: the unit rows stay)
+    for (unsigned int r = 0; r < N && r < 3; r++)
+      for (unsigned int c = 0; c < N && c < 3; c++) i2p[r * 3 + c] = image->GetDirection()[r][c] * image->GetSpacing()[c];
+    Invert3(i2p, m_P2I);
+  }
+  // lower[k], upper[k]: the clamped neighbour indices; distance[k]: ci - floor(ci)
+  template <class TPoint> void Locate(const TPoint &point, long lower[], long upper[], double distance[]) const {
+    double cv[N], ci[N];
+    for (unsigned int k = 0; k < N; k++) cv[k] = static_cast<double>(point[k]) - m_Origin[k];
+    for (unsigned int r = 0; r < N; r++) {
+      double sum = 0.0;
+      for (unsigned int c = 0; c < N; c++) sum += m_P2I[r * 3 + c] * cv[c];
+      ci[r] = sum;
+    }
+    for (unsigned int k = 0; k < N; k++) {
+      const double base = std::floor(ci[k]);
+      distance[k] = ci[k] - base;
+      lower[k] = Clamp(base, k);
+      upper[k] = Clamp(base + 1.0, k);
+    }
+  }
+private:
+  long Clamp(double b, unsigned int k) const {
+    if (!(b >= static_cast<double>(m_Lo[k]))) return m_Lo[k];
+    if (b >= static_cast<double>(m_Hi[k])) return m_Hi[k];
+    return static_cast<long>(b);
+  }
+  long m_Lo[N], m_Hi[N];
+  double m_Origin[N], m_P2I[9];
+};
+
+}  // namespace lite
+
 // declared so that the driver's typedefs and includes resolve; never instantiated
 // (CuberilleTest01.cxx:23-26 compiles those pipelines out)
 template <class TPixel, unsigned int VDimension = 3, class TTraits = void> class QuadEdgeMesh;
@@ -709,25 +774,21 @@ public:
   typedef double RealType;
   typedef Point<TCoordRep, TInputImage::ImageDimension> PointType;
   typedef typename TInputImage::IndexType IndexType;
-  void SetInputImage(const TInputImage *img) { m_Image = img; }
+  void SetInputImage(const TInputImage *img) { m_Image = img; if (img) m_Where.SetImage(img); }
   const TInputImage *GetInputImage() const { return m_Image; }
+  // ImageBase::TransformPhysicalPointToContinuousIndex through the direction matrix and the spacing (lite::LinearNeighbourhood:
+  // the library's own arithmetic, operation for operation), then the 2^N neighbours in counter order, clamped into the buffer
   OutputType Evaluate(const PointType &point) const {
     const unsigned int N = TInputImage::ImageDimension;
-    const typename TInputImage::RegionType &reg = m_Image->GetBufferedRegion();
-    double ci[8];
-    // identity-direction form of TransformPhysicalPointToContinuousIndex
-    for (unsigned int k = 0; k < N; k++) ci[k] = (point[k] - m_Image->GetOrigin()[k]) / m_Image->GetSpacing()[k];
-    long base[8];
-    double dist[8];
-    for (unsigned int k = 0; k < N; k++) { base[k] = (long)std::floor(ci[k]); dist[k] = ci[k] - (double)base[k]; }
+    long lower[N], upper[N];
+    double distance[N];
+    m_Where.Locate(point, lower, upper, distance);
     double value = 0.0, total = 0.0;
     for (unsigned int counter = 0; counter < (1u << N); counter++) {
       double overlap = 1.0;
       IndexType ni;
       for (unsigned int k = 0; k < N; k++) {
-        long lo = reg.GetIndex()[k], hi = lo + (long)reg.GetSize()[k] - 1, v;
-        if (counter & (1u << k)) { v = base[k] + 1; overlap *= dist[k]; } else { v = base[k]; overlap *= 1.0 - dist[k]; }
-        ni[k] = v < lo ? lo : (v > hi ? hi : v);
+        if (counter & (1u << k)) { ni[k] = upper[k]; overlap *= distance[k]; } else { ni[k] = lower[k]; overlap *= 1.0 - distance[k]; }
       }
       if (overlap) { value += overlap * static_cast<double>(m_Image->GetPixel(ni)); total += overlap; }
       if (total == 1.0) break;
@@ -737,6 +798,7 @@ public:
 protected:
   LinearInterpolateImageFunction() : m_Image(0) {}
   const TInputImage *m_Image;
+  lite::LinearNeighbourhood<TInputImage> m_Where;
 };
 
 #else

@@ -22,66 +22,7 @@ namespace itk {
 
 namespace lite {
 
-// the 3x3 inverse by cofactors (ITK: vnl's inverse of m_IndexToPhysicalPoint).  The same formula, operation for operation,
-// as the library uses (csrc/cuberille_api.hip, invert3), so that all sides divide by the same doubles.
-inline void Invert3(const double m[9], double inv[9]) {
-  const double c00 = m[4] * m[8] - m[5] * m[7];
-  const double c01 = m[5] * m[6] - m[3] * m[8];
-  const double c02 = m[3] * m[7] - m[4] * m[6];
-  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-  inv[0] = c00 / det;
-  inv[1] = (m[2] * m[7] - m[1] * m[8]) / det;
-  inv[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-  inv[3] = c01 / det;
-  inv[4] = (m[0] * m[8] - m[2] * m[6]) / det;
-  inv[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-  inv[6] = c02 / det;
-  inv[7] = (m[1] * m[6] - m[0] * m[7]) / det;
-  inv[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-}
-
-// What both linear interpolators share (I4, I5): ImageBase::TransformPhysicalPointToContinuousIndex in double, then per axis
-// the floor, the distance to it and the two neighbour indices clamped into the buffered region.  A coordinate that is not
-// a number takes the region's first index (quirk Q4: a vertex gone NaN must still read inside the buffer).
-template <class TImage> class LinearNeighbourhood {
-public:
-  enum { N = TImage::ImageDimension };
-  void SetImage(const TImage *image) {
-    for (unsigned int k = 0; k < N; k++) {
-      m_Lo[k] = image->GetBufferedRegion().GetIndex()[k];
-      m_Hi[k] = m_Lo[k] + static_cast<long>(image->GetBufferedRegion().GetSize()[k]) - 1;
-      m_Origin[k] = image->GetOrigin()[k];
-    }
-    double i2p[9];
-    for (unsigned int r = 0; r < 3; r++)
-      for (unsigned int c = 0; c < 3; c++) i2p[r * 3 + c] = image->GetDirection()[r][c] * image->GetSpacing()[c];
-    Invert3(i2p, m_P2I);
-  }
-  // lower[k], upper[k]: the clamped neighbour indices; distance[k]: ci - floor(ci)
-  template <class TPoint> void Locate(const TPoint &point, long lower[], long upper[], double distance[]) const {
-    double cv[N], ci[N];
-    for (unsigned int k = 0; k < N; k++) cv[k] = static_cast<double>(point[k]) - m_Origin[k];
-    for (unsigned int r = 0; r < N; r++) {
-      double sum = 0.0;
-      for (unsigned int c = 0; c < N; c++) sum += m_P2I[r * 3 + c] * cv[c];
-      ci[r] = sum;
-    }
-    for (unsigned int k = 0; k < N; k++) {
-      const double base = std::floor(ci[k]);
-      distance[k] = ci[k] - base;
-      lower[k] = Clamp(base, k);
-      upper[k] = Clamp(base + 1.0, k);
-    }
-  }
-private:
-  long Clamp(double b, unsigned int k) const {
-    if (!(b >= static_cast<double>(m_Lo[k]))) return m_Lo[k];
-    if (b >= static_cast<double>(m_Hi[k])) return m_Hi[k];
-    return static_cast<long>(b);
-  }
-  long m_Lo[N], m_Hi[N];
-  double m_Origin[N], m_P2I[9];
-};
+// (Invert3 and LinearNeighbourhood, which the linear interpolator of itkLite.h shares, are defined there)
 
 // the value of VectorLinearInterpolateImageFunction::Evaluate: components in double; narrows to the pixel's own component
 // type where the caller assigns it to one (I7: `normal = m_GradientInterpolator->Evaluate(vertex)`)

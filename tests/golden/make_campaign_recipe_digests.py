@@ -14,6 +14,9 @@ draw_case of the day, restricted to `keys`, and requires equality -- a new key i
 --out names the fixture: campaign_celldata_recipe_digests.json is the same record taken on the commit before the keep entered the
 recipe (070778d) -- it holds the keys of the second stream too (cell_pixels, components, drop_cell_rows, emit_offset,
 refusal_slab), which the keep's third stream must not move.
+--dropin writes campaign_dropin_recipe_digests.json instead, on the checkout of the day: the recipes of tests/fuzz_dropin.py
+-- fuzz_campaign's with the `dropin` entry from a stream of its own, np.random.default_rng([seed, case, 6]) -- for the same seeds
+and cases and the five slice_recipes(kind) lists of fuzz_dropin, each digested whole and as its `dropin` entry alone.
 Needs no GPU and no oracle."""
 import argparse
 import hashlib
@@ -42,8 +45,18 @@ def collect(fz, keys=None):
             {k: [digest(r, keys) for r in rs] for k, rs in by_kind.items()}, recipes)
 
 
+def collect_dropin(fd):
+    """The fixture of the drop-in campaign's stream: per seed and per slice, (digest of the recipe, digest of its dropin entry)."""
+    by_seed = {str(s): [fd.draw_case(s, c) for c in range(CASES)] for s in SEEDS}
+    by_kind = {kind: fd.slice_recipes(kind) for kind in fd.fz.KINDS}
+    both = lambda rs: [[digest(r), digest(r["dropin"])] for r in rs]                                 # noqa: E731
+    return dict(cases=CASES, seeds={s: both(rs) for s, rs in by_seed.items()}, slices={k: both(rs) for k, rs in by_kind.items()},
+                slice_seeds=dict(fd.SLICE), dropin_keys=sorted({k for rs in by_seed.values() for r in rs for k in r["dropin"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dropin", action="store_true", help="write campaign_dropin_recipe_digests.json from tests/fuzz_dropin.py")
     ap.add_argument("--tests", default=os.path.dirname(HERE), help="the tests/ directory of the checkout whose draw_case is recorded")
     ap.add_argument("--out", default="campaign_recipe_digests.json", help="the fixture's file name in tests/golden/")
     args = ap.parse_args()
@@ -52,6 +65,12 @@ def main():
     sys.path.insert(0, tests)
     import fuzz_campaign as fz
     assert os.path.dirname(os.path.abspath(fz.__file__)) == tests, fz.__file__
+    if args.dropin:
+        import fuzz_dropin as fd
+        with open(os.path.join(HERE, "campaign_dropin_recipe_digests.json"), "w") as f:
+            json.dump(collect_dropin(fd), f, indent=1)
+            f.write("\n")
+        return
     seeds, slices, recipes = collect(fz)
     keys = sorted({k for r in recipes for k in r})
     with open(os.path.join(HERE, os.path.basename(args.out)), "w") as f:

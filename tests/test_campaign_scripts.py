@@ -498,3 +498,192 @@ def test_compare_sees_one_bit(oracle):
         g["kept"][0]["null"] = tuple(i != at for i in range(3))
         with pytest.raises(AssertionError, match="null device pointers"):
             fz.compare(g, wn)
+
+
+# ---- the campaign through the C++ drop-in filter (tests/fuzz_dropin.py, tests/test_gpu_dropin_campaign.py) -------------------------
+_DROPIN = {}
+
+
+def _dropin_slice(oracle):
+    """{kind: (lines, references, script)} of the drop-in slice, prepared once per process (no GPU: the oracle and the numpy
+    references alone; the volumes are not written)."""
+    import fuzz_campaign as fz
+    import fuzz_dropin as fd
+    if not _DROPIN:
+        for kind in fz.KINDS:
+            _DROPIN[kind] = fd.prepare(oracle, fd.slice_recipes(kind))
+    return _DROPIN
+
+
+def test_the_dropin_stream_draws_what_its_digests_say():
+    """tests/golden/campaign_dropin_recipe_digests.json (tests/golden/make_campaign_recipe_digests.py --dropin): every recipe of
+    fuzz_dropin.draw_case for seeds 1 and 11, cases 0 .. 299, and of the five slice lists, whole and as its `dropin` entry alone.
+    The entry comes from a stream of its own -- the two older fixtures, which test_the_first_stream_draws_what_it_drew holds
+    fuzz_campaign.draw_case to, are not touched by it -- and a drop-in recipe is fuzz_campaign's recipe of the same (seed, case)
+    wherever the filter's route leaves the draw alone."""
+    import sys
+    import fuzz_campaign as fz
+    import fuzz_dropin as fd
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_campaign_recipe_digests as mk
+    finally:
+        sys.path.pop(0)
+    with open(os.path.join(ROOT, "tests", "golden", "campaign_dropin_recipe_digests.json")) as f:
+        fixture = json.load(f)
+    assert mk.collect_dropin(fd) == fixture
+    assert fixture["slice_seeds"] == fd.SLICE and sorted(fixture["slices"]) == sorted(fz.KINDS) and fixture["cases"] == 300
+    # pure, plain data, and the volume, the geometry and the parameters are the C ABI campaign's of the same (seed, case)
+    for case in range(60):
+        r = fd.draw_case(11, case)
+        assert r == fd.draw_case(11, case) == json.loads(json.dumps(r))
+        q = fz.draw_case(11, case, dict(route=r["route"], kind=r["kind"]))
+        for key in ("kind", "dtype", "field", "spacing", "origin", "direction", "index_start", "iso", "border", "region", "band", "bspline", "first"):
+            assert r.get(key) == q.get(key), (case, key)
+        assert r["kw"] == dict(q["kw"], variant=0) and set(r["dropin"]) == set(fixture["dropin_keys"])
+        assert r["keep"] is None or r["keep"]["rule"] in ("largest", "min_cells") and (r["keep"]["then"] is None or r["keep"]["rule"] == "largest" and r["keep"]["then"]["rule"] == "min_cells")
+
+
+def test_dropin_scripts_round_trip_through_the_binary(oracle):
+    """Recipe -> script -> the binary's mode without a GPU -> getters, for every line of the slice: every setter lands, the image
+    description and the buffer box are the recipe's, nan / inf / 64-bit values arrive exact -- and, on lines made for it, the
+    reference's clamps hold (the threshold against NumericTraits<InputPixelType>::max(), the step length, the relaxation factor,
+    the host-walk threads)."""
+    import copy
+    import fuzz_campaign as fz
+    import fuzz_dropin as fd
+    seen = {"inf": 0, "beyond_2_53": 0, "region": 0, "band": 0, "moved": 0, "keep_step": 0, "lines": 0}
+    for kind in fz.KINDS:
+        lines, _, script = _dropin_slice(oracle)[kind]
+        got, want = fd.parse_dry(fd.run_dry(script), lines), fd.dry_getters(lines)
+        assert len(got) == len(want) == len(lines) == len(script.splitlines())
+        for number, (g, w) in enumerate(zip(got, want)):
+            assert g == w, (kind, number, {k: (g.get(k), w.get(k)) for k in set(g) | set(w) if g.get(k) != w.get(k)})
+            s = lines[number]["settings"]
+            values = [s["iso"], s["border"]] + list(s["band"] or [])
+            seen["inf"] += any(isinstance(v, str) and "inf" in v for v in values)
+            seen["beyond_2_53"] += any(isinstance(v, int) and abs(v) > 2 ** 53 for v in values)
+            seen["region"] += s["region"] is not None and any(g["box"][:3])
+            seen["band"] += bool(s["bandon"])
+            seen["moved"] += any(s["start"])
+            seen["keep_step"] += s["step"] is None
+            seen["lines"] += 1
+    assert min(seen.values()) > 0, seen
+    # the clamps, on lines of the slice whose values are pushed past them
+    lines = copy.deepcopy([l for l in _dropin_slice(oracle)["whole"][0] if l["settings"]["dtype"] in ("uint8", "int8", "int64", "float32")][:8])
+    for i, line in enumerate(lines):
+        line["settings"].update(thr=[1000.0, -3.0, 1e30, 1e300][i % 4], step=[-5.0, 1e6, 0.0, 123.5][i % 4], relax=[2.0, -1.0, 1.0, 0.25][i % 4],
+                                threads=[0, 1000, 4, 256][i % 4], fresh=True)
+        if line["settings"]["dtype"] == "float32":       # (the slice draws no NaN: a ring of NaN, a band of -inf .. inf mapped to -0 and NaN)
+            line["settings"].update(border="nan", band=["-inf", "inf", -0.0, "nan"], bandon=True)
+    script = "\n".join(fd.script_line(n, l, "-", "-") for n, l in enumerate(lines)) + "\n"
+    got, want = fd.parse_dry(fd.run_dry(script), lines), fd.dry_getters(lines)
+    assert got == want
+    assert any(g["border"] == "nan" and g["band"] == [float("-inf").hex(), float("inf").hex(), (-0.0).hex(), "nan"] for g in got)
+    by = {l["settings"]["dtype"]: g for l, g in zip(lines, got) if l["settings"]["thr"] == 1000.0}
+    assert any(g["thr"] == float(hi).hex() for dt, hi in (("uint8", 255), ("int8", 127)) for g in [by.get(dt)] if g), by
+    assert {g["step"] for g in got} == {0.0.hex(), 100000.0.hex(), 123.5.hex()} and {g["relax"] for g in got} == {1.0.hex(), 0.0.hex(), 0.25.hex()}
+    assert {g["threads"] for g in got} == {1, 256, 4}
+
+
+def test_dropin_slice_conditions_hold_on_the_oracle(oracle):
+    """The seeded slice of tests/test_gpu_dropin_campaign.py from the recipes and the oracle alone: fuzz_dropin.slice_conditions,
+    the cap on empty reference meshes among them; the conditions see what they are there for."""
+    import fuzz_campaign as fz
+    import fuzz_dropin as fd
+    facts = []
+    for kind in fz.KINDS:
+        lines, refs, _ = _dropin_slice(oracle)[kind]
+        recipes = fd.slice_recipes(kind)
+        assert len(recipes) == 20 and [l["case"] for l in lines if l["sub"] == "main"] == list(range(20))
+        for i, r in enumerate(recipes):
+            assert (r["seed"], r["case"], r["kind"], r["dtype"]) == (fd.SLICE[kind], i, kind, np.dtype(fz.DTYPES[i % 10]).name)
+            buf = r["field"]["shape"]
+            box = r["region"]["size"][::-1] if kind == "region" else buf
+            assert max(box[:2]) <= 12 and np.prod(box) <= 30000 and np.prod(buf) <= 60000
+        mine = fd.slice_facts(lines, refs)
+        mains = [f for f in mine if f["sub"] == "main"]
+        assert len(mains) == 20 and 4 * sum(f["empty"] for f in mains) <= 20
+        facts += mine
+    assert fd.slice_conditions(facts) == []
+    gone = lambda keep: fd.slice_conditions([f for f in facts if keep(f)])                      # noqa: E731
+    assert any("hw_keep" in m for m in gone(lambda f: f["refusal"] != "hw_keep"))
+    assert any("followed by a full case" in m for m in gone(lambda f: not f["behind_throw"]))
+    assert any("fewer slices" in m for m in gone(lambda f: f["threw"] or f["devices"] <= f["slices"]))
+    assert any("2^53" in m for m in gone(lambda f: f["threw"] or not (f["host_walk"] and f["beyond_2_53"])))
+    assert any("sticks" in m for m in gone(lambda f: f["threw"] or not f["sticks"]))
+    assert any("switch stale" in m for m in gone(lambda f: "stale" not in f["turned_off"]))
+    assert any("single, then group" in m for m in gone(lambda f: f["threw"] or f["devices"] <= 1))
+    assert any("leaves nothing" in m for m in gone(lambda f: f["threw"] or not (f["ks"] and f["ks"][-1] == 0)))
+    assert any("host-walk path" in m for m in gone(lambda f: f["threw"] or not (f["interp"] == "inherit" and f["dtype"] == "uint64")))
+
+
+def test_the_dropin_comparer_sees_one_bit(oracle, tmp_path):
+    """fuzz_dropin.compare_line is the drop-in campaign's only judge.  From a fabricated output directory that equals the
+    reference (fuzz_dropin.write_reference: the files the binary writes) the comparison passes; one flipped bit in a point, a cell
+    id, a cell datum, a normal, a cell pixel, each of the three component rows, K, the slab count or the step length fails it, and
+    so do a dropped cell-data container, a cell of another arity, an Update() that threw, a refusal that was accepted and a
+    refusal with another text."""
+    import fuzz_dropin as fd
+    import pytest
+    import fuzz_campaign as fz
+    lines, refs, number = next((ls, rs, n) for ls, rs, _ in (_dropin_slice(oracle)[k] for k in fz.KINDS) for n, (l, r) in enumerate(zip(ls, rs))
+                               if not r["threw"] and l["settings"]["normals"] and l["settings"]["celldata"] and l["settings"]["components"]
+                               and len(r["cells"]) > 1 and r["K"] >= 1 and np.isfinite(r["normals"]).any())
+    line, ref = lines[number], refs[number]
+    s = line["settings"]
+    out = str(tmp_path)
+
+    def fresh():
+        fd.write_reference(ref, out, number, s["traits"])
+    fresh()
+    fd.compare_line(fd.read_line(out, number, s), ref)
+    base = os.path.join(out, "%d." % number)
+    finite = int(np.flatnonzero(np.isfinite(ref["normals"]).ravel())[0])
+    for name, byte, match in (("points", 4, "coordinates differ"), ("cells", 8, "cell topology"), ("celldata", 0, "cell data"), ("normals", 4 * finite, "normals"),
+                              ("pixels", 0, "cell pixels"), ("pcomp", 0, "pcomp"), ("ccomp", 0, "ccomp"), ("counts", 0, "counts"), ("arity", 1, "a cell of")):
+        fresh()
+        raw = bytearray(open(base + name, "rb").read())
+        raw[byte] ^= 1
+        open(base + name, "wb").write(bytes(raw))
+        with pytest.raises(AssertionError, match=match):
+            fd.compare_line(fd.read_line(out, number, s), ref)
+
+    def meta(change):
+        fresh()
+        text = open(base + "meta").read()
+        changed = change(text)
+        assert changed != text
+        open(base + "meta", "w").write(changed)
+    meta(lambda t: t.replace("K=%d" % ref["K"], "K=%d" % (ref["K"] ^ 1)))
+    with pytest.raises(AssertionError, match="GetNumberOfComponents"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace("slabs=1", "slabs=0"))
+    with pytest.raises(AssertionError, match="GetLastNumberOfSlabs"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace("step=" + fd._real(ref["step"]), "step=" + fd._real(np.nextafter(ref["step"], 1e9))))
+    with pytest.raises(AssertionError, match="GetProjectVertexStepLength"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace("celldata=1", "celldata=0"))
+    open(base + "celldata", "wb").close()
+    with pytest.raises(AssertionError, match="no cell-data container"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace("threw=0", "threw=1"))
+    with pytest.raises(AssertionError, match="threw"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    # a refusal: its own words pass; accepted, or refused in other words, fails; so does an accessor that is not empty
+    number = next(n for n, r in enumerate(refs) if r["threw"])
+    line, ref = lines[number], refs[number]
+    s, base = line["settings"], os.path.join(out, "%d." % number)
+    fresh()
+    fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace(ref["fragment"], "another reason to refuse"))
+    with pytest.raises(AssertionError, match="refused for another reason"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    meta(lambda t: t.replace("threw=1", "threw=0"))
+    with pytest.raises(AssertionError, match="was accepted"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
+    fresh()
+    np.zeros(3, np.float32).tofile(base + "normals")
+    with pytest.raises(AssertionError, match="normals"):
+        fd.compare_line(fd.read_line(out, number, s), ref)
