@@ -1151,9 +1151,11 @@ int cuberille_minimum_halo(const cuberille_image_desc *img, const cuberille_para
     // slices floor - 1 .. floor + 2 (gradient ring).  Vertices that matter sit on planes own_z0 .. own_z1.
     double oz = 0.0;
     for (int k = 0; k < 3; k++) oz -= geo.p2i[6 + k] * (geo.spacing[k] / 2.0);
-    const long long b = 1 - (long long)std::floor(oz - 1e-6), a = (long long)std::floor(oz + 1e-6) + 3;
-    if (b > lo) lo = b;
-    if (a > hi) hi = a;
+    // (compared in double and capped like projection_reach: under a spacing of (1e12, 1, 1e-12) and a tilted direction oz is
+    //  beyond 2^63, and a conversion of that to an integer is not defined -- it used to hand out a negative halo)
+    const double b = 1.0 - std::floor(oz - 1e-6), a = std::floor(oz + 1e-6) + 3.0;
+    if (!(b <= (double)lo)) lo = b < 1e9 ? (long long)b : 1000000000LL;
+    if (!(a <= (double)hi)) hi = a < 1e9 ? (long long)a : 1000000000LL;
   }
   if (below) *below = lo;
   if (above) *above = hi;

@@ -120,7 +120,14 @@ REFUSALS = {"whole": ["normals_rg", "bspline_variant", "bspline_held", "cell_pix
 REFUSALS_FIRST_STREAM = {"whole": 3}
 SLAB_REFUSALS = {"cell_pixels_slab": "cell_pixels", "components_slab": "components"}
 DEFAULT_OPTIONS = dict(max_voxels=900000, big=False, recursive_gaussian=False, kind=None, dtype=None, route=None, max_rows=None,
-                       cell_pixels=None, components=None, keep=None)
+                       cell_pixels=None, components=None, keep=None, envelope=False)
+# --envelope: the edges of the number range (tests/ref_filter.py's envelope cases, drawn).  The line search starts its best
+# metric at 10000 (txx:405): where |voxel - iso| reaches that everywhere the reference never assigns its result, so a
+# line-search case redraws its voxel scale until max |voxel - iso| over the finite voxels is below it.
+ENVELOPE_VOXEL_EXP = {"float32": (-120, 126), "float64": (-1000, 1000)}
+ENVELOPE_SPACING_EXP = (-100, 100)
+ENVELOPE_LIMIT = 1 << 30
+LINESEARCH_BOUND = 10000.0
 KEEP_RULES = ("largest", "min_cells", "mask")
 
 
@@ -219,7 +226,35 @@ def geometry_form(recipe):
 # ---- the voxels of a recipe -----------------------------------------------------------------------------------------------
 def _field(spec):
     vox, iso = draw_field(np.random.default_rng(spec["rng"]), tuple(spec["shape"]), np.dtype(spec["dtype"]), big=spec.get("big", True))
+    if spec.get("scale_exp"):                              # --envelope: a power of two, so the scaling is exact until it leaves the type
+        with np.errstate(over="ignore", under="ignore"):
+            vox = np.ldexp(vox, int(spec["scale_exp"])).astype(vox.dtype)
     return vox, iso
+
+
+def _draw_envelope(rng, dt):
+    """The envelope's own stream: a power-of-two voxel scale (float types), a power-of-two spacing scale, an origin of up to
+    1e9, and in one case of ten a start index near +-2^30 (far enough inside for a border's ring and a region's box)."""
+    both = {name: int(rng.integers(lo, hi + 1)) for name, (lo, hi) in sorted(ENVELOPE_VOXEL_EXP.items())}
+    env = dict(voxel_exp=both.get(np.dtype(dt).name, 0), spacing_exp=int(rng.integers(ENVELOPE_SPACING_EXP[0], ENVELOPE_SPACING_EXP[1] + 1)),
+               origin=[float(v) for v in rng.uniform(-1.0, 1.0, size=3) * 10.0 ** rng.uniform(0.0, 9.0)], start=None)
+    near, signs, inside = rng.random() < 0.1, rng.choice([-1, 1], size=3), rng.integers(40, 100, size=3)
+    if near:
+        env["start"] = [int(s) * (ENVELOPE_LIMIT - int(r)) for s, r in zip(signs, inside)]
+    return env
+
+
+def linesearch_defined(vox, iso):
+    """The campaign's form of the 10000 rule: max |voxel - iso| < 10000 over the FINITE voxels.  Weaker on purpose than
+    ref_filter.linesearch_defined, which takes the whole volume: draw_field pokes an infinite or NaN voxel now and then, no scale
+    brings that under the bound, and the campaign's truth is the oracle, which is defined there -- the rule only keeps the
+    scaled field itself where the reference is defined too."""
+    v = vox[np.isfinite(vox)] if vox.dtype.kind == "f" else vox
+    if not v.size:
+        return True
+    if vox.dtype.kind == "f":
+        return bool(np.max(np.abs(v.astype(np.float64) - float(iso))) < LINESEARCH_BOUND)
+    return max(abs(int(v.max()) - int(iso)), abs(int(v.min()) - int(iso))) < LINESEARCH_BOUND
 
 
 def voxels(recipe):
@@ -290,7 +325,9 @@ def draw_case(seed, case, options=None):
     existed, in the order it drew it then -- no draw of it may move, tests/golden/campaign_recipe_digests.json pins them --, and
     np.random.default_rng([seed, case, 3]) draws cell_pixels, components, drop_cell_rows, emit_offset and refusal_slab -- pinned in
     turn by tests/golden/campaign_celldata_recipe_digests.json --, np.random.default_rng([seed, case, 4]) draws keep
-    ([seed, case, 1] is the field's stream, [seed, case, 2] that of a held case's first volume, [seed, case, 5] a keep's mask)."""
+    ([seed, case, 1] is the field's stream, [seed, case, 2] that of a held case's first volume, [seed, case, 5] a keep's mask,
+    [seed, case, 6] the drop-in campaign's).  options["envelope"]: np.random.default_rng([seed, case, 7]) draws recipe["envelope"]
+    (_draw_envelope; tests/golden/campaign_envelope_recipe_digests.json); off, no draw is made and no key is added."""
     opt = dict(DEFAULT_OPTIONS)
     opt.update(options or {})
     rng = np.random.default_rng([int(seed), int(case)])
@@ -310,6 +347,15 @@ def draw_case(seed, case, options=None):
     dt = np.dtype(opt["dtype"] if opt["dtype"] is not None else DTYPES[int(rng.integers(0, len(DTYPES)))])
     spacing, origin, direction = draw_geometry(rng)
     start = tuple(int(v) for v in rng.integers(-3000, 3000, size=3)) if rng.random() < 0.3 else (0, 0, 0)
+    env = env_rng = None
+    if opt["envelope"]:
+        # (the first stream draws what it always drew; the envelope moves spacing, origin and start behind it, and the step,
+        #  a multiple of the smallest spacing, with them)
+        env_rng = np.random.default_rng([int(seed), int(case), 7])
+        env = _draw_envelope(env_rng, dt)
+        spacing = tuple(float(np.ldexp(v, env["spacing_exp"])) for v in spacing)
+        origin = tuple(env["origin"])
+        start = tuple(env["start"]) if env["start"] else start
     project = bool(rng.random() < 0.75)
     variant = int(rng.choice([0, 0, 0, 1, 2])) if project and kind == "whole" else 0
     kw = dict(triangles=bool(rng.integers(0, 2)), project=project,
@@ -347,7 +393,14 @@ def draw_case(seed, case, options=None):
         recipe["region"] = dict(form=form, start=lo, size=size)
         shape = [buf[2], buf[1], buf[0]]
     recipe["field"] = dict(rng=[int(seed), int(case), 1], shape=shape, dtype=dt.name, big=kind != "bspline")
+    if env:
+        recipe["envelope"] = env
+        recipe["field"]["scale_exp"] = env["voxel_exp"]
     vox, iso = _field(recipe["field"])
+    while env and variant == 2 and dt.kind == "f" and not linesearch_defined(vox, iso):       # (integer voxels are not scaled)
+        lo, hi = ENVELOPE_VOXEL_EXP[dt.name]
+        env["voxel_exp"] = recipe["field"]["scale_exp"] = int(env_rng.integers(lo, hi + 1))
+        vox, iso = _field(recipe["field"])
     recipe["iso"] = iso if dt.kind == "f" else int(iso)
 
     if kind == "border":
@@ -1176,6 +1229,46 @@ def slice_recipes(kind, seed=None, n=None):
                                     components=i % 3 != 2, keep=KEEP_RULES[(i // 2) % 3])) for i in range(n)]
 
 
+# the envelope's slice: every kind and route in turn, a float type in two cases of three, nothing but the mesh (and the normals
+# the first stream draws) compared
+ENVELOPE_SLICE = (2, 60)        # (the first seed for which the oracle alone shows every condition of envelope_slice_conditions())
+
+
+def envelope_slice_recipes(seed=None, n=None):
+    seed = ENVELOPE_SLICE[0] if seed is None else seed
+    n = ENVELOPE_SLICE[1] if n is None else n
+    out = []
+    for i in range(n):
+        kind = KINDS[i % len(KINDS)]
+        dtype = ("float32", "float64")[(i // 3) % 2] if i % 3 else np.dtype(DTYPES[i % len(DTYPES)]).name
+        out.append(draw_case(seed, i, dict(SLICE_OPTIONS, kind=kind, dtype=dtype, route=ROUTES[kind][(i // len(KINDS)) % len(ROUTES[kind])],
+                                           cell_pixels=False, components=False, keep=False, envelope=True)))
+    return out
+
+
+def envelope_slice_conditions(recipes, wants):
+    """What the envelope's slice must show, from the recipes and the references alone, as the list of what is missing."""
+    missing = []
+    def need(ok, what):
+        if not ok:
+            missing.append(what)
+    env = [r["envelope"] for r in recipes]
+    need({r["kind"] for r in recipes} == set(KINDS), "every kind")
+    for dt, (lo, hi) in ENVELOPE_VOXEL_EXP.items():
+        mine = [e["voxel_exp"] for r, e in zip(recipes, env) if r["dtype"] == dt]
+        need(mine and min(mine) < lo // 2 and max(mine) > hi // 2, "%s voxel scales in the lower and in the upper quarter of the exponents" % dt)
+    need(min(e["spacing_exp"] for e in env) < -50 and max(e["spacing_exp"] for e in env) > 50, "spacing scales below 2^-50 and above 2^50")
+    need(max(max(abs(v) for v in e["origin"]) for e in env) > 1e8, "an origin beyond 1e8")
+    need(sum(e["start"] is not None for e in env) >= 3, "three start indices near +-2^30")
+    need(all(linesearch_defined(voxels(r), r["iso"]) for r in recipes if r["kw"]["variant"] == 2), "every line-search case under the 10000 rule")
+    need(any(r["kw"]["variant"] == 2 and r["kw"]["project"] for r in recipes), "a line-search case")
+    walked = [w["mesh"].points for r, w in zip(recipes, wants) if r["kw"]["project"] and r["kw"]["max_steps"] > 0 and len(w["mesh"].points)]
+    need(sum(bool(np.isfinite(p).all()) for p in walked) >= 5, "five walked meshes that stay finite")
+    need(sum(bool(np.isnan(p).any()) for p in walked) >= 5, "five walked meshes with NaN coordinates")
+    need(4 * sum(len(w["mesh"].points) == 0 for w in wants) <= len(wants), "at most a quarter of the cases with an empty reference mesh")
+    return missing
+
+
 def slice_facts(recipe, want, row_before=None, pixels_row_before=None, components_row_before=None, keep_before=False):
     """What one executed case of the slice contributes to the conditions, from the recipe and the reference alone.  row_before,
     pixels_row_before, components_row_before: what row_after(), pixels_row_after(), components_row_after() gave for the case
@@ -1328,6 +1421,8 @@ def main():
     ap.add_argument("--cell-pixels", action="store_true", help="every case that can takes cuberille_set_cell_pixels")
     ap.add_argument("--components", action="store_true", help="every case that can takes cuberille_set_components")
     ap.add_argument("--keep", action="store_true", help="every case with components takes a cuberille_keep_components behind it")
+    ap.add_argument("--envelope", action="store_true", help="the edges of the number range: voxel scales of 2^-120 .. 2^126 (float32) and 2^-1000 .. 2^1000 (float64), spacing scales of 2^-100 .. 2^100, "
+                    "origins up to 1e9, start indices near +-2^30")
     ap.add_argument("--big", action="store_true", help="up to 120 rows and slices (fewer, larger cases: set --max-voxels too)")
     ap.add_argument("--kind", choices=KINDS, default=None, help="draw this kind only")
     ap.add_argument("--dtype", default=None, help="draw this pixel type only (a numpy name)")
@@ -1338,7 +1433,7 @@ def main():
     args = ap.parse_args()
     options = dict(max_voxels=args.max_voxels, big=args.big, recursive_gaussian=args.recursive_gaussian, kind=args.kind,
                    dtype=args.dtype, route=args.route, max_rows=args.max_rows, cell_pixels=args.cell_pixels or None,
-                   components=args.components or None, keep=args.keep or None)
+                   components=args.components or None, keep=args.keep or None, envelope=args.envelope)
     pkg = graft.load_package()
     oracle = graft.load_oracle()
     oracle.build()

@@ -17,6 +17,9 @@ refusal_slab), which the keep's third stream must not move.
 --dropin writes campaign_dropin_recipe_digests.json instead, on the checkout of the day: the recipes of tests/fuzz_dropin.py
 -- fuzz_campaign's with the `dropin` entry from a stream of its own, np.random.default_rng([seed, case, 6]) -- for the same seeds
 and cases and the five slice_recipes(kind) lists of fuzz_dropin, each digested whole and as its `dropin` entry alone.
+--envelope writes campaign_envelope_recipe_digests.json, on the checkout of the day: the recipes draw_case draws with the
+option `envelope` on -- their `envelope` entry from np.random.default_rng([seed, case, 7]) -- for the same seeds and cases and
+fuzz_campaign.envelope_slice_recipes(), digested in blocks of 25 cases, whole and as their `envelope` entries alone.
 Needs no GPU and no oracle."""
 import argparse
 import hashlib
@@ -27,6 +30,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SEEDS = (1, 11)
 CASES = 300
+ENVELOPE_BLOCK = 25
 
 
 def digest(recipe, keys=None):
@@ -54,8 +58,19 @@ def collect_dropin(fd):
                 slice_seeds=dict(fd.SLICE), dropin_keys=sorted({k for rs in by_seed.values() for r in rs for k in r["dropin"]}))
 
 
+def collect_envelope(fz):
+    """The fixture of the envelope's stream: per seed and for the slice, (digest of the recipe, digest of its envelope entry)."""
+    by_seed = {str(s): [fz.draw_case(s, c, dict(envelope=True)) for c in range(CASES)] for s in SEEDS}
+    # (one digest per block of ENVELOPE_BLOCK cases, of the recipes and of their envelope entries: a moved draw names its block)
+    blocks = lambda rs: [rs[i:i + ENVELOPE_BLOCK] for i in range(0, len(rs), ENVELOPE_BLOCK)]        # noqa: E731
+    both = lambda rs: [[digest(b), digest([r["envelope"] for r in b])] for b in blocks(rs)]         # noqa: E731
+    return dict(cases=CASES, seeds={s: both(rs) for s, rs in by_seed.items()}, slice=both(fz.envelope_slice_recipes()),
+                slice_seed=list(fz.ENVELOPE_SLICE), envelope_keys=sorted({k for rs in by_seed.values() for r in rs for k in r["envelope"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--envelope", action="store_true", help="write campaign_envelope_recipe_digests.json from draw_case(envelope=True)")
     ap.add_argument("--dropin", action="store_true", help="write campaign_dropin_recipe_digests.json from tests/fuzz_dropin.py")
     ap.add_argument("--tests", default=os.path.dirname(HERE), help="the tests/ directory of the checkout whose draw_case is recorded")
     ap.add_argument("--out", default="campaign_recipe_digests.json", help="the fixture's file name in tests/golden/")
@@ -65,6 +80,11 @@ def main():
     sys.path.insert(0, tests)
     import fuzz_campaign as fz
     assert os.path.dirname(os.path.abspath(fz.__file__)) == tests, fz.__file__
+    if args.envelope:
+        with open(os.path.join(HERE, "campaign_envelope_recipe_digests.json"), "w") as f:
+            json.dump(collect_envelope(fz), f)
+            f.write("\n")
+        return
     if args.dropin:
         import fuzz_dropin as fd
         with open(os.path.join(HERE, "campaign_dropin_recipe_digests.json"), "w") as f:

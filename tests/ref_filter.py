@@ -23,6 +23,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
 BINARIES = ("ref_filter", "ref_filter_advanced", "ref_filter_linesearch")
 DIGESTS = os.path.join(GOLDEN, "reference_filter_digests.json")
+ENVELOPE_FINITE = os.path.join(GOLDEN, "envelope_finite_vertices.json")      # {family: {rest of the case name: [finite vertices, vertices]}}, from the binary
+BSPLINE_DIGESTS = os.path.join(GOLDEN, "envelope_bspline_digests.json")      # rows as DIGESTS', of bspline_envelope_cases()
 
 PIXEL_NAMES = {np.dtype(np.uint8): "u8", np.dtype(np.int8): "i8", np.dtype(np.uint16): "u16", np.dtype(np.int16): "i16",
                np.dtype(np.uint32): "u32", np.dtype(np.int32): "i32", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64",
@@ -86,6 +88,10 @@ def make_volume(spec):
     rng = np.random.default_rng(spec.get("seed", 0))
     if kind == "random":
         # dense noise: `base` + integers of [0, span), for float types with a fraction added
+        if spec.get("whole"):
+            # the type's whole range, uint64's included (an int64 draw cannot reach it)
+            vox = rng.integers(np.iinfo(dt).min, np.iinfo(dt).max, size=shape, dtype=dt, endpoint=True)
+            return np.ascontiguousarray(vox), None
         vox = rng.integers(0, spec["span"], size=shape, dtype=np.int64)
         if dt.kind == "f":
             vox = (vox.astype(np.float64) + rng.random(shape) + spec.get("base", 0)).astype(dt)
@@ -97,7 +103,8 @@ def make_volume(spec):
         # the smooth field scaled into the type: value = base + scale * f
         f = _field(shape, spec.get("seed", 0)) * spec.get("scale", 1.0)
         if dt.kind == "f":
-            vox = (f + spec.get("base", 0)).astype(dt)
+            with np.errstate(over="ignore"):                 # (a scale past the type's largest number: infinite voxels, meant)
+                vox = (f + spec.get("base", 0)).astype(dt)
         elif dt == np.dtype(np.uint64):
             vox = np.rint(f - f.min()).astype(np.uint64) + np.uint64(spec.get("base", 0))
         else:
@@ -109,6 +116,10 @@ def make_volume(spec):
             vox[z0:z1, y0:y1, x0:x1] = value
     else:
         raise ValueError(kind)
+    if spec.get("band"):
+        # the copy itk::BinaryThresholdImageFilter would hand the filter: [lower, upper, inside, outside] in the pixel type
+        lower, upper, inside, outside = (np.asarray(v, dtype=dt) for v in spec["band"])
+        vox = np.where((lower <= vox) & (vox <= upper), inside, outside).astype(dt)
     for z, y, x, value in spec.get("poke", []):          # single voxels: "nan", "inf", "-inf", "-0.0" or a number
         vox[z, y, x] = float(value)
     return np.ascontiguousarray(vox), None
@@ -193,8 +204,9 @@ def run_reference(case, workdir=None):
     return points, cells
 
 
-def run_oracle(oracle, case):
-    """The same case through the oracle (oracle.run); the padded recipe as np.pad with the start index moved down by one."""
+def run_oracle(oracle, case, **more):
+    """The same case through the oracle (oracle.run); the padded recipe as np.pad with the start index moved down by one.
+    more: further arguments of oracle.run (gradient=1: the recursive-Gaussian gradient, which the reference compiles out)."""
     vox, geo, first = case_inputs(case)
     thr, step, relax = effective(case, vox)
     start = list(geo["start"])
@@ -207,6 +219,7 @@ def run_oracle(oracle, case):
     if first:
         fg = first[1]
         kw["first"] = (first[0], tuple(fg["spacing"]), tuple(fg["origin"]), np.asarray(fg["direction"]).reshape(3, 3), tuple(fg["start"]))
+    kw.update(more)
     m = oracle.run(vox, iso_of(case), **kw)
     return m.points, m.cells
 
@@ -455,6 +468,178 @@ def bspline_cases():
     return out
 
 
+# ---- the envelope: the same walk at the edges of the number range -----------------------------------------------------
+# [7, 8, 9] fields and [6, 7, 9] noise: the smallest at which every vertex still has a full gradient ring and the walk takes
+# several passes.  Every family runs the default branch and the advanced one; the line search (variant 2) only where
+# max |voxel - iso| < LINESEARCH_BOUND over the whole volume: `bestMetric` starts at 10000 (txx:405), every interpolated value
+# is a convex combination of voxels, so under that rule the first sample beats it and `bestVertex` (txx:404,437) is assigned.
+# Above it the reference returns stack contents (seen at a float32 field scaled by 1e6 and at full-range int16 noise), which
+# is why the large magnitudes and the spans carry variants 0 and 1 only and the line search has scales and a span of its own.
+
+LINESEARCH_BOUND = 10000.0
+ENV_ROTATED = dict(UNIT, spacing=[0.7, 1.3, 0.9], direction=_rot(21.0, -13.0))
+ENV_DIAGONAL = dict(UNIT, spacing=[0.25, 0.5, 3.0])                     # identity direction: the kernels' GEOM 1 form
+ENV_F32_GEOMETRIES = [("unit", None), ("rotated", ENV_ROTATED), ("diagonal", ENV_DIAGONAL)]
+ENV_F64_GEOMETRIES = [("rotated", ENV_ROTATED), ("unit", None)]
+ENV_F32_SCALES = [1e-42, 1e-30, 1e-20, 1e15, 1e30, 1e37, 1e38, 1.5e38, 2e38, 3e38]
+ENV_F64_SCALES = [1e-310, 1e-44, 1e-38, 1e-30, 1e30, 1e38, 2e38, 4e38, 1e200, 1e300]
+ENV_LINESEARCH_SCALES = [1e-42, 1e-30, 1e-20, 1e3]
+# 1e38 leaves 96 % of the B-spline walk's vertices finite and 2e38 only 4 %: the scale between them is the mixed one
+ENV_BSPLINE_SCALES = [1e-30, 1e30, 1e38, 1.4e38, 2e38]
+ENV_LIMIT = 1 << 30
+ENV_STARTS = [[ENV_LIMIT, ENV_LIMIT, ENV_LIMIT], [-ENV_LIMIT, -ENV_LIMIT, -ENV_LIMIT], [ENV_LIMIT - 9, -ENV_LIMIT, 12345678],
+              [(1 << 24) + 1, -(1 << 24) - 1, 1 << 29]]
+# the mixed-share condition (tests/test_reference_filter.py): name prefix of each magnitude family that must have a case whose
+# vertices are neither nearly all finite nor nearly all NaN
+ENV_MIXED_FAMILIES = ["envelope/magnitude/float32_unit_", "envelope/magnitude/float32_rotated_", "envelope/magnitude/float32_diagonal_",
+                      "envelope/magnitude/float64_rotated_", "envelope_bspline/magnitude_float32_"]
+
+
+def note_finite(record, case, points):
+    """record[family][rest of the name] = [finite vertices, vertices] for a case of one of ENV_MIXED_FAMILIES (ENVELOPE_FINITE)."""
+    for family in ENV_MIXED_FAMILIES:
+        if case["name"].startswith(family):
+            record.setdefault(family, {})[case["name"][len(family):]] = [int(np.isfinite(points).all(axis=1).sum()), len(points)]
+
+
+def _env_field(dtype, scale=1.0):
+    return dict(kind="field", dtype=dtype, shape=[7, 8, 9], seed=900 if dtype == "float32" else 901, scale=scale)
+
+
+def _env(out, name, volume, iso, variants=(0, 1, 2), threshold=0.01, step=0.2, **more):
+    more.setdefault("relax", 0.9)
+    for v in variants:
+        out.append(_case("envelope/%s_v%d" % (name, v), volume, iso, variant=v, threshold=threshold, step=step, max_steps=8, **more))
+
+
+def envelope_magnitude_cases():
+    out = []
+    for dt, scales, geos in (("float32", ENV_F32_SCALES, ENV_F32_GEOMETRIES), ("float64", ENV_F64_SCALES, ENV_F64_GEOMETRIES)):
+        for gname, geo in geos:
+            for s in scales:
+                _env(out, "magnitude/%s_%s_%g" % (dt, gname, s), _env_field(dt, s), 0.0, variants=(0, 1), threshold=0.0, step=0.25, geometry=geo)
+            for s in ENV_LINESEARCH_SCALES:
+                _env(out, "magnitude/%s_%s_%g" % (dt, gname, s), _env_field(dt, s), 0.0, variants=(2,), threshold=0.0, step=0.25, geometry=geo)
+    return out
+
+
+def envelope_span_cases():
+    """Integer noise over the type's whole range, iso at its middle; the line search on a span of 9999 at int32's lowest."""
+    out = []
+    for dt in ("int16", "uint16", "int32", "uint32", "int64", "uint64"):
+        info = np.iinfo(dt)
+        for proj in (0, 1):
+            _env(out, "span/%s_proj%d" % (dt, proj), dict(kind="random", dtype=dt, shape=[6, 7, 9], seed=77, whole=1),
+                 (int(info.max) + int(info.min) + 1) // 2, variants=(0, 1), step=0.25, project=proj)
+    _env(out, "span/int32_lowest_9999", dict(kind="random", dtype="int32", shape=[6, 7, 9], seed=78, span=9999, base=-(1 << 31)),
+         -(1 << 31) + 4999, variants=(2,), step=0.25)
+    return out
+
+
+def envelope_geometry_cases():
+    """Spacing, origin and start index at their extremes, a step far below and far above a voxel, a direction matrix near
+    singular, no relaxation."""
+    out = []
+    vol = _env_field("float32")
+    for s in (1e-60, 1e-30, 1e-12, 1e-4, 1e4, 1e12, 1e30, 1e60):
+        # At 1e-60 and 1e60 the float gradient overflows or vanishes, Normalize() (txx:409) makes every normal NaN, no sample's
+        # metric compares below bestMetric (txx:430) and the line search returns the unassigned bestVertex (txx:404,437) at
+        # EVERY vertex: undefined in the reference, taken out (4 cases).  The other two branches are defined there (all NaN).
+        variants = (0, 1) if s in (1e-60, 1e60) else (0, 1, 2)
+        _env(out, "spacing/isotropic_%g" % s, vol, 0.0, variants=variants, step=0.25 * s, geometry=dict(UNIT, spacing=[s, s, s]))
+        _env(out, "spacing/rotated_%g" % s, vol, 0.0, variants=variants, step=0.25 * min(s, 1.0 / s),
+             geometry=dict(ENV_ROTATED, spacing=[s, 1.0, 1.0 / s]))
+    for o in (1e5, 1e7, 1e9, 1e15, 1e30):
+        _env(out, "origin/aligned_%g" % o, vol, 0.0, geometry=dict(UNIT, origin=[o, -o, o / 3], spacing=[0.7, 1.3, 0.9]))
+        _env(out, "origin/rotated_%g" % o, vol, 0.0, geometry=dict(ENV_ROTATED, origin=[o, -o, o / 3]))
+    for st in ENV_STARTS:
+        _env(out, "start/unit_%d_%d_%d" % tuple(st), vol, 0.0, geometry=dict(UNIT, start=st))
+        _env(out, "start/all_%d_%d_%d" % tuple(st), vol, 0.0, geometry=dict(GEOMETRIES["all"], start=st))
+    for step in (1e-300, 1e-30, 1e-9, 50.0, 1e5):
+        _env(out, "step/%g" % step, vol, 0.0, step=step, geometry=GEOMETRIES["anisotropic"])
+    for e in (1e-3, 1e-8, 1e-14):
+        _env(out, "shear/%g" % e, vol, 0.0, geometry=dict(UNIT, direction=[1.0, 1.0 - e, 0.0, 0.0, e, 0.0, 0.0, 0.0, 1.0]))
+    _env(out, "relax_0", vol, 0.0, relax=0.0)
+    return out
+
+
+def envelope_pad_cases():
+    """One case per family again behind the class comment's recipe (ConstantPadImageFilter by one pixel): the twins that
+    cuberille_set_border is held to.  (The padded image starts one index lower, so the start-index twin is the one that stays
+    inside the legal range.)"""
+    names = ["magnitude/float32_rotated_2e+38", "magnitude/float64_rotated_2e+38", "span/int64_proj1", "spacing/rotated_1e-12",
+             "origin/rotated_1e+09", "start/all_%d_%d_%d" % tuple(ENV_STARTS[3]), "step/50", "shear/1e-14", "relax_0"]
+    byname = {c["name"]: c for c in envelope_magnitude_cases() + envelope_span_cases() + envelope_geometry_cases()}
+    return [dict(byname["envelope/%s_v0" % n], name="envelope/pad/%s_v0" % n, pad=1) for n in names]
+
+
+ENV_BAND_TWINS = ["magnitude/float32_unit_1e+30", "magnitude/float32_rotated_1e-42", "magnitude/float32_diagonal_1e+38",
+                  "magnitude/float64_rotated_1e+300", "spacing/isotropic_1e-30", "spacing/rotated_1e-12", "origin/aligned_1e+07",
+                  "origin/rotated_1e+07", "start/all_%d_%d_%d" % tuple(ENV_STARTS[2]), "step/1e-09", "shear/1e-14"]
+
+
+def envelope_band_cases():
+    """One case per geometry again on the {0, 1} copy of its field -- 1 where iso <= voxel <= the type's largest number, so an
+    infinite voxel is outside --, iso 1: the twins that cuberille_set_band on the field itself is held to.  (Where float32
+    vertices are coarser than a voxel -- the start index, the squeezed spacing, the shear -- the walk reads a clamped, flat corner
+    of the {0, 1} image and every vertex goes NaN (quirk Q4); the others stay finite, origin/aligned_1e+07 in part.)"""
+    byname = {c["name"]: c for c in envelope_magnitude_cases() + envelope_geometry_cases()}
+    out = []
+    for n in ENV_BAND_TWINS:
+        c = byname["envelope/%s_v0" % n]
+        band = [c["iso"], pixel_max(c["volume"]["dtype"]), 1, 0]
+        out.append(dict(c, name="envelope/band/%s_v0" % n, volume=dict(c["volume"], band=band), iso=1, threshold=0.01))
+    return out
+
+
+ENVELOPE_GROUPS = ["envelope_magnitude_cases", "envelope_span_cases", "envelope_geometry_cases", "envelope_pad_cases", "envelope_band_cases"]
+
+
+def envelope_cases():
+    return envelope_magnitude_cases() + envelope_span_cases() + envelope_geometry_cases() + envelope_pad_cases() + envelope_band_cases()
+
+
+def recursive_gaussian_restated_cases():
+    """The envelope cases that tests/restate.py's recursive-Gaussian restatement covers (tests/test_oracle.py): the default
+    branch on an identity direction, of the families that run with that gradient on the GPU (tests/test_gpu_envelope.py)."""
+    return [c for c in envelope_magnitude_cases() + envelope_geometry_cases()
+            if c["variant"] == 0 and envelope_family(c) in ("magnitude", "spacing", "origin")
+            and (c["geometry"] is None or c["geometry"]["direction"] == UNIT["direction"])]
+
+
+def envelope_family(case):
+    """'magnitude', 'span', 'spacing', 'origin', 'start', 'step', 'shear', 'relax_0', 'pad' or 'band'."""
+    family = case["name"].split("/")[1]
+    return "relax_0" if family.startswith("relax_0") else family
+
+
+def linesearch_defined(case):
+    """The rule above, on the inputs alone."""
+    vox, _, _ = case_inputs(case)
+    if vox.dtype.kind == "f":
+        return bool(np.max(np.abs(vox.astype(np.float64) - float(iso_of(case)))) < LINESEARCH_BOUND)
+    iso = int(iso_of(case))
+    return max(abs(int(vox.max()) - iso), abs(int(vox.min()) - iso)) < LINESEARCH_BOUND
+
+
+def bspline_envelope_cases():
+    """The B-spline instantiations at the same edges; held as bspline_cases() are, the binary against the host walk and the
+    HIP walk against the binary (there is no oracle for it)."""
+    out = []
+    walk = dict(threshold=0.001, step=0.2, relax=0.9, max_steps=8)
+    vol = lambda s=1.0, dt="float32": dict(kind="field", dtype=dt, shape=[7, 8, 9], seed=800, scale=s)
+    for ip in ("bspline_f", "bspline_d"):
+        add = lambda name, v, **kw: out.append(_case("envelope_bspline/%s_%s" % (name, ip), v, 0.0, interp=ip, **dict(walk, **kw)))
+        add("origin_1e+07", vol(), geometry=dict(ENV_ROTATED, origin=[1e7, -1e7, 1e7 / 3]))
+        add("start_limit", vol(), geometry=dict(ENV_ROTATED, start=[ENV_LIMIT, -ENV_LIMIT, ENV_LIMIT - 9]))
+        add("spacing_isotropic_0.0001", vol(), geometry=dict(UNIT, spacing=[1e-4, 1e-4, 1e-4]), step=0.2e-4)
+        add("spacing_10000_1_0.0001", vol(), geometry=dict(UNIT, spacing=[1e4, 1.0, 1e-4]), step=0.2e-4)
+        for s in ENV_BSPLINE_SCALES:
+            add("magnitude_float32_%g" % s, vol(s), threshold=0.0)          # (no threshold a scaled-down field meets at once)
+        add("magnitude_float64_1e+200", vol(1e200, "float64"), threshold=0.0)
+    return out
+
+
 def split_quads(points, quads):
     """txx:295-307 on arrays: each quad as two triangles, cut along the diagonal 1-3 unless 0-2 is strictly shorter; squared
     lengths summed in double over x, y, z in that order (I10)."""
@@ -466,7 +651,7 @@ def split_quads(points, quads):
 
 
 def synthetic_cases():
-    return pixel_type_cases() + cast_cases() + geometry_cases() + quirk_cases() + walk_cases() + border_cases()
+    return pixel_type_cases() + cast_cases() + geometry_cases() + quirk_cases() + walk_cases() + border_cases() + envelope_cases()
 
 
 def points_defined(case):

@@ -195,6 +195,10 @@ def recursive_gaussian_gradient(vol, spacing=(1.0, 1.0, 1.0)):
 def py_normal_from_gradient_image(grad, p, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """VectorLinearInterpolate of a double gradient image at physical point p + Normalize(), all in double (the
     recursive-Gaussian variant's GradientPixelType is CovariantVector<double,3>); identity direction."""
+    if not all(np.isfinite(c) for c in p):
+        # a coordinate that is not finite: its fraction ci - floor(ci) is NaN (inf - inf, or NaN itself), every weight has it
+        # as a factor, so every component of the sum is NaN whichever sites are read -- no index is made of it here
+        return (float("nan"),) * 3
     n = grad.shape[2::-1]
     lo, hi, d = [], [], []
     for k in range(3):

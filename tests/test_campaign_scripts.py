@@ -145,6 +145,59 @@ def test_the_first_stream_draws_what_it_drew():
         assert {k for r in recipes for k in r} == set(fixture["keys"]) | new
 
 
+def test_the_envelope_stream_draws_what_its_digests_say():
+    """tests/golden/campaign_envelope_recipe_digests.json (tests/golden/make_campaign_recipe_digests.py --envelope): every recipe
+    drawn with the option `envelope` on, seeds 1 and 11, cases 0 .. 299, and the slice of tests/test_gpu_campaign.py, in blocks
+    of 25 cases, whole and as their `envelope` entries alone.  Off, the option adds no key and moves no draw (test_the_first_stream_draws_what_it_drew); on, the
+    first stream still draws what it drew: everything the envelope does not touch is the plain recipe's."""
+    import sys
+    import fuzz_campaign as fz
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_campaign_recipe_digests as mk
+    finally:
+        sys.path.pop(0)
+    with open(os.path.join(ROOT, "tests", "golden", "campaign_envelope_recipe_digests.json")) as f:
+        fixture = json.load(f)
+    assert mk.collect_envelope(fz) == fixture
+    assert fixture["envelope_keys"] == ["origin", "spacing_exp", "start", "voxel_exp"] and len(fixture["slice"]) == -(-fz.ENVELOPE_SLICE[1] // mk.ENVELOPE_BLOCK)
+    touched = {"envelope", "spacing", "origin", "index_start", "field", "iso", "kw", "band", "normals", "cuts", "route", "keep", "first"}
+    near = 0
+    for case in range(120):
+        plain, env = fz.draw_case(1, case), fz.draw_case(1, case, dict(envelope=True))
+        assert "envelope" not in plain and set(env) - set(plain) <= {"envelope", "cuts"}
+        assert {k: v for k, v in env.items() if k not in touched} == {k: v for k, v in plain.items() if k not in touched}, case
+        e = env["envelope"]
+        k = e["spacing_exp"]
+        assert -100 <= k <= 100 and env["spacing"] == [float(np.ldexp(v, k)) for v in plain["spacing"]] and env["origin"] == e["origin"]
+        assert max(abs(v) for v in e["origin"]) <= 1e9
+        lo, hi = fz.ENVELOPE_VOXEL_EXP.get(env["dtype"], (0, 0))
+        assert lo <= e["voxel_exp"] <= hi and env["field"].get("scale_exp") == e["voxel_exp"]
+        if e["start"]:
+            near += 1
+            assert env["index_start"] == e["start"] and all((1 << 30) - 100 < abs(v) <= (1 << 30) - 40 for v in e["start"])
+        else:
+            assert env["index_start"] == plain["index_start"]
+        if env["kw"]["variant"] == 2:
+            assert fz.linesearch_defined(fz.voxels(env), env["iso"]), case
+        if e["voxel_exp"] and np.dtype(env["dtype"]).kind == "f":       # a power of two: the finite voxels scale exactly, or leave the type
+            a, b = fz.voxels(dict(plain, field=dict(env["field"], scale_exp=0))).astype(np.float64), fz.voxels(env).astype(np.float64)
+            exact = np.isfinite(b) & (b != 0) & (np.abs(b) >= np.finfo(env["dtype"]).tiny)
+            assert np.array_equal(np.ldexp(a[exact], e["voxel_exp"]), b[exact]), case
+    assert 4 <= near <= 25                                              # one case of ten
+
+
+def test_envelope_slice_conditions_hold_on_the_oracle(oracle):
+    """The envelope's seeded slice of tests/test_gpu_campaign.py shows what envelope_slice_conditions asks -- every kind, voxel
+    scales at both ends of both float types, spacings beyond 2^+-50, start indices near +-2^30, line-search cases under the
+    10000 rule, walked meshes that stay finite and walked meshes that go NaN -- from the recipes and the references alone."""
+    import fuzz_campaign as fz
+    recipes = fz.envelope_slice_recipes()
+    assert len(recipes) == 60 and recipes == json.loads(json.dumps(recipes))
+    wants = [fz.expected(oracle, r) for r in recipes]
+    assert fz.envelope_slice_conditions(recipes, wants) == []
+
+
 def test_recipes_survive_json_and_run_through_the_references(oracle):
     """Every kind, route, normals, repeat and refusal the campaign draws: the recipe is plain data, its JSON round trip rebuilds
     the same voxel bytes and the same expected mesh (and normals), and draw_case is a pure function of (seed, case).  The keep

@@ -125,6 +125,27 @@ def test_bspline_slice(pkg, oracle):
     _run_slice(pkg, oracle, "bspline")
 
 
+def test_envelope_slice(pkg, oracle):
+    """fuzz_campaign.py --envelope, a seeded slice: voxel scales of 2^-120 .. 2^126 (float32) and 2^-1000 .. 2^1000 (float64), spacing scales of 2^-100 .. 2^100, origins up
+    to 1e9, start indices near +-2^30, on every kind and route in turn, each mesh (and the normals the case draws) equal to
+    the references'.  Its conditions: tests/test_campaign_scripts.py."""
+    recipes = fz.envelope_slice_recipes()
+    assert len(recipes) == fz.ENVELOPE_SLICE[1] == 60 and all(r["envelope"] for r in recipes)
+    contexts = fz.open_contexts(pkg)
+    wants = []
+    try:
+        for recipe in recipes:
+            try:
+                got, want = fz.one_case(pkg, oracle, contexts, recipe)
+            except AssertionError as e:
+                raise AssertionError("seed %d case %d (%s %s %s, envelope %s): %s" % (recipe["seed"], recipe["case"], recipe["kind"], recipe["dtype"],
+                                                                                      recipe["route"], recipe["envelope"], e)) from e
+            wants.append(want)
+    finally:
+        fz.close_contexts(contexts)
+    assert fz.envelope_slice_conditions(recipes, wants) == []
+
+
 def test_whole_slice_conditions(pkg, oracle):
     """What the slice must hold over all five kinds together, over the cases executed (a kind that has not run yet in this
     process runs here)."""

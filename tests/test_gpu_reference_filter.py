@@ -87,6 +87,30 @@ def test_bspline_device_walk_against_the_reference_filter(pkg, oracle, ex):
         assert diff is None, "%s: %s" % (case["name"], diff)
 
 
+@needs_binary
+def test_bspline_envelope_device_walk_against_the_reference_filter(pkg, oracle, ex):
+    """The B-spline device walk at the edges of the number range (ref_filter.bspline_envelope_cases): an origin of 1e7, a start
+    index at +-2^30, spacings of 1e-4 and 1e4, voxels from 1e-30 up to where the coefficients overflow."""
+    cases = rf.bspline_envelope_cases()
+    assert len(cases) == 20
+    for case in cases:
+        points, cells = run_hip(pkg, ex, case)
+        diff = rf.first_difference(points, cells, *rf.run_reference(case))
+        assert diff is None, "%s: %s" % (case["name"], diff)
+
+
+def test_bspline_envelope_matches_recorded_reference_results(pkg, oracle, ex):
+    """tests/golden/envelope_bspline_digests.json alone, where the binaries did not travel."""
+    with open(rf.BSPLINE_DIGESTS) as f:
+        rows = json.load(f)
+    cases = rf.bspline_envelope_cases()
+    assert len(rows) == len(cases) == 20
+    for case, row in zip(cases, rows):
+        assert row["case"] == case, case["name"]
+        d = rf.digest(*run_hip(pkg, ex, case))
+        assert {k: d[k] for k in d} == {k: row[k] for k in d}, case["name"]
+
+
 def test_hip_matches_recorded_reference_results(pkg, oracle, ex):
     """tests/golden/reference_filter_digests.json alone: meaningful where the binaries did not travel."""
     with open(rf.DIGESTS) as f:

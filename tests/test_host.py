@@ -98,6 +98,25 @@ def test_required_halo_follows_the_parameters(pkg):
     assert pkg.required_halo(d, pkg.make_params(0.5, step=0.25, relax=0.95, max_steps=0))[0] == 1 + 3
 
 
+def test_halos_stay_in_range_at_the_edges_of_the_number_range(pkg):
+    """cuberille_minimum_halo and cuberille_required_halo on the envelope's geometries (tests/ref_filter.py): at least the
+    topology's 2 / 1, at most the cap of 10^9, and never more than the full halo -- under a spacing of (1e12, 1, 1e-12) and a
+    tilted direction the start of the walk lies beyond 2^63 slices from its corner, and cuberille_minimum_halo converted that
+    to an integer: it handed out -9223372036854775807 slices below (found by tests/test_gpu_envelope.py's thin-halo slabs)."""
+    import ref_filter as rf
+    seen = set()
+    for case in rf.envelope_geometry_cases():
+        vox, geo, _ = rf.case_inputs(case)
+        thr, step, relax = rf.effective(case, vox)
+        nz, ny, nx = vox.shape
+        desc = pkg.make_desc(vox.dtype, (nx, ny, nz), geo["spacing"], geo["origin"], np.asarray(geo["direction"]).reshape(3, 3), geo["start"])
+        prm = pkg.make_params(0.0, True, True, thr, step, relax, case["max_steps"])
+        (below, above), (tb, ta) = pkg.required_halo(desc, prm), pkg.cuberille.minimum_halo(desc, prm)
+        assert 2 <= tb <= below <= 10 ** 9 and 1 <= ta <= above <= 10 ** 9, (case["name"], below, above, tb, ta)
+        seen.add((tb, ta))
+    assert (2, 2) in seen and (2, 10 ** 9) in seen
+
+
 def test_required_halo_covers_the_start_of_the_walk_under_a_tilted_direction(pkg, oracle):
     """The reference takes half a spacing off every PHYSICAL axis of a corner's position (txx:266-270): under a tilted
     direction matrix with unequal spacings the walk starts slices away from the lattice corner, not half a voxel.  A slab cut

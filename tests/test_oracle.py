@@ -452,3 +452,36 @@ def test_recursive_gaussian_gradient_against_second_restatement(oracle):
     g = recursive_gaussian_gradient(ramp)
     mid = g[4:8, 4:8, 4:8]
     assert np.allclose(mid[..., 0], 2.0, atol=1e-2) and np.allclose(mid[..., 1], 3.0, atol=1e-2) and np.allclose(mid[..., 2], -1.0, atol=1e-2)
+
+
+def test_recursive_gaussian_gradient_at_the_edges_of_the_number_range(oracle):
+    """The envelope cases of tests/ref_filter.py that the rule above covers -- the default branch on an identity direction: the
+    float32 and float64 magnitudes on unit and diagonal spacing, the isotropic spacings of 1e-60 .. 1e60, the axis-aligned
+    origins up to 1e30 -- through the same second restatement, every projected vertex bit for bit (NaN for NaN) and the number
+    of passes: tests/test_gpu_envelope.py holds the HIP kernels of the recursive-Gaussian gradient to the oracle on these
+    cases, and the oracle's filter is a restatement, not compiled from ITK -- it is not the only witness there."""
+    import ref_filter as rf
+    from restate import py_default_walk_normal_fn, py_normal_from_gradient_image, recursive_gaussian_gradient
+    cases = rf.recursive_gaussian_restated_cases()
+    assert len(cases) == 43 and {rf.envelope_family(c) for c in cases} == {"magnitude", "spacing", "origin"}
+    some_finite = some_nan = 0
+    for case in cases:
+        vox, geo, _ = rf.case_inputs(case)
+        thr, step, relax = rf.effective(case, vox)
+        sp, org = tuple(geo["spacing"]), tuple(geo["origin"])
+        kw = dict(threshold=thr, step=step, relax=relax, max_steps=case["max_steps"], spacing=sp, origin=org)
+        flat = oracle.run(vox, 0.0, triangles=False, project=False, **kw)
+        got = oracle.run(vox, 0.0, triangles=False, project=True, gradient=1, **kw)
+        with np.errstate(all="ignore"):
+            grad = recursive_gaussian_gradient(vox, sp)
+            passes = 0
+            for i, v in enumerate(flat.points):
+                want, n = py_default_walk_normal_fn(lambda p: py_normal_from_gradient_image(grad, p, sp, org),
+                                                    lambda p: oracle.interpolate(vox, p, spacing=sp, origin=org), 0.0, v,
+                                                    thr, step, relax, case["max_steps"])
+                passes += n
+                assert rf.point_bytes(np.asarray(want, dtype=np.float32)) == rf.point_bytes(got.points[i]), (case["name"], i, want, got.points[i])
+        assert got.info["proj_iterations"] == passes, case["name"]
+        some_finite += bool(np.isfinite(got.points).all())
+        some_nan += bool(np.isnan(got.points).any())
+    assert some_finite >= 10 and some_nan >= 10

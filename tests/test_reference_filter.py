@@ -93,7 +93,9 @@ def test_variant_digests_reproduced_by_the_switched_reference_filters(oracle):
     assert undefined == rf.UNDEFINED_VARIANT_ROWS           # one row: blob3's line search meets a zero gradient
 
 
-GROUPS = [("pixel_type_cases", 50), ("cast_cases", 55), ("geometry_cases", 36), ("quirk_cases", 50), ("walk_cases", 45), ("border_cases", 12)]
+GROUPS = [("pixel_type_cases", 50), ("cast_cases", 55), ("geometry_cases", 36), ("quirk_cases", 50), ("walk_cases", 45), ("border_cases", 12),
+          ("envelope_magnitude_cases", 120), ("envelope_span_cases", 25), ("envelope_geometry_cases", 125), ("envelope_pad_cases", 9),
+          ("envelope_band_cases", 11)]
 
 
 @needs_binary
@@ -114,6 +116,53 @@ def test_case_lists_cover_what_they_claim():
     assert {c["max_steps"] for c in rf.walk_cases()} >= {0, 1, 3} and {c["relax"] for c in rf.walk_cases()} >= {1.0, 0.5}
     assert any(c["first"] and c["step"] < 0 for c in rf.walk_cases())
     assert all(c["pad"] for c in rf.border_cases())
+    # the envelope: every family on both switched branches, the line search only where the reference defines it -- on the inputs
+    env = rf.envelope_cases()
+    assert [g for g, _ in GROUPS[-5:]] == rf.ENVELOPE_GROUPS and sum(n for _, n in GROUPS[-5:]) == len(env)
+    assert rf.synthetic_cases()[-len(env):] == env                      # appended: the earlier rows of the digest file keep their place
+    families = {}
+    for c in env:
+        families.setdefault(rf.envelope_family(c), set()).add(c["variant"])
+        assert c["triangles"] == 1 and rf.points_defined(c) and c["max_steps"] == 8 and c["threshold"] in (0.0, 0.01), c["name"]
+        assert tuple(c["volume"]["shape"]) == ((7, 8, 9) if c["volume"]["kind"] == "field" else (6, 7, 9)), c["name"]
+        if c["variant"] == 2:
+            assert rf.linesearch_defined(c), c["name"]
+    assert families == dict({f: {0, 1, 2} for f in ("magnitude", "span", "spacing", "origin", "start", "step", "shear", "relax_0")}, pad={0}, band={0})
+    large = [c for c in env if c["variant"] != 2 and rf.envelope_family(c) in ("magnitude", "span") and not rf.linesearch_defined(c)]
+    assert len(large) >= 2 * (6 * 3 + 5 * 2 + 6 * 2)                     # what the rule keeps from the line search runs the other two
+    whole = {c["volume"]["dtype"]: rf.case_inputs(c)[0] for c in rf.envelope_span_cases() if c["volume"].get("whole")}
+    assert sorted(whole) == ["int16", "int32", "int64", "uint16", "uint32", "uint64"]
+    for dt, vox in whole.items():                                       # the whole range of the type: both top bits drawn, uint64's too
+        info = np.iinfo(dt)
+        assert int(vox.max()) > info.max - (info.max - info.min) // 16 and int(vox.min()) < info.min + (info.max - info.min) // 16, dt
+    starts = {tuple(c["geometry"]["start"]) for c in env if rf.envelope_family(c) == "start"}
+    assert starts == {tuple(s) for s in rf.ENV_STARTS} and max(abs(v) for s in starts for v in s) == 1 << 30
+    bs = rf.bspline_envelope_cases()
+    assert len(bs) == 20 and {c["interp"] for c in bs} == {"bspline_f", "bspline_d"} and len({c["name"] for c in bs}) == 20
+
+
+def test_envelope_magnitude_families_are_mixed():
+    """A family whose vertices are all finite or all NaN says little: from the reference's recorded output alone
+    (tests/golden/envelope_finite_vertices.json, written with the digests from the binary) each magnitude family has a case whose
+    share of finite vertices lies strictly between 5 % and 95 %."""
+    with open(rf.ENVELOPE_FINITE) as f:
+        recorded = json.load(f)
+    names = [c["name"] for c in rf.envelope_cases() + rf.bspline_envelope_cases()]
+    assert sorted(recorded) == sorted(rf.ENV_MIXED_FAMILIES)
+    for family in rf.ENV_MIXED_FAMILIES:
+        assert sorted(family + rest for rest in recorded[family]) == sorted(n for n in names if n.startswith(family)), family
+        shares = {rest: finite / points for rest, (finite, points) in recorded[family].items()}
+        assert shares and any(0.05 < s < 0.95 for s in shares.values()), (family, shares)
+
+
+@needs_binary
+def test_envelope_finite_vertices_are_the_reference_filters():
+    with open(rf.ENVELOPE_FINITE) as f:
+        recorded = json.load(f)
+    again = {}
+    for case in rf.envelope_magnitude_cases() + rf.bspline_envelope_cases():
+        rf.note_finite(again, case, rf.run_reference(case)[0])
+    assert again == recorded
 
 
 @needs_binary
@@ -123,13 +172,27 @@ def test_bspline_instantiations_against_the_host_walk(tmp_path):
     itkCuberilleImageToMeshFilter.txx through the same interpolator class, run by itk/tests/bspline_walk.cxx without a GPU --
     from the reference's own unprojected vertices: every walked vertex bit for bit, and the triangles the reference makes of
     them equal to the split rule applied to those vertices."""
-    import subprocess
-    from bspline_ref import geometry_arg, walk_exe
     cases = rf.bspline_cases()
     assert len(cases) == 9
+    _bspline_host_walk(tmp_path, cases)
+
+
+@needs_binary
+def test_bspline_envelope_against_the_host_walk(tmp_path):
+    """The same at the edges of the number range (ref_filter.bspline_envelope_cases)."""
+    cases = rf.bspline_envelope_cases()
+    assert len(cases) == 20
+    # (at an origin of 1e7 or a start index of 2^30 a float32 coordinate's last place is 1 or 128, a step of 0.2 is below it:
+    # those walks may leave every vertex where it started)
+    _bspline_host_walk(tmp_path, cases, moved=lambda case: "/spacing" in case["name"] or "/magnitude" in case["name"])
+
+
+def _bspline_host_walk(tmp_path, cases, moved=lambda case: True):
+    import subprocess
+    from bspline_ref import geometry_arg, walk_exe
     for n, case in enumerate(cases):
         vox, geo, _ = rf.case_inputs(case)
-        assert vox.dtype in (np.uint8, np.float32)
+        assert vox.dtype in (np.uint8, np.float32, np.float64)
         start, quads = rf.run_reference(dict(case, interp="linear", project=0, triangles=0))
         rpoints, rquads = rf.run_reference(dict(case, triangles=0))
         assert np.array_equal(quads, rquads) and len(start) == len(rpoints) > 0, case["name"]
@@ -146,7 +209,7 @@ def test_bspline_instantiations_against_the_host_walk(tmp_path):
         got = np.fromfile(op, dtype="<f4").reshape(-1, 3)
         diff = rf.first_difference(got, quads, rpoints, rquads)
         assert diff is None, "%s: %s" % (case["name"], diff)
-        assert not np.array_equal(got, start), case["name"]                     # the walk moved them
+        assert not moved(case) or not np.array_equal(got, start), case["name"]  # the walk moved them
         tpoints, tcells = rf.run_reference(dict(case, triangles=1))
         diff = rf.first_difference(got, rf.split_quads(got, quads), tpoints, tcells)
         assert diff is None, "%s (triangles): %s" % (case["name"], diff)
