@@ -570,6 +570,58 @@ int cuberille_components_device(cuberille_ctx *ctx, const uint32_t **d_point_com
                                 const uint64_t **d_component_cells);
 int cuberille_components_download(cuberille_ctx *ctx, uint32_t *point_component, uint32_t *cell_component,
                                   uint64_t *component_cells, size_t capacity_components);
+/* Point scalars (new symbols within ABI 13, no struct changed).  The value of ANOTHER image on the surface: what a host loop of
+ * interpolator->SetInputImage(other); interpolator->Evaluate(point) over mesh->GetPoints() gives -- the intensity volume under a
+ * surface of its label volume, a PET or a dose grid under a surface of the CT, the next time step -- without the mesh leaving the
+ * device.  With the extraction's own image as the second one it is the interpolated value at each final vertex, whose distance from
+ * the iso value is what the walk stopped on.
+ * Image B, the second image: any of the ten pixel types under a description of its own (dims, spacing, origin, direction,
+ * index_start), whole and contiguous, x fastest.  One definition for every route, pixel type and source view of the extraction:
+ * for each point p of the final mesh the three floats as the points buffer holds them (behind the walk, or the lattice start with
+ * project_vertices off; behind cuberille_keep_components on the kept mesh), widened to double,
+ *   1. cv = p - origin_B; ci[r] = ((0 + m[r][0]*cv[0]) + m[r][1]*cv[1]) + m[r][2]*cv[2] with m B's point-to-index matrix, built
+ *      without contraction (ci = cv where m is the unit matrix): ci is in B's INDEX space;
+ *   2. p is inside B when index_start_k - 0.5 <= ci_k && ci_k < index_start_k + n_k - 0.5 on every axis; a NaN coordinate
+ *      (quirk Q4) fails the comparison and is outside;
+ *   3. inside, the value is itk::LinearInterpolateImageFunction<B, double>::Evaluate(p) under the contract of DESIGN.md section 3:
+ *      the cell from floor(ci), the eight neighbours clamped into B's buffered region (I5), each pixel converted by (double) -- a
+ *      64-bit integer past 2^53 rounds --, the sum in double in counter order, zero weights skipped, stopped once the weights sum
+ *      to exactly 1 (I7);
+ *   4. outside, outside_value with its 64 bits as given: a NaN's payload and -0.0 survive.
+ * The output is one double per point in point order.  A pass of its own behind the walk (and behind the normals' pass) writes
+ * it, one lane per vertex; with stage timing on its time is part of ms_project.  Points, cells, normals, cell pixels, components
+ * and counters are the bytes of the same extraction with the setting off.
+ * cuberille_set_point_scalars: img == NULL turns the setting off (the default: nothing allocated, nothing launched, every result
+ *   as before the symbols existed; it frees the row, its spare and the library's copy of B).  CUBERILLE_MEM_HOST: the library
+ *   uploads a copy of its own at the call and waits for it, the caller's memory is free on return; the copy lives until the
+ *   setting goes off, is replaced, or the context is destroyed, and counts in cuberille_debug_device_bytes.  CUBERILLE_MEM_DEVICE:
+ *   (The upload is ONE plain copy on the context's stream whatever the size -- the chunk pipeline that cuberille_extract_host
+ *   takes for a GiB and more is not used here: a caller with an image that large uploads it as it sees fit and hands it over
+ *   with CUBERILLE_MEM_DEVICE.  The new copy is complete before an earlier one is freed -- for a moment the context holds
+ *   both -- and a call that fails, for lack of memory say, leaves the setting exactly as it was, off or on with the earlier
+ *   image.)
+ *   the pointer is borrowed -- valid and filled until the setting goes off, read on the context's stream; it may be the very
+ *   buffer being extracted.  Not between cuberille_step_begin and _end.
+ * cuberille_point_scalars_device: *d_scalars = double[n_points] of the last extraction in the library's buffer (valid until the
+ *   next call on the context; null for an empty mesh).  cuberille_point_scalars_download: the same into host memory;
+ *   CUBERILLE_ERR_ARGUMENT when capacity_bytes is below 8 * n_points.  Both: CUBERILLE_ERR_STATE with a message when the last
+ *   extraction ran with the setting off (or there is no mesh).
+ * cuberille_keep_components compacts the row with the others: point_scalars' = point_scalars[kp].
+ * cuberille_mesh_write_vtk on a context that holds point scalars writes "SCALARS point_scalar double 1" / "LOOKUP_TABLE default"
+ *   last in POINT_DATA (opening the block where none exists), one %.17g per line; with the setting off the file is byte for byte
+ *   what it was.
+ * Offered: cuberille_extract_host, cuberille_extract_device, cuberille_extract_stream, cuberille_count + cuberille_emit_points /
+ * cuberille_emit on a whole volume; every source view, both interpolators, every projection and gradient variant, a held gradient
+ * (it reads the points, not the first image).  Refused with CUBERILLE_ERR_ARGUMENT and a message that says "point scalars", the
+ * context left usable: a slab that is not the whole volume; the cuberille_step_* calls; cuberille_group_extract_host with a member
+ * that has the setting on; a description the library would refuse as an input image; a null `voxels`; an unknown `location`.
+ * Out of scope: nearest-neighbour and B-spline sampling of B; vector images or several second images; slabs, steps and groups; a
+ * count of the outside points (it is isnan or == outside_value on the row). */
+enum { CUBERILLE_MEM_HOST = 0, CUBERILLE_MEM_DEVICE = 1 };
+int cuberille_set_point_scalars(cuberille_ctx *ctx, const cuberille_image_desc *img, const void *voxels, int location,
+                                double outside_value);           /* img == NULL: off */
+int cuberille_point_scalars_device(cuberille_ctx *ctx, const double **d_scalars);
+int cuberille_point_scalars_download(cuberille_ctx *ctx, double *out, size_t capacity_bytes);
 /* Keep the largest surface, or drop the specks (new symbols within ABI 13, no struct changed): the last mesh of ctx -- one that
  * came with components -- is replaced on the device by the part of it that lies in the kept components, order preserved.
  *   CUBERILLE_KEEP_LARGEST    the one component with the most cells; a tie goes to the smaller component number; K = 0 keeps

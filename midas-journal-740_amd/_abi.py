@@ -41,7 +41,9 @@ EXPORTS = [
     "cuberille_set_cell_pixels", "cuberille_cell_pixels_device", "cuberille_cell_pixels_download",
     "cuberille_set_components", "cuberille_components_info", "cuberille_components_device", "cuberille_components_download",
     "cuberille_keep_components",
+    "cuberille_set_point_scalars", "cuberille_point_scalars_device", "cuberille_point_scalars_download",
 ]
+MEM_HOST, MEM_DEVICE = 0, 1        # cuberille_set_point_scalars: where the second image lies
 GROUP_MAX = 64                      # cuberille_group_create: members of a group
 ABI_VERSION = 13
 
@@ -160,6 +162,9 @@ def lib():
     L.cuberille_components_download.argtypes = [vp, vp, vp, vp, C.c_size_t]
     L.cuberille_keep_components.argtypes = [vp, C.c_int, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+    L.cuberille_set_point_scalars.argtypes = [vp, C.POINTER(ImageDesc), vp, C.c_int, C.c_double]
+    L.cuberille_point_scalars_device.argtypes = [vp, C.POINTER(vp)]
+    L.cuberille_point_scalars_download.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients.argtypes = [vp, vp, C.c_size_t]
     L.cuberille_bspline_coefficients_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.cuberille_debug_bits.argtypes = [vp, vp, C.c_size_t]

@@ -30,6 +30,8 @@ int append_vtk_cell_pixels(const char *path, const void *pixels, int pixel_type,
 // (the component array of the POINT_DATA or the CELL_DATA block; block: "POINT_DATA" / "CELL_DATA" where this array opens the
 //  block, null where the block exists)
 int append_vtk_components(const char *path, const char *block, const uint32_t *labels, uint64_t n);
+// (the point scalars' array, last in the POINT_DATA block; block as above)
+int append_vtk_point_scalars(const char *path, const char *block, const double *values, uint64_t n);
 }
 using namespace cuberille;
 
@@ -130,6 +132,22 @@ size_t row_reserve_bytes(int r, const u64 n[N_PERS], int verts_per_cell, size_t 
 }
 struct MeshRow { DevBuf row, spare; };
 
+// cuberille_set_point_scalars, the fourth optional output: a row held BESIDE the tables (the tables' sizes are
+// written out in the host-only test of the three), with a {row, spare} pair and an {on, counting, have} state of its own and
+// its own line wherever a loop over the tables stands for the others.  One double per point: the row of an emit of n points
+// (none for an empty mesh), the spare of a keep to n.
+size_t point_scalars_bytes(u64 n) { return (size_t)n * sizeof(double); }
+struct PointScalars {
+  bool on = false, counting = false, have = false;   // the setting, as the running count/emit pair found it, whether the last mesh has the row
+  MeshRow rows;
+  DevBuf copy;                       // CUBERILLE_MEM_HOST: the library's own copy of the second image
+  const void *vox = nullptr;         // the second image on the device: the copy, or the caller's pointer (CUBERILLE_MEM_DEVICE)
+  int pixel_type = 0, n[3] = {0, 0, 0};
+  Geo geo{};
+  double outside = 0.0;
+};
+const char *const kPointScalarsNoun = "point scalars", *const kPointScalarsFn = "cuberille_set_point_scalars";
+
 }  // namespace
 
 struct cuberille_ctx {
@@ -161,6 +179,7 @@ struct cuberille_ctx {
   int64_t bsDims[3] = {0, 0, 0};         // ... and its size
   // the optional outputs (kAttrWords): the setting, the setting as the running count/emit pair found it, whether the last mesh has it
   struct { bool on = false, counting = false, have = false; } attr[N_ATTRS];
+  PointScalars ps;                       // cuberille_set_point_scalars: beside the tables
   // the components' scratch, no rows of the mesh: the union-find's forest and the numbering's scan row (CompRows), and what
   // cuberille_keep_components decides and scans in; freed with the component rows
   DevBuf compParent, compScan, keepSel, keepScan, *const compScratch[4] = {&compParent, &compScan, &keepSel, &keepScan};
@@ -237,6 +256,11 @@ std::vector<DevBuf *> device_buffers(cuberille_ctx *c) {
                                &c->gradImg, &c->rgA, &c->rgB, &c->rgScratch, &c->heldGrad, &c->bsCoef, &c->bsScratch};
   all.insert(all.end(), c->compScratch, c->compScratch + 4);
   for (MeshRow &m : c->rows) { all.push_back(&m.row); all.push_back(&m.spare); }
+  // (the point scalars' three exist only while the setting is on -- off, its setter has released them and a failed call keeps
+  //  none --; listed as well whenever one of them holds memory, so that nothing this context owns can go unlisted)
+  if (c->ps.on || c->ps.rows.row.p || c->ps.rows.spare.p || c->ps.copy.p) {
+    all.push_back(&c->ps.rows.row); all.push_back(&c->ps.rows.spare); all.push_back(&c->ps.copy);
+  }
   return all;
 }
 
@@ -440,6 +464,11 @@ int attrs_offered(const cuberille_ctx *c, const cuberille_params *prm, Route rou
       if (prm->gradient_variant != CUBERILLE_GRADIENT_CENTRAL)
         return no(name + " are the central-difference gradient: not offered with CUBERILLE_GRADIENT_RECURSIVE_GAUSSIAN");
     }
+    if (!whole_volume(slab) && (slab->global_nz != nz || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + nz)) return no(name + kAttrSlab);
+  }
+  if (c->ps.on) {                     // the point scalars, beside the table: one context's whole volume like the three, in their words
+    const std::string noun = kPointScalarsNoun, fn = kPointScalarsFn, name = noun + " (" + fn + ")";
+    if (const char *r = kAttrRoute[route]) return route == ROUTE_GROUP ? no("has " + noun + " set (" + fn + "): " + r) : no(name + r);
     if (!whole_volume(slab) && (slab->global_nz != nz || slab->own_z0 != slab->z_begin || slab->own_z1 != slab->z_begin + nz)) return no(name + kAttrSlab);
   }
   return CUBERILLE_OK;
@@ -911,6 +940,12 @@ EmitSizes emit_sizes(const Grid &g, const Tuning &t, bool triangles, bool dyn, u
   return s;
 }
 
+// The point scalars' row of an emit of nV points, beside EmitSizes::rows: 8 bytes per point, nothing for an empty mesh, and
+// the cover of the points' own row (dyn, the blind launch of cuberille_extract_device: nV is that cover already)
+Want point_scalars_want(u64 nV, bool dyn = false) {
+  return nV ? Want{point_scalars_bytes(nV), point_scalars_bytes(dyn ? nV : nV + nV / 4 + 4096)} : Want{0, 0};
+}
+
 // An optional buffer: its pointer, or null when it is not wanted or cannot be had
 void *optional(DevBuf &b, size_t bytes, size_t cover = 0) {
   if (bytes && b.reserve_covering(bytes, cover) == hipSuccess) return b.p;
@@ -927,6 +962,7 @@ void rows_home(cuberille_ctx *c) {
     if (a != ATTR_NONE && a != ATTR_COMPONENTS && !c->attr[a].on) continue;
     if (c->rows[r].spare.cap > c->rows[r].row.cap) std::swap(c->rows[r].row, c->rows[r].spare);
   }
+  if (c->ps.on && c->ps.rows.spare.cap > c->ps.rows.row.cap) std::swap(c->ps.rows.row, c->ps.rows.spare);   // (off: left alone)
 }
 
 // First half of a count: layout, parameters, workspace, zeroed state.  The caller then thresholds the slices
@@ -938,6 +974,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->pointsEmitted = false;
   c->haveMesh = false;
   for (auto &a : c->attr) a.have = false;
+  c->ps.have = false;
   c->hostMeshValid = false;
   c->stepMode = 0;
   c->voxelHaloEvent = nullptr;
@@ -1033,6 +1070,7 @@ int count_prepare(cuberille_ctx *c, const cuberille_image_desc *img, const void 
   c->g = g; c->geo = geo; c->prm = p; c->pixel_type = img->pixel_type; c->w = w;
   c->countBsBits = (p.project && c->interp == CUBERILLE_INTERP_BSPLINE) ? c->bsBits : 0;
   for (auto &a : c->attr) a.counting = a.on;
+  c->ps.counting = c->ps.on;
   c->nwords = sz.nwords; c->nseg = sz.nseg;
   return CUBERILLE_OK;
 }
@@ -1285,6 +1323,10 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
       HIP_TRY(c, c->compParent.reserve_covering(want.bytes, want.cover));
     HIP_TRY(c, c->row(r).reserve_covering(want.bytes, want.cover));
   }
+  // (the point scalars' row, beside the table: 8 bytes per point, none for an empty mesh)
+  const Want scalarsWant = c->ps.counting ? point_scalars_want(nV, dyn) : Want{0, 0};
+  const bool scalars = scalarsWant.bytes != 0;
+  if (scalars) HIP_TRY(c, c->ps.rows.row.reserve_covering(scalarsWant.bytes, scalarsWant.cover));
   if (sz.compScan.bytes) {
     HIP_TRY(c, c->compScan.reserve_covering(sz.compScan.bytes, sz.compScan.cover));
     if (!c->hostK) HIP_TRY(c, hipHostMalloc((void **)&c->hostK, sizeof(u64), hipHostMallocDefault));
@@ -1381,6 +1423,10 @@ int emit_points_phase(cuberille_ctx *c, bool ahead, bool dyn = false, u64 coverV
   // and one more pass reads each of them once (with stage timing on, part of ms_project)
   if (sz.rows[ROW_NORMALS].bytes)
     HIP_TRY(c, launch_point_normals(c->pixel_type, w, c->g, c->geo, (float *)c->row(ROW_NORMALS).p, nV, dyn ? 1 : 0, s));
+  // cuberille_set_point_scalars: the second image at the final points, one more pass behind that one (part of ms_project too)
+  if (scalars)
+    HIP_TRY(c, launch_point_scalars(c->ps.pixel_type, c->ps.vox, c->ps.n, c->ps.geo, (const float *)w.points, (double *)c->ps.rows.row.p,
+                                    nV, (const Totals *)w.totals, dyn ? 1 : 0, c->ps.outside, s));
   if (ahead) c->pointsStartedEarly = true;   // the caller turns to the other ranks now: the cells come as an interval of their own
   HIP_TRY(c, mark(c, PROJECT_END));
   c->pointsEmitted = true;
@@ -1465,6 +1511,7 @@ int finish_result(cuberille_ctx *c, cuberille_result *res) {
   c->stepMode = 0;
   c->haveMesh = true;
   for (auto &a : c->attr) a.have = a.counting;
+  c->ps.have = c->ps.counting;
   c->nComponents = c->attr[ATTR_COMPONENTS].counting && c->hostK ? *c->hostK : 0;
   c->counted = false;                        // the workspace now belongs to this mesh
   if (res) *res = r;
@@ -2107,6 +2154,7 @@ int cuberille_warm_up(cuberille_ctx *c, const cuberille_image_desc *img, const c
     c->haveHistory = false;                  // (sizes of a toy volume: the first real extraction reads its own counts)
     c->haveMesh = false;
     for (auto &a : c->attr) a.have = false;
+    c->ps.have = false;
     c->counted = false;
     c->warm = true;
   }
@@ -2360,6 +2408,104 @@ int cuberille_normals_download(cuberille_ctx *c, float *normals) {
   return download_pipelined(c, normals, c->row(ROW_NORMALS).p, mesh_row_bytes(c, ROW_NORMALS));
 }
 
+// The point scalars' setter: what it releases when the setting goes off or the image is replaced -- the row with its spare, and
+// the copy -- behind whatever may still be reading or writing them.
+static int point_scalars_release(cuberille_ctx *c, bool rows) {
+  PointScalars &ps = c->ps;
+  if ((rows && (ps.rows.row.p || ps.rows.spare.p)) || ps.copy.p) {
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (rows) { ps.rows.row.release(); ps.rows.spare.release(); }
+  ps.copy.release();
+  ps.vox = nullptr;
+  return CUBERILLE_OK;
+}
+
+int cuberille_set_point_scalars(cuberille_ctx *c, const cuberille_image_desc *img, const void *voxels, int location, double outside_value) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (c->stepMode != 0) return fail(c, CUBERILLE_ERR_STATE, "a step is open on this context");
+  PointScalars &ps = c->ps;
+  if (!img) {                                          // off: the context holds what one that never heard of the setting holds
+    if (const int rc = point_scalars_release(c, true)) return rc;
+    ps.on = ps.counting = ps.have = false;
+    return CUBERILLE_OK;
+  }
+  // the description, by the rules of an input image (validate), in this setting's words; the setting stays as it was
+  const std::string name = std::string(kPointScalarsNoun) + " (" + kPointScalarsFn + "): the second image's ";
+  if (!voxels) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "voxel pointer is null");
+  if (location != CUBERILLE_MEM_HOST && location != CUBERILLE_MEM_DEVICE)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, name + "location is neither CUBERILLE_MEM_HOST nor CUBERILLE_MEM_DEVICE");
+  if (pixel_size(img->pixel_type) == 0) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "pixel type is unknown");
+  for (int i = 0; i < 3; i++) {
+    if (img->dims[i] < 1) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "dimensions must be >= 1");
+    if (img->dims[i] > 0x7fffffffLL) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "dimension exceeds 2^31-1");
+    if (!(img->spacing[i] > 0.0)) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "spacing must be > 0");
+    if (img->index_start[i] < -(1LL << 30) || img->index_start[i] > (1LL << 30))
+      return fail(c, CUBERILLE_ERR_ARGUMENT, name + "start index must lie within +-2^30");
+  }
+  Geo geo{};
+  Params unused{};
+  const cuberille_params noParams{};
+  resolve(img, &noParams, geo, unused);
+  for (int i = 0; i < 9; i++)                          // (a singular direction has no point-to-index matrix)
+    if (!std::isfinite(geo.p2i[i])) return fail(c, CUBERILLE_ERR_ARGUMENT, name + "direction has no inverse");
+  // CUBERILLE_MEM_HOST: a copy of the library's own, complete on return.  The new copy is allocated and filled BEFORE the
+  // earlier one is given up, and the setting changes only once nothing can fail any more: a call that fails leaves the
+  // context exactly as it was -- off, or on with the earlier image -- and holds no memory of its own.  (One plain copy on
+  // the context's stream, whatever the size: the chunk pipeline of cuberille_extract_host is not used here.)
+  DevBuf fresh;
+  if (location == CUBERILLE_MEM_HOST) {
+    const size_t bytes = (size_t)img->dims[0] * (size_t)img->dims[1] * (size_t)img->dims[2] * pixel_size(img->pixel_type);
+    (void)hipSetDevice(c->device);
+    hipError_t e = fresh.reserve(bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(fresh.p, voxels, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      fresh.release();
+      return fail(c, CUBERILLE_ERR_HIP, name + "copy could not be made (" + hipGetErrorString(e) + "): the setting stays as it was");
+    }
+  }
+  // (the earlier copy goes behind whatever may still be reading it; a failure here has released nothing)
+  if (const int rc = point_scalars_release(c, false)) { fresh.release(); return rc; }
+  ps.copy = fresh;
+  ps.vox = location == CUBERILLE_MEM_HOST ? (const void *)ps.copy.p : voxels;
+  ps.pixel_type = img->pixel_type;
+  for (int i = 0; i < 3; i++) ps.n[i] = (int)img->dims[i];
+  ps.geo = geo;
+  ps.outside = outside_value;
+  ps.on = true;
+  return CUBERILLE_OK;
+}
+
+static int point_scalars_preconditions(cuberille_ctx *c) {
+  if (!c->haveMesh) return fail(c, CUBERILLE_ERR_STATE, "no mesh: call cuberille_extract_* or cuberille_emit first");
+  if (!c->ps.have)
+    return fail(c, CUBERILLE_ERR_STATE, std::string("no ") + kPointScalarsNoun + ": the last extraction ran with the setting off (" + kPointScalarsFn + ")");
+  return CUBERILLE_OK;
+}
+
+int cuberille_point_scalars_device(cuberille_ctx *c, const double **d_scalars) {
+  if (!c || !d_scalars) return CUBERILLE_ERR_ARGUMENT;
+  *d_scalars = nullptr;
+  if (const int rc = point_scalars_preconditions(c)) return rc;
+  *d_scalars = c->res.n_points ? (const double *)c->ps.rows.row.p : nullptr;   // (a row sized by an earlier mesh is no value of an empty one)
+  return CUBERILLE_OK;
+}
+
+int cuberille_point_scalars_download(cuberille_ctx *c, double *out, size_t capacity_bytes) {
+  if (!c) return CUBERILLE_ERR_ARGUMENT;
+  if (const int rc = point_scalars_preconditions(c)) return rc;
+  const size_t bytes = point_scalars_bytes(c->res.n_points);
+  if (capacity_bytes < bytes)
+    return fail(c, CUBERILLE_ERR_ARGUMENT, std::string("the ") + kPointScalarsNoun + " take " + std::to_string(bytes) + " bytes, the buffer holds " +
+                                           std::to_string(capacity_bytes));
+  if (!bytes) return CUBERILLE_OK;
+  if (!out) return fail(c, CUBERILLE_ERR_ARGUMENT, "null output pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  return download_pipelined(c, out, c->ps.rows.row.p, bytes);
+}
+
 int cuberille_set_cell_pixels(cuberille_ctx *c, int on) { return set_attr(c, ATTR_CELL_PIXELS, on); }
 
 int cuberille_cell_pixels_device(cuberille_ctx *c, const void **d_pixels, int *pixel_type) {
@@ -2400,11 +2546,17 @@ int cuberille_set_components(cuberille_ctx *c, int on) {
       if (bytes) HIP_TRY(c, hipMemcpyAsync(m.spare.p, m.row.p, bytes, hipMemcpyDeviceToDevice, c->stream));
       std::swap(m.row, m.spare);
     }
+    if (MeshRow &m = c->ps.rows; m.spare.cap > m.row.cap && m.row.p) {      // (the point scalars' pair, beside the table)
+      const size_t bytes = c->ps.have ? point_scalars_bytes(c->res.n_points) : 0;
+      if (bytes) HIP_TRY(c, hipMemcpyAsync(m.spare.p, m.row.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+      std::swap(m.row, m.spare);
+    }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->w.points = (float *)c->row(ROW_POINTS).p;
     c->w.cells = (u64 *)c->row(ROW_CELLS).p;
   }
   for (MeshRow &m : c->rows) m.spare.release();
+  c->ps.rows.spare.release();
   return CUBERILLE_OK;
 }
 
@@ -2514,6 +2666,7 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
       HIP_TRY(c, c->rows[i].spare.reserve(row_reserve_bytes(i, n2, c->res.verts_per_cell, pix)));
       in[i] = c->rows[i].row.p; out[i] = c->rows[i].spare.p;
     }
+    if (c->ps.have) HIP_TRY(c, c->ps.rows.spare.reserve(point_scalars_bytes(nP2)));   // (the point scalars' spare, beside the table)
     const KeepOut o = {(float *)out[ROW_POINTS], (float *)out[ROW_NORMALS], (u64 *)out[ROW_CELLS], out[ROW_CELL_PIX],
                        (u32 *)out[ROW_COMP_POINT], (u32 *)out[ROW_COMP_CELL], (u64 *)out[ROW_COMP_COUNT]};
     Workspace w = c->w;
@@ -2521,6 +2674,8 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
     w.cells = (u64 *)in[ROW_CELLS];
     HIP_TRY(c, launch_keep_scatter(w, r, k, o, (const float *)in[ROW_NORMALS], in[ROW_CELL_PIX], kept[ROW_CELL_PIX] ? (int)pix : 0,
                                    c->prm.triangles, c->pointOffset, K, nP, nC, s));
+    if (c->ps.have)
+      HIP_TRY(c, launch_keep_scatter_point_scalars(r, k, (const double *)c->ps.rows.row.p, (double *)c->ps.rows.spare.p, K, nP, s));
   }
   HIP_TRY(c, hipEventRecord(c->keepEv[1], s));
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -2530,6 +2685,7 @@ int cuberille_keep_components(cuberille_ctx *c, int rule, uint64_t n, const uint
       // the kept mesh is complete in the spare rows: the buffers change places (the earlier ones are the next call's spare rows)
       for (int i = 0; i < N_ROWS; i++)
         if (kept[i]) std::swap(c->rows[i].row, c->rows[i].spare);
+      if (c->ps.have) std::swap(c->ps.rows.row, c->ps.rows.spare);
       c->w.points = (float *)c->row(ROW_POINTS).p;
       c->w.cells = (u64 *)c->row(ROW_CELLS).p;
     }
@@ -2693,6 +2849,13 @@ int cuberille_mesh_write_vtk(cuberille_ctx *c, const char *path, int n_threads) 
     const int dl = cuberille_components_download(c, pointComp.data(), cellComp.data(), nullptr, 0);
     if (dl != CUBERILLE_OK) return dl;
     wr = cuberille::append_vtk_components(path, withNormals ? nullptr : "POINT_DATA", pointComp.data(), r.n_points);
+  }
+  if (wr == CUBERILLE_OK && c->ps.have) {
+    // a context that holds point scalars: SCALARS point_scalar double 1, last in POINT_DATA (setting off: the file as it was)
+    std::vector<double> val(r.n_points);
+    const int dl = cuberille_point_scalars_download(c, val.data(), val.size() * sizeof(double));
+    if (dl != CUBERILLE_OK) return dl;
+    wr = cuberille::append_vtk_point_scalars(path, withNormals || withComponents ? nullptr : "POINT_DATA", val.data(), r.n_points);
   }
   if (wr == CUBERILLE_OK && withPixels) {
     // a context that holds cell pixels: CELL_DATA n / SCALARS pixel <type> 1 behind everything else (setting off: the file as it was)

@@ -330,5 +330,15 @@ hipError_t launch_keep_scatter(const Workspace &w, const CompRows &r, const Keep
                                const void *cellPixIn, int pixBytes, int triangles, u64 pointOffset, u64 K, u64 nP, u64 nC,
                                hipStream_t s);
 
+// cuberille_set_point_scalars: a second image (vox: whole, contiguous, n voxels of pixel_type under geo) linearly interpolated
+// at vertices [0, nPoints) of `points` as they stand, into `scalars` -- one double per point in id order, `outside` bit for
+// bit where the point lies outside that image's buffer.  A row of its own beside the table's rows.  dyn: as in
+// launch_point_normals.
+hipError_t launch_point_scalars(int pixel_type, const void *vox, const int n[3], const Geo &geo, const float *points, double *scalars,
+                                u64 nPoints, const Totals *totals, int dyn, double outside, hipStream_t s);
+// ... and its stable scatter in cuberille_keep_components, over the decision and the point scan of launch_keep_count
+hipError_t launch_keep_scatter_point_scalars(const CompRows &r, const KeepRows &k, const double *in, double *out, u64 K, u64 nP,
+                                             hipStream_t s);
+
 }  // namespace cuberille
 #endif

@@ -3820,6 +3820,106 @@ __global__ __launch_bounds__(256) void k_point_normals(const T *__restrict__ vox
 }
 
 // ---------------------------------------------------------------------------------------------
+// K4f: point scalars (cuberille_set_point_scalars).  A SECOND image B -- its own pixel type T2, dims and geometry, whole and
+// contiguous -- sampled at every FINAL vertex: what itk::LinearInterpolateImageFunction<B, double>::Evaluate(point) returns
+// in a host loop over mesh->GetPoints(), where the point lies inside B's buffer, and the caller's outside value elsewhere.
+// The three floats as they stand in the points buffer go through I4 with B's Geo (cv = p - origin, ci the full product of
+// make_cell in its order, or its unit form where make_cell shows the two equal: a NaN or an infinity on another axis fails the
+// inside test below on that axis either way), the inside test on ci BEFORE any clamp -- istart - 0.5 <= ci < istart + n - 0.5
+// on every axis, what ImageFunction::IsInsideBuffer asks; a NaN coordinate (quirk Q4) fails it --, then make_cell (I5: the
+// eight sites clamped into B) and the literal sum of I7 in double: counter order, zero weights skipped, stopped once the
+// weights sum to exactly 1, every pixel through (double), so a 64-bit integer past 2^53 rounds as the reference's does.
+// One lane per vertex in id order, as in k_point_normals: ids follow raster order, neighbouring lanes share rows of B.  The
+// two sites of a row come as ONE load of a pair where the row has two pixels: the pair starts at min(lo, nx - 2), so it
+// never reaches past the row's last pixel, and a cell clamped at either end of the row (lo == hi) takes the pixel it names
+// out of that pair.  A row of one pixel is one load.  No LDS, no atomics; nothing is written but the 8 bytes per lane,
+// consecutive lanes at consecutive addresses, and the outside value goes out as the 64 bits it came in as.  dyn (the blind
+// launch of cuberille_extract_device, sized from the previous extraction): the vertex count is read where k_point_normals'
+// blind form reads it, and the lanes stride over it.
+// ---------------------------------------------------------------------------------------------
+template <class T> struct __attribute__((packed, aligned(alignof(T)))) SitePair { T a, b; };
+
+template <class T>
+__global__ __launch_bounds__(256) void k_point_scalars(const T *__restrict__ vox, int nx, int ny, int nz, Geo geo,
+                                                       const float *__restrict__ points, u64 *__restrict__ scalars,
+                                                       u64 nPoints, const Totals *__restrict__ tot, int dyn, u64 outsideBits) {
+  if (dyn) {
+    if (!tot->go) return;
+    nPoints = tot->totV;
+  }
+  const Sampler<T, VIEW_WHOLE> s{vox, nx, ny, nz, 0, nz};
+  const int n[3] = {nx, ny, nz};
+  bool unitP2I = true;
+#pragma unroll
+  for (int i = 0; i < 9; i++) unitP2I = unitP2I && (geo.p2i[i] == ((i % 4 == 0) ? 1.0 : 0.0));
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 idx = (u64)blockIdx.x * blockDim.x + threadIdx.x; idx < nPoints; idx += stride) {
+    const double p[3] = {(double)points[3 * idx], (double)points[3 * idx + 1], (double)points[3 * idx + 2]};
+    // ci ahead of make_cell's clamp, by make_cell's own expressions
+    double cv[3], ci[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) cv[k] = p[k] - geo.origin[k];
+    if (unitP2I) {
+#pragma unroll
+      for (int r = 0; r < 3; r++) ci[r] = cv[r];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) sum += geo.p2i[r * 3 + k] * cv[k];
+        ci[r] = sum;
+      }
+    }
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++)   // (a start index within +-2^30 and n < 2^31: both bounds are exact doubles)
+      inside = inside && ((double)geo.istart[k] - 0.5 <= ci[k]) && (ci[k] < (double)((long long)geo.istart[k] + n[k]) - 0.5);
+    u64 bits = outsideBits;
+    if (inside) {
+      Cell8 c;
+      make_cell(geo, unitP2I, n, p, c);                                               // I4, I5
+      T V[8];
+      // the four rows of the cell; their loads are issued together, ahead of one wait, whichever form the rows take (the
+      // test on nx is uniform and stands around the loads, not between them)
+      const T *row[4];
+#pragma unroll
+      for (int zy = 0; zy < 4; zy++) row[zy] = s.row((zy & 1) ? c.hi[1] : c.lo[1], s.zlocal((zy & 2) ? c.hi[2] : c.lo[2]));
+      if (nx >= 2) {
+        const int q = min(c.lo[0], nx - 2);                                           // the pair's first pixel
+        SitePair<T> pr[4];
+#pragma unroll
+        for (int zy = 0; zy < 4; zy++) pr[zy] = *(const SitePair<T> *)(row[zy] + q);
+#pragma unroll
+        for (int zy = 0; zy < 4; zy++) {
+          V[2 * zy] = c.lo[0] == q ? pr[zy].a : pr[zy].b;
+          V[2 * zy + 1] = c.hi[0] == q ? pr[zy].a : pr[zy].b;
+        }
+      } else {                                                                        // a row of one pixel
+        T one[4];
+#pragma unroll
+        for (int zy = 0; zy < 4; zy++) one[zy] = row[zy][0];
+#pragma unroll
+        for (int zy = 0; zy < 4; zy++) V[2 * zy] = V[2 * zy + 1] = one[zy];
+      }
+      double value = 0.0, total = 0.0;                                                // I7
+#pragma unroll
+      for (unsigned counter = 0; counter < 8; counter++) {
+        double overlap = 1.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) overlap *= (counter & (1u << k)) ? c.d[k] : (1.0 - c.d[k]);
+        if (overlap != 0.0 && total != 1.0) {
+          value += overlap * (double)V[counter];
+          total += overlap;
+        }
+      }
+      bits = (u64)__double_as_longlong(value);
+    }
+    scalars[idx] = bits;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // K3c: cell pixels (cuberille_set_cell_pixels).  What the reference's commented-out mesh->SetCellData( id, ... ) behind every
 // cell it adds (txx:314, 321, 330) would carry: quad (u, f) -- inside voxel u, face f, numbered as DESIGN.md section 2 item 1
 // says -- gets I(u), the pixel of its inside voxel in the image's own type T, moved as bits (a NaN keeps its payload, -0.0
@@ -4236,6 +4336,21 @@ __global__ __launch_bounds__(COMP_SCAN_B) void k_keep_scatter_points(const float
     normalsOut[3 * (u64)at + 2] = nz;
   }
   pointCompOut[at] = number[k];
+}
+
+// ... and the point scalars (cuberille_set_point_scalars), a row beside the table's: the same decision and the same scan of the
+// points (level 0 of k.scanP plus the rank in the block), so the same stable positions; launched only where the mesh has the row.
+// V: the row's element as the bits it is moved as (u64 for the doubles: a NaN keeps its payload).
+template <class V>
+__global__ __launch_bounds__(COMP_SCAN_B) void k_keep_scatter_point_scalars(const V *__restrict__ scalars, const u32 *__restrict__ pointComp,
+                                                                            const u32 *__restrict__ keep, const u32 *__restrict__ base,
+                                                                            V *__restrict__ scalarsOut, u64 nP, u64 K) {
+  __shared__ u32 waveSum[COMP_SCAN_B / 64];
+  const u64 p = (u64)blockIdx.x * COMP_SCAN_B + threadIdx.x;
+  u32 k, total;
+  const u32 f = keep_flag(keep, pointComp, p, nP, K, k);
+  const u32 at = comp_block_scan(f, waveSum, total) + base[blockIdx.x];
+  if (f) scalarsOut[at] = scalars[p];
 }
 
 template <int NV>
@@ -4988,6 +5103,31 @@ hipError_t launch_point_normals(int pixel_type, const Workspace &w, const Grid &
     });
     return hipGetLastError();
   });
+}
+
+// The point scalars of vertices [0, nPoints) of `points` into `scalars` (K4f), behind whatever left the points final on `s`.
+// vox, n, geo: the second image, whole and contiguous, of pixel_type.  dyn: nPoints is what the launch is sized for, the kernel
+// reads the real count from the device totals.
+hipError_t launch_point_scalars(int pixel_type, const void *vox, const int n[3], const Geo &geo, const float *points, double *scalars,
+                                u64 nPoints, const Totals *totals, int dyn, double outside, hipStream_t s) {
+  if (nPoints == 0) return hipSuccess;
+  u64 outsideBits;
+  memcpy(&outsideBits, &outside, sizeof outsideBits);
+  return by_pixel_type(pixel_type, [&](auto *tag) -> hipError_t {
+    typedef typename std::remove_cv<typename std::remove_pointer<decltype(tag)>::type>::type T;
+    hipLaunchKernelGGL((k_point_scalars<T>), dim3(grid_for(nPoints, 256, 0x7fffffffu)), dim3(256), 0, s, (const T *)vox, n[0], n[1], n[2],
+                       geo, points, (u64 *)scalars, nPoints, totals, dyn, outsideBits);
+    return hipGetLastError();
+  });
+}
+
+// cuberille_keep_components with point scalars on the mesh: their stable scatter into `out`, over the decision and the point
+// scan launch_keep_count left.  Beside launch_keep_scatter on `s`, in either order (neither reads what the other writes).
+hipError_t launch_keep_scatter_point_scalars(const CompRows &r, const KeepRows &k, const double *in, double *out, u64 K, u64 nP,
+                                             hipStream_t s) {
+  hipLaunchKernelGGL(k_keep_scatter_point_scalars<u64>, dim3((unsigned)comp_scan_plan(nP).len[0]), dim3(COMP_SCAN_B), 0, s, (const u64 *)in,
+                     r.pointComp, k.keep, k.scanP, (u64 *)out, nP, K);
+  return hipGetLastError();
 }
 
 // The cell pixels of quads [0, nQ) of the owned range into `out` (K3c: one value per quad, two with triangles), behind the

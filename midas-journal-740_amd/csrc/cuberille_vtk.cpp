@@ -198,4 +198,18 @@ int append_vtk_components(const char *path, const char *block, const uint32_t *l
   ok = (std::fclose(f) == 0) && ok;
   return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
 }
+
+// The point scalars' array of the POINT_DATA block (cuberille_set_point_scalars): one double per line as %.17g, which reads
+// back to the same value (a NaN as "nan" or "-nan": its payload is not a text's to keep).
+int append_vtk_point_scalars(const char *path, const char *block, const double *values, uint64_t n) {
+  if (!path || (n && !values)) return CUBERILLE_ERR_ARGUMENT;
+  std::FILE *f = std::fopen(path, "ab");
+  if (!f) return CUBERILLE_ERR_ARGUMENT;
+  bool ok = true;
+  if (block) ok = std::fprintf(f, "%s %llu\n", block, (unsigned long long)n) > 0;
+  ok = ok && std::fprintf(f, "SCALARS point_scalar double 1\nLOOKUP_TABLE default\n") > 0;
+  for (uint64_t i = 0; ok && i < n; i++) ok = std::fprintf(f, "%.17g\n", values[i]) > 0;
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? CUBERILLE_OK : CUBERILLE_ERR_STATE;
+}
 }  // namespace cuberille

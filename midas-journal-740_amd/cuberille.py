@@ -193,6 +193,19 @@ def make_desc(np_dtype, dims_xyz, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
     return d
 
 
+def _set_point_scalars(lib, ctx, image, outside):
+    """cuberille_set_point_scalars on one context; image: a Volume (host), a (dev_ptr, desc) pair (device) or None (off)."""
+    if image is None:
+        _abi.check(ctx, lib.cuberille_set_point_scalars(ctx, None, None, 0, 0.0))
+    elif isinstance(image, tuple):
+        dev_ptr, desc = image
+        _abi.check(ctx, lib.cuberille_set_point_scalars(ctx, C.byref(desc), C.c_void_p(dev_ptr), _abi.MEM_DEVICE, float(outside)))
+    else:
+        vox = np.ascontiguousarray(image.voxels)
+        desc = make_desc(vox.dtype, image.dims, image.spacing, image.origin, image.direction, getattr(image, "index_start", (0, 0, 0)))
+        _abi.check(ctx, lib.cuberille_set_point_scalars(ctx, C.byref(desc), C.c_void_p(vox.ctypes.data), _abi.MEM_HOST, float(outside)))
+
+
 class Extractor:
     """One context (stream + workspace) on one GPU."""
 
@@ -495,6 +508,31 @@ class Extractor:
         _abi.check(self._ctx, self._lib.cuberille_normals_device(self._ctx, C.byref(p)))
         return p.value
 
+    def set_point_scalars(self, image, outside=float("nan")):
+        """Point scalars (cuberille_set_point_scalars): every later extraction also leaves, for every point, the linearly
+        interpolated value of a SECOND image at the point's final position -- what a host loop of
+        itk::LinearInterpolateImageFunction::Evaluate over the mesh's points gives -- as a double, and `outside` (bit for bit)
+        where the point lies outside that image's buffer.  image: a Volume in host memory (the library uploads a copy of its
+        own at this call), a (dev_ptr, desc) pair (borrowed: valid and filled until the setting goes off; it may be the volume
+        being extracted), or None (off, the default: frees the row and the copy).  Points, cells and counters are unchanged.
+        Slabs, steps and groups are refused at the extraction."""
+        _set_point_scalars(self._lib, self._ctx, image, outside)
+
+    def download_point_scalars(self):
+        """The point scalars of the last extraction as a float64 array of length n_points, in point-id order
+        (cuberille_point_scalars_download); CuberilleError ERR_STATE when that extraction ran with the setting off."""
+        n = int(self.result.n_points) if self.result is not None else 0
+        out = np.empty(n, dtype=np.float64)
+        _abi.check(self._ctx, self._lib.cuberille_point_scalars_download(self._ctx, C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def point_scalars_device(self):
+        """Device pointer of the point scalars of the last extraction, one double per point in the library's buffer
+        (cuberille_point_scalars_device; None for an empty mesh)."""
+        p = C.c_void_p()
+        _abi.check(self._ctx, self._lib.cuberille_point_scalars_device(self._ctx, C.byref(p)))
+        return p.value
+
     def set_cell_pixels(self, on=True):
         """Cell pixels (cuberille_set_cell_pixels): every later extraction also leaves, for every cell, the pixel of the
         inside voxel of the cell's quad, in the volume's own dtype -- the value the reference's commented-out SetCellData
@@ -783,6 +821,12 @@ class ExtractorGroup:
         refusal -- they belong to one context's whole volume."""
         self._on_every_member(self._lib.cuberille_set_cell_pixels, 1 if on else 0)
 
+    def set_point_scalars(self, image, outside=float("nan")):
+        """Point scalars (Extractor.set_point_scalars) on every member: the group's extraction then raises the library's
+        refusal -- they belong to one context's whole volume."""
+        for i in range(len(self.devices)):
+            _set_point_scalars(self._lib, self.context(i), image, outside)
+
     def set_components(self, on=True):
         """Components (Extractor.set_components) on every member: the group's extraction then raises the library's
         refusal -- a component does not stop at a slab's face."""
@@ -855,6 +899,7 @@ class CuberilleImageToMeshFilter:
     _components_on = False    # SetGenerateComponents: off (likewise)
     _keep_largest = False     # SetKeepLargestComponent: off (likewise)
     _min_component_cells = 0  # SetMinimumComponentCells: none (likewise)
+    _scalar_image = None      # SetPointScalarImage: none (likewise)
 
     _NOT_IN_A_GROUP = (
         ("_pad_border", False, "an implied border (SetPadBorder / cuberille_set_border)", "the ring would have to reach across slabs"),
@@ -864,6 +909,7 @@ class CuberilleImageToMeshFilter:
         ("_cell_pixels_on", False, "cell pixels (SetSavePixelAsCellData / cuberille_set_cell_pixels)", "they belong to one context's whole volume"),
         ("_components_on", False, "components (SetGenerateComponents / cuberille_set_components)", "a component does not stop at a slab's face"),
         ("_keep_largest", False, "the largest component (SetKeepLargestComponent / cuberille_keep_components)", "a component does not stop at a slab's face"),
+        ("_scalar_image", None, "point scalars (SetPointScalarImage / cuberille_set_point_scalars)", "they belong to one context's whole volume"),
         ("_min_component_cells", 0, "a minimum of cells per component (SetMinimumComponentCells / cuberille_keep_components)", "a component does not stop at a slab's face"))
 
     def __init__(self, device=0, devices=None):
@@ -901,6 +947,10 @@ class CuberilleImageToMeshFilter:
         self._components = None                   # (point_component, cell_component, component_cells) of the last Update(), or None
         self._keep_largest = False                # SetKeepLargestComponent: off
         self._min_component_cells = 0             # SetMinimumComponentCells: none
+        self._scalar_image = None                 # SetPointScalarImage: the second image (a Volume), or None
+        self._scalar_outside = float("nan")       # SetPointScalarOutsideValue
+        self._scalar_uploaded = False             # ... the extractor holds its copy of that image
+        self._point_scalars = None                # GetPointScalars(): float64 per point of the last Update(), or None
         self.last_result = None
         # like the C++ drop-in: the GPU context and the code objects are set up when the filter is made, not inside the
         # first Update() (the reference's driver times one cold Update(), test:158-160); silent without a device --
@@ -1128,6 +1178,24 @@ class CuberilleImageToMeshFilter:
         """(n, 3) float32 in point-id order, filled by the last Update() with the switch on; None with it off."""
         return self._point_normals
 
+    def SetPointScalarImage(self, volume):
+        """Not in the reference -- what a caller does with the mesh afterwards: a second image (a Volume of any pixel type,
+        size and geometry) is linearly interpolated at every point's final position, as a host loop of
+        itk::LinearInterpolateImageFunction::Evaluate over the mesh's points would (cuberille_set_point_scalars), and Update()
+        fills GetPointScalars().  None turns it off (the default).  The image is uploaded once per call of this method: a
+        caller who changes its pixels calls it again."""
+        self._scalar_image = volume
+        self._scalar_uploaded = False
+
+    def SetPointScalarOutsideValue(self, v):
+        """The value of a point outside the second image's buffer (default NaN), kept bit for bit."""
+        self._scalar_outside = float(v)
+        self._scalar_uploaded = False
+
+    def GetPointScalars(self):
+        """float64 per point id, filled by the last Update() with a second image set; None without one."""
+        return self._point_scalars
+
     def SetSavePixelAsCellData(self, b):
         """The switch of the filter's maintained successor; the reference reserves the place with a commented-out
         mesh->SetCellData( id, ... ) behind every cell (txx:314, 321, 330).  On: Update() also fills GetCellPixels() with
@@ -1235,6 +1303,7 @@ class CuberilleImageToMeshFilter:
             self._point_normals = None
             self._cell_pixels = None
             self._components = None
+            self._point_scalars = None
             self.last_result = self._group.extract_host(vol, prm)
             self._output = self._group.download()
             self.last_number_of_slabs = len(self._group.plan(self._group_desc(vol), prm))
@@ -1260,6 +1329,12 @@ class CuberilleImageToMeshFilter:
         keep = self._keep_largest or self._min_component_cells > 0
         self._extractor.set_components(self._components_on or keep)
         self._components = None
+        if self._scalar_image is None:
+            self._extractor.set_point_scalars(None)
+        elif not self._scalar_uploaded:
+            self._extractor.set_point_scalars(self._scalar_image, self._scalar_outside)
+            self._scalar_uploaded = True
+        self._point_scalars = None
         self.last_result = self._extractor.extract_host(vol, prm)
         # (the mesh is compacted on the device before anything of it comes to the host)
         if self._keep_largest:
@@ -1273,6 +1348,8 @@ class CuberilleImageToMeshFilter:
             self._cell_pixels = self._extractor.download_cell_pixels()
         if self._components_on or keep:
             self._components = self._extractor.download_components()
+        if self._scalar_image is not None:
+            self._point_scalars = self._extractor.download_point_scalars()
         self.last_number_of_slabs = 1
 
     @staticmethod

@@ -51,6 +51,8 @@ namespace cuberille_detail
 {
 // process-wide: do the filters constructed from now on set up their GPU context in the constructor (see SetEagerDeviceSetup)
 inline bool &EagerDeviceSetup() { static bool on = true; return on; }
+// (itkCuberilleImageToMeshFilter.txx) an image as the C ABI takes it; false when nothing is buffered
+template <class TImage> bool DescribeImage(const TImage *image, ::cuberille_image_desc &desc);
 }
 
 
@@ -318,6 +320,34 @@ public:
   const std::vector<uint64_t> &GetComponentCellCounts() const { return m_ComponentCellCounts; }
   size_t GetNumberOfComponents() const { return m_ComponentCellCounts.size(); }
 
+  /** Not in the reference: what a caller does with the mesh afterwards -- interpolator->SetInputImage(other);
+   *  interpolator->Evaluate(point) in a loop over mesh->GetPoints() -- on the device, where the mesh already is
+   *  (cuberille_set_point_scalars).  SetPointScalarImage(other): `other` is any three-dimensional itk::Image of one of the ten
+   *  pixel types, with its own buffered region, spacing, origin and direction; Update() then also fills GetPointScalars() with
+   *  one double per point id: itk::LinearInterpolateImageFunction<TScalarImage, double>::Evaluate at the point's FINAL position
+   *  where that lies inside the image's buffer (index - 0.5 <= continuous index < index + size - 0.5 on every axis), and
+   *  SetPointScalarOutsideValue's value (default: a quiet NaN) elsewhere.  The output mesh's point data holds
+   *  static_cast<OutputPixelType>(value) per point.  A null pointer turns it off (the default: GetPointScalars() is empty and
+   *  the mesh has no point-data container).  The image's pixels are uploaded ONCE per call of SetPointScalarImage, by the next
+   *  Update(), and the filter holds a reference to the image until then: a caller who changes its pixels calls
+   *  SetPointScalarImage again.  Not offered with SetDevices of more than one device nor with an interpolator that takes the
+   *  host walk (the library never sees the final vertices): Update() throws an itk::ExceptionObject that says "point scalars".
+   *  Out of scope: nearest-neighbour and B-spline sampling of the second image, vector images, several second images. */
+  template <class TScalarImage> void SetPointScalarImage(const TScalarImage *image)
+  {
+    static_assert(TScalarImage::ImageDimension == 3, "SetPointScalarImage: the second image is three-dimensional, like the input");
+    m_PointScalarImage = image;
+    m_PointScalarVoxels = image ? static_cast<const void *>(image->GetBufferPointer()) : 0;
+    m_HasPointScalarImage = image != 0;
+    m_PointScalarDesc = ::cuberille_image_desc();
+    if (image) (void)cuberille_detail::DescribeImage(image, m_PointScalarDesc);      // (false: an empty region, which the library refuses by its dims)
+    m_PointScalarUploadedTo = 0;
+    this->Modified();
+  }
+  void SetPointScalarOutsideValue(double v) { m_PointScalarOutsideValue = v; m_PointScalarUploadedTo = 0; this->Modified(); }
+  double GetPointScalarOutsideValue() const { return m_PointScalarOutsideValue; }
+  const std::vector<double> &GetPointScalars() const { return m_PointScalars; }
+
   /** Not in the reference: what a caller of itk::ConnectedRegionsMeshFilter does behind the filter -- keep the largest surface,
    *  drop the specks -- on the device, before the output mesh is filled (cuberille_keep_components).
    *  KeepLargestComponentOn(): Update() keeps the one connected surface with the most cells (a tie goes to the component with
@@ -394,9 +424,16 @@ private:
   unsigned long long m_MinimumComponentCells;
   std::vector<uint32_t> m_PointComponents, m_CellComponents;   // filled by Update() with the switch on, else empty
   std::vector<uint64_t> m_ComponentCellCounts;
+  SmartPointer<const LightObject> m_PointScalarImage;   // SetPointScalarImage: the second image, held until its upload
+  const void *m_PointScalarVoxels;
+  ::cuberille_image_desc m_PointScalarDesc;
+  bool m_HasPointScalarImage;
+  double m_PointScalarOutsideValue;
+  ::cuberille_ctx *m_PointScalarUploadedTo;   // the context that holds the copy of the image as last set (null: none does)
+  std::vector<double> m_PointScalars;         // GetPointScalars(): filled by Update() with a second image set, else empty
   bool m_InsideBand;
   InputPixelType m_BandLower, m_BandUpper, m_BandInside, m_BandOutside;
-  void ClearAttributeOutputs();               // the five vectors above, emptied: how every Update() begins and how a throwing one ends
+  void ClearAttributeOutputs();               // the six vectors above, emptied: how every Update() begins and how a throwing one ends
   void BandArguments(double v[4], int64_t vi[4]) const;   // the four members as cuberille_set_band / _band_check take them
   // SetExtractionRegion as a position in the buffer `desc` describes: ITK index - the buffer's start index (all zero: none)
   void BufferBox(const ::cuberille_image_desc &desc, int64_t start[3], int64_t size[3]) const;

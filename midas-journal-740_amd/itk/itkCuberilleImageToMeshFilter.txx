@@ -11,6 +11,7 @@
 #include "cuberille_hip.h"
 
 #include <cmath>
+#include <limits>
 #include <cstdlib>
 #if defined(__linux__)
 #include <sys/mman.h>
@@ -505,6 +506,11 @@ CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::CuberilleIm
   m_GenerateComponents = false;
   m_KeepLargestComponent = false;
   m_MinimumComponentCells = 0;
+  m_PointScalarVoxels = 0;
+  m_PointScalarDesc = ::cuberille_image_desc();
+  m_HasPointScalarImage = false;
+  m_PointScalarOutsideValue = std::numeric_limits<double>::quiet_NaN();
+  m_PointScalarUploadedTo = 0;
   m_InsideBand = false;
   m_BandLower = m_BandUpper = NumericTraits<InputPixelType>::Zero;
   m_BandInside = NumericTraits<InputPixelType>::One;
@@ -593,6 +599,7 @@ bool CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Acquir
       return false;
       }
     m_ContextDevice = m_Device;
+    m_PointScalarUploadedTo = 0;              // (a new context holds no copy of the second image, whatever its address)
     (void)cuberille_warm_up(m_Context, 0, 0);
     }
   return true;
@@ -730,6 +737,13 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     itkExceptionMacro(<< "point normals (GeneratePointNormalsOn / cuberille_set_point_normals) are not offered with an interpolator "
                          "that takes the host walk: the library never sees the final vertices");
 
+  if (m_HasPointScalarImage && hostWalk)
+    itkExceptionMacro(<< "point scalars (SetPointScalarImage / cuberille_set_point_scalars) are not offered with an interpolator "
+                         "that takes the host walk: the library never sees the final vertices");
+  if (m_HasPointScalarImage && m_Devices.size() > 1)
+    itkExceptionMacro(<< "point scalars (SetPointScalarImage / cuberille_set_point_scalars) are not offered with SetDevices of "
+                         "more than one device: they belong to one context's whole volume");
+
   // InsideBandOn(): the four values against the pixel type by the library's validator (lower > upper: the threshold filter
   // throws there too), and on the device's walk
   if (m_InsideBand)
@@ -813,6 +827,19 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
       itkExceptionMacro(<< "cuberille_set_cell_pixels: " << cuberille_last_error(m_Context));
     if (cuberille_set_components(m_Context, components ? 1 : 0) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_set_components: " << cuberille_last_error(m_Context));
+    // SetPointScalarImage: one upload per call of it (and per context); off: the library frees its copy and the row
+    if (!m_HasPointScalarImage)
+      {
+      (void)cuberille_set_point_scalars(m_Context, 0, 0, CUBERILLE_MEM_HOST, 0.0);
+      m_PointScalarUploadedTo = 0;
+      }
+    else if (m_PointScalarUploadedTo != m_Context)
+      {
+      if (cuberille_set_point_scalars(m_Context, &m_PointScalarDesc, m_PointScalarVoxels, CUBERILLE_MEM_HOST,
+                                      m_PointScalarOutsideValue) != CUBERILLE_OK)
+        itkExceptionMacro(<< "cuberille_set_point_scalars: " << cuberille_last_error(m_Context));
+      m_PointScalarUploadedTo = m_Context;
+      }
     extractStart = cuberille_detail::WallSeconds();
     if (cuberille_extract_host(m_Context, &desc, image->GetBufferPointer(), &prm, &res) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_extract_host: " << cuberille_last_error(m_Context));
@@ -854,6 +881,13 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
     if (cuberille_cell_pixels_download(m_Context, m_CellPixels.empty() ? 0 : &m_CellPixels[0],
                                        m_CellPixels.size() * sizeof(InputPixelType)) != CUBERILLE_OK)
       itkExceptionMacro(<< "cuberille_cell_pixels_download: " << cuberille_last_error(m_Context));
+    }
+  if (m_HasPointScalarImage)                  // (the single context, the device's walk: the others were refused above)
+    {
+    m_PointScalars.resize(static_cast<size_t>(res.n_points));
+    if (cuberille_point_scalars_download(m_Context, m_PointScalars.empty() ? 0 : &m_PointScalars[0],
+                                         m_PointScalars.size() * sizeof(double)) != CUBERILLE_OK)
+      itkExceptionMacro(<< "cuberille_point_scalars_download: " << cuberille_last_error(m_Context));
     }
   if (components)                             // (the single context: a group has refused above)
     {
@@ -921,6 +955,10 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::Genera
   mesh->SetCellData(static_cast<typename OutputMeshType::CellDataContainer *>(0));
   for (size_t i = 0; i < m_CellPixels.size(); i++)
     mesh->SetCellData(static_cast<typename OutputMeshType::CellIdentifier>(i), static_cast<OutputPixelType>(m_CellPixels[i]));
+  // SetPointScalarImage: the value at each point as the mesh's point data; none set: the mesh has no point-data container
+  mesh->SetPointData(static_cast<typename OutputMeshType::PointDataContainer *>(0));
+  for (size_t i = 0; i < m_PointScalars.size(); i++)
+    mesh->SetPointData(static_cast<typename OutputMeshType::PointIdentifier>(i), static_cast<OutputPixelType>(m_PointScalars[i]));
   m_LastMeshFillSeconds = cuberille_detail::WallSeconds() - fillStart;
   if (m_ReleaseHostMeshAfterFill)
     {
@@ -938,6 +976,7 @@ void CuberilleImageToMeshFilter<TInputImage, TOutputMesh, TInterpolator>::ClearA
   m_PointComponents.clear();
   m_CellComponents.clear();
   m_ComponentCellCounts.clear();
+  m_PointScalars.clear();
 }
 
 template <class TInputImage, class TOutputMesh, class TInterpolator>

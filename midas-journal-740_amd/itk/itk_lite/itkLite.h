@@ -515,6 +515,7 @@ public:
   typedef VectorContainer<PointIdentifier, PointType> PointsContainer;
   typedef VectorContainer<CellIdentifier, CellType *> CellsContainer;
   typedef VectorContainer<CellIdentifier, CellPixelType> CellDataContainer;
+  typedef VectorContainer<PointIdentifier, PixelType> PointDataContainer;
 };
 
 // itk::DefaultDynamicMeshTraits: the same names, points and cells in MapContainers
@@ -527,6 +528,7 @@ public:
   typedef MapContainer<typename Base::PointIdentifier, typename Base::PointType> PointsContainer;
   typedef MapContainer<typename Base::CellIdentifier, typename Base::CellType *> CellsContainer;
   typedef MapContainer<typename Base::CellIdentifier, typename Base::CellPixelType> CellDataContainer;
+  typedef MapContainer<typename Base::PointIdentifier, typename Base::PixelType> PointDataContainer;
 };
 
 template <class TPixelType, class TCellTraits> class CellInterface {
@@ -605,6 +607,8 @@ public:
   typedef typename MeshTraits::CellPixelType CellPixelType;
   typedef typename MeshTraits::CellDataContainer CellDataContainer;
   typedef typename CellDataContainer::Pointer CellDataContainerPointer;
+  typedef typename MeshTraits::PointDataContainer PointDataContainer;
+  typedef typename PointDataContainer::Pointer PointDataContainerPointer;
 
   PointsContainer *GetPoints() { if (m_Points.IsNull()) m_Points = PointsContainer::New(); return m_Points; }
   CellsContainer *GetCells() { if (m_Cells.IsNull()) m_Cells = CellsContainer::New(); return m_Cells; }
@@ -642,12 +646,23 @@ public:
     *v = m_CellData->GetElement(id);
     return true;
   }
+  // point data as itk::PointSet keeps it: likewise a container of its own, null until the first SetPointData(id, value)
+  void SetPointData(PointIdentifier id, PixelType v) { if (m_PointData.IsNull()) m_PointData = PointDataContainer::New(); m_PointData->InsertElement(id, v); }
+  bool GetPointData(PointIdentifier id, PixelType *v) const {
+    if (m_PointData.IsNull() || !m_PointData->IndexExists(id)) return false;
+    *v = m_PointData->GetElement(id);
+    return true;
+  }
+  PointDataContainer *GetPointData() { return m_PointData.GetPointer(); }
+  const PointDataContainer *GetPointData() const { return m_PointData.GetPointer(); }
+  void SetPointData(PointDataContainer *data) { if (m_PointData.GetPointer() != data) { m_PointData = data; this->Modified(); } }
   CellDataContainer *GetCellData() { return m_CellData.GetPointer(); }
   const CellDataContainer *GetCellData() const { return m_CellData.GetPointer(); }
   void SetCellData(CellDataContainer *data) { if (m_CellData.GetPointer() != data) { m_CellData = data; this->Modified(); } }
   virtual void Initialize() {
     ReleaseCellsMemory();
     m_CellData = 0;
+    m_PointData = 0;
     m_CellsAllocationMethod = CellsAllocatedDynamicallyCellByCell;
     if (m_Points.IsNotNull()) m_Points->Initialize();
   }
@@ -665,6 +680,7 @@ protected:
   PointsContainerPointer m_Points;
   CellsContainerPointer m_Cells;
   CellDataContainerPointer m_CellData;
+  PointDataContainerPointer m_PointData;
   CellsAllocationMethodType m_CellsAllocationMethod;
 };
 
